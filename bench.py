@@ -58,6 +58,9 @@ def parse():
     ap.add_argument("--transport", choices=["rccl", "tcp"], default=None,
                     help="data plane of an N > 1 run: rccl (default), or tcp = the same messages through the library's host mesh, "
                          "for ranks that share a GPU (rehearsal on a one-GPU box); also HEMOCELL_TRANSPORT")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (a fixed, seeded sample of the lattice and the cell vertices) "
+                         "as DIR/<name>.npy, for comparing two builds output for output")
     return ap.parse_args()
 
 
@@ -250,6 +253,47 @@ def target_512(args, steps=25, warmup=5):
     return out
 
 
+DUMP_NODES, DUMP_VERTICES, DUMP_SEED = 1 << 17, 1 << 18, 20261015
+
+
+def dump_outputs(runner, out_dir, rank, world):
+    """--dump-outputs: the state the timed steps leave to their caller, on this rank's slab, as float64 .npy files (about
+    50 MB in all; names get a .rank<r> suffix when world > 1).  Fluid: post-stream populations (f - t_i), density and
+    velocity at DUMP_NODES nodes drawn with a fixed seed (sample_nodes: their indices in the order z + nz*(y + ny*x)).
+    Cells: vertex position, velocity and force of whole cells drawn with a fixed seed per cell (type, id) up to
+    DUMP_VERTICES vertices, sorted by vertex_key = (cell type, cell id, vertex id)."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    pop = runner.populations()
+    n = len(pop)
+    nodes = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_NODES), replace=False))
+    out["populations"] = pop[nodes]
+    del pop
+    rho, u = runner.lattice.rho_u()
+    out["sample_nodes"], out["density"], out["velocity"] = nodes.astype(np.float64), rho[nodes], u[nodes]
+    del rho, u
+    if runner.cells is not None:
+        rec = runner.cells.records()
+        rec = rec[np.lexsort((rec["vertexId"], rec["cellId"], rec["celltype"]))]
+        cells, first, size = np.unique(rec["celltype"].astype(np.int64) << 40 | rec["cellId"], return_index=True, return_counts=True)
+        draw = np.empty(len(cells))
+        for t in np.unique(cells >> 40):
+            sel = (cells >> 40) == t
+            ids = cells[sel] & ((1 << 40) - 1)
+            draw[sel] = np.random.default_rng([DUMP_SEED, int(t)]).random(int(ids.max()) + 1)[ids]   # same draw for a cell id whatever the others
+        order = np.argsort(draw, kind="stable")
+        take = np.sort(order[:np.searchsorted(np.cumsum(size[order]), DUMP_VERTICES, side="right")])
+        rows = np.concatenate([np.arange(first[c], first[c] + size[c]) for c in take]) if len(take) else np.zeros(0, np.int64)
+        rec = rec[rows]
+        out["vertex_key"] = np.stack([rec["celltype"], rec["cellId"], rec["vertexId"]], axis=1).astype(np.float64)
+        out["vertex_position"], out["vertex_velocity"], out["vertex_force"] = rec["position"], rec["v"], rec["force"]
+    suffix = ".rank%d" % rank if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    print("bench.py: outputs of the last timed step in %s: %s" % (out_dir, ", ".join("%s%s %s" % (k, suffix, v.shape) for k, v in out.items())),
+          file=sys.stderr)
+
+
 def launch_ranks(args):
     """plain `python bench.py --gpus N`: start the N ranks as child processes (one per GPU, nothing in this process has
     touched the GPU), hand rank 0's stdout through, fail if any rank fails"""
@@ -353,6 +397,8 @@ def main():
         m2, n2 = C.c_double(), C.c_long()
         host.check(lib.hc_profile_read(k.encode(), C.byref(m2), C.byref(n2)))
         prof[k] = {"ms_total": m2.value, "launches": n2.value}
+    if args.dump_outputs:
+        dump_outputs(runner, args.dump_outputs, rank, world)
     # After the timed region: the dominant kernel with the GPU to itself (inside the timed region four launches of five share
     # it with advance and the next spread on the side stream)
     alone_ms = None

@@ -1,6 +1,6 @@
 """python examples/pipe/run_reference_pipeflow_config3.py [workdir]
 
-BASELINE config 3 geometry on one GPU through the reference's OWN driver: build/ref_drivers/pipeflow_nohdf5 is
+BASELINE config 3 geometry on one GPU through the reference's OWN driver: oracle/_ref/pipeflow_nohdf5 is
 examples/pipeflow/pipeflow.cpp of the reference tree, compiled unchanged against the facade by __graft_entry__.build()
 (without the HDF5 writers: at this size every writeOutput() would compress about 1 GB).  Inputs: the reference's
 tube.stl, RBC.xml, PLT.xml and config.xml from tests/golden/pipeflow_case with refDirN raised from 50 to 254, which
@@ -24,9 +24,9 @@ NX, NY = 2 * REF_N + 3, REF_N + 3
 
 def main():
     work = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "examples", "pipe", "tmp_config3")
-    drv = os.path.join(ROOT, "build", "ref_drivers", "pipeflow_nohdf5")
+    drv = os.path.join(ROOT, "oracle", "_ref", "pipeflow_nohdf5")
     if not os.path.exists(drv):
-        sys.exit("build/ref_drivers/pipeflow_nohdf5 is missing: run __graft_entry__.build() where the reference tree is present")
+        sys.exit("oracle/_ref/pipeflow_nohdf5 is missing: run __graft_entry__.build() where the reference tree is present")
     os.makedirs(work, exist_ok=True)
     for name in ("tube.stl", "RBC.xml", "PLT.xml"):
         shutil.copy(os.path.join(CASE, name), os.path.join(work, name))

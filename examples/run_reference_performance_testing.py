@@ -1,6 +1,6 @@
 """python examples/run_reference_performance_testing.py [workdir] [tmax]
 
-The reference's own performance harness on one GPU: build/ref_drivers/performance_testing_nohdf5 is
+The reference's own performance harness on one GPU: oracle/_ref/performance_testing_nohdf5 is
 cases/performance_testing/performance_testing.cpp of the reference tree, compiled unchanged against the facade by
 __graft_entry__.build() (without the HDF5 writers), run on the reference's inputs for the 1-rank case of its 33 %
 hematocrit strong-scaling series (tests/golden/performance_case: config_1.xml, RBC.xml, RBC.pos with 10 935 cells;
@@ -20,9 +20,9 @@ CASE = os.path.join(ROOT, "tests", "golden", "performance_case")
 def main():
     work = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "examples", "tmp_performance_testing")
     tmax_long = int(sys.argv[2]) if len(sys.argv) > 2 else 500      # config_1.xml: 500
-    drv = os.path.join(ROOT, "build", "ref_drivers", "performance_testing_nohdf5")
+    drv = os.path.join(ROOT, "oracle", "_ref", "performance_testing_nohdf5")
     if not os.path.exists(drv):
-        sys.exit("build/ref_drivers/performance_testing_nohdf5 is missing: run __graft_entry__.build() where the reference tree is present")
+        sys.exit("oracle/_ref/performance_testing_nohdf5 is missing: run __graft_entry__.build() where the reference tree is present")
     os.makedirs(work, exist_ok=True)
     for name in ("RBC.xml", "RBC.pos"):
         shutil.copy(os.path.join(CASE, name), os.path.join(work, name))

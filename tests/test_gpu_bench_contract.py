@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,8 +19,8 @@ def _run(args):
     return json.loads(lines[0])
 
 
-def test_bench_line_small_pipe(gpu):
-    j = _run(["--nx", "64", "--ny", "66", "--nz", "66", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2"])
+def test_bench_line_small_pipe(gpu, tmp_path):
+    j = _run(["--nx", "64", "--ny", "66", "--nz", "66", "--steps", "20", "--warmup", "5", "--cpu-seconds", "2", "--dump-outputs", str(tmp_path)])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in j, key
@@ -50,6 +51,13 @@ def test_bench_line_small_pipe(gpu):
     k = j["kernel_ms"]
     assert k["collide_stream_alone"]["launches"] + k["collide_stream_beside"]["launches"] == 20
     assert k["collide_stream_beside"]["launches"] > 0 and k["ibm_interpolate"]["launches"] == 4
+    # --dump-outputs: the state after the last timed step, float64, at most 64 MB, a seeded sample of the 278 784 nodes
+    d = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert sorted(d) == ["density", "populations", "sample_nodes", "velocity", "vertex_force", "vertex_key", "vertex_position", "vertex_velocity"]
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    assert d["populations"].shape == (len(d["sample_nodes"]), 19) and len(d["sample_nodes"]) == 1 << 17
+    assert d["vertex_position"].shape == d["vertex_key"].shape and 0 < len(d["vertex_key"]) <= j["config"]["vertices"]
+    assert (np.abs(d["velocity"]).max() > 0) and abs(d["density"].mean() - 1.0) < 0.1
 
 
 @pytest.mark.parametrize("launcher", ["self", "torchrun", "self-auto"])

@@ -361,13 +361,13 @@ def test_moving_wall_couette_vs_oracle(orc, gpu):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # The reference's OWN drivers (examples/pipeflow/pipeflow.cpp, examples/stretchCell/stretchCell.cpp), compiled unchanged
-# against the facade by __graft_entry__.build_reference_drivers() in the build container (the reference tree does not
+# against the facade by __graft_entry__.build() into oracle/_ref/ where the reference tree is present (it does not
 # travel), run here on its own CI inputs (tests/golden/*_case: the config of scripts/ci, the XML / .pos / .stl files of
 # the example) and judged by its own CI scripts, restated line by line.
 def _ref_driver(name):
-    exe = os.path.join(ROOT, "build", "ref_drivers", name)
+    exe = os.path.join(ROOT, "oracle", "_ref", name)
     if not os.path.exists(exe):
-        pytest.skip("build/ref_drivers/%s not built (needs the reference tree at build time)" % name)
+        pytest.skip("oracle/_ref/%s not built (needs the reference tree at build time)" % name)
     return exe
 
 
@@ -713,9 +713,9 @@ def test_reference_performance_testing_driver_runs_its_1_rank_case(tmp_path, gpu
     velocities interpolated every step).  The reference holds no known answer for this case: the checks are that every
     cell of the .pos file that lies in the 128 um domain is placed and none is lost, and that the flow responds to the
     body force (statistics printed by the driver itself)."""
-    drv = os.path.join(ROOT, "build", "ref_drivers", "performance_testing_nohdf5")
+    drv = os.path.join(ROOT, "oracle", "_ref", "performance_testing_nohdf5")
     if not os.path.exists(drv):
-        pytest.skip("build/ref_drivers/performance_testing_nohdf5 is built by __graft_entry__.build() where the reference tree is present")
+        pytest.skip("oracle/_ref/performance_testing_nohdf5 is built by __graft_entry__.build() where the reference tree is present")
     import re
     import shutil
     case = os.path.join(ROOT, "tests", "golden", "performance_case")
