@@ -31,6 +31,12 @@ class Material(C.Structure):
                 ("aspect_ratio", C.c_double), ("inner_edges", c_long_p), ("n_inner", C.c_int)]
 
 
+class WbcMaterial(C.Structure):
+    """hc_wbc_material == the extra <MaterialModel> tags of WBC_HO.xml (SI units)"""
+    _fields_ = [("kInnerRigid", C.c_double), ("kCytoskeleton", C.c_double), ("coreRadius", C.c_double),
+                ("radius", C.c_double)]
+
+
 # every symbol include/hemocell_amd.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
 SIGNATURES = {
@@ -101,6 +107,9 @@ SIGNATURES = {
     "hcl_mlups_bytes_per_node": (C.c_double, [VP]),
     "hc_params_base": (C.c_int, [C.POINTER(Params)] + [C.c_double] * 5),
     "hcp_celltype_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Material)]),
+    "hcp_celltype_create_wbc": (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(Params), C.POINTER(Material),
+                                          C.POINTER(WbcMaterial)]),
+    "hcp_celltype_wbc_constants": (C.c_int, [VP, c_double_p]),
     "hcp_celltype_destroy": (C.c_int, [VP]),
     "hcp_celltype_sizes": (C.c_int, [VP, c_int_p]),
     "hcp_celltype_tables": (C.c_int, [VP, c_double_p, c_long_p, c_long_p, c_double_p, c_double_p, c_double_p,

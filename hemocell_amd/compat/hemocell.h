@@ -380,6 +380,25 @@ class DeviceMechanics : private DeviceModelTag<MODEL>, public CellMechanics {
 typedef DeviceMechanics<HC_MODEL_RBC_HO> RbcHighOrderModel;   // mechanics/rbcHighOrderModel.h
 typedef DeviceMechanics<HC_MODEL_PLT_SIMPLE> PltSimpleModel;  // mechanics/pltSimpleModel.h
 
+// mechanics/wbcHighOrderModel.h: the RBC_HO laws plus the inner-link law, evaluated by mechanics_kernel<HC_MODEL_WBC_HO>;
+// the four extra constants come from the <MaterialModel> tags create_device_type reads for this model
+class WbcHighOrderModel : public DeviceMechanics<HC_MODEL_WBC_HO> {
+ public:
+  WbcHighOrderModel(Config &modelCfg_, HemoCellField &field) : DeviceMechanics<HC_MODEL_WBC_HO>(modelCfg_, field) {
+    double w[4];
+    hc_check(hcp_celltype_wbc_constants(field.dev, w), "hcp_celltype_wbc_constants");
+    k_inner_rigid = w[0]; k_cytoskeleton = w[1]; core_radius = w[2]; radius = w[3];
+  }
+  void statistics() override {   // mechanics/wbcHighOrderModel.cpp:227-238
+    hlog << "(Cell-mechanics model) High Order model parameters for " << cellField.name << " cellfield" << endl;
+    hlog << "\t k_link:   " << k_link << endl << "\t k_area:   " << k_area << endl << "\t k_bend: : " << k_bend << endl
+         << "\t k_volume: " << k_volume << endl << "\t k_cytoskeleton: " << k_cytoskeleton << endl
+         << "\t k_inner_rigid: " << k_inner_rigid << endl << "\t eta_m:    " << eta_m << endl
+         << "\t wbc_radius:    " << radius << endl << "\t core_radius:    " << core_radius << endl;
+  }
+  T k_inner_rigid = 0, k_cytoskeleton = 0, core_radius = 0, radius = 0;
+};
+
 // ------------------------------------------------------------------ core/hemoCellParticleField.h:39-207
 // The reference keeps std::vector<HemoCellParticle> per atomic block; here the vertices live on the GPU and this object is
 // a host VIEW of this rank's block: refresh() fills `particles` from the device in the reference's record
@@ -694,8 +713,15 @@ inline void HemoCellField::create_device_type(int model) {
   } catch (std::invalid_argument &) {}
   M.inner_edges = inner.empty() ? nullptr : inner.data(); M.n_inner = (int)inner.size() / 2;
   innerEdges = inner;
-  if (constructType != RBC_FROM_SPHERE && constructType != ELLIPSOID_FROM_SPHERE) { hlog << "(HemoCell) (AddCellType) construct type " << constructType << " is not supported by the GPU back end" << endl; std::exit(1); }
-  hc_check(hcp_celltype_create(&dev, model, constructType, &Parameters::raw(), &M), "hcp_celltype_create");
+  if (constructType != WBC_SPHERE && constructType != RBC_FROM_SPHERE && constructType != ELLIPSOID_FROM_SPHERE) { hlog << "(HemoCell) (AddCellType) construct type " << constructType << " is not supported by the GPU back end" << endl; std::exit(1); }
+  if (model == HC_MODEL_WBC_HO) {   // WbcHighOrderModel::calculate_* (mechanics/wbcHighOrderModel.cpp:242-262)
+    hc_wbc_material W;
+    W.kInnerRigid = m["MaterialModel"]["kInnerRigid"].read<T>(); W.kCytoskeleton = m["MaterialModel"]["kCytoskeleton"].read<T>();
+    W.coreRadius = m["MaterialModel"]["coreRadius"].read<T>(); W.radius = m["MaterialModel"]["radius"].read<T>();
+    hc_check(hcp_celltype_create_wbc(&dev, constructType, &Parameters::raw(), &M, &W), "hcp_celltype_create_wbc");
+  } else {
+    hc_check(hcp_celltype_create(&dev, model, constructType, &Parameters::raw(), &M), "hcp_celltype_create");
+  }
   int sz[4]; hcp_celltype_sizes(dev, sz);
   numVertex = sz[0]; numTriangles = sz[1];
   vertices.resize(3 * (size_t)sz[0]); triangles.resize(3 * (size_t)sz[1]);

@@ -235,16 +235,13 @@ void host_append_state(hc_cells *C, int type, long cell_id) {
   C->host_dirty = true;
 }
 
-}  // namespace hcc
-
-extern "C" {
-
-int hcp_celltype_create(hc_celltype **out, int model, int shape, const hc_params *P, const hc_material *M) {
-  HC_REQUIRE(out && P && M, "hcp_celltype_create: null pointer");
-  if (hc::stream() == nullptr) { hc::set_error("hcp_celltype_create: hc_init() has not been called"); return HC_ERR_STATE; }
+// hcp_celltype_create / hcp_celltype_create_wbc: mesh, tables and moduli on the host, then the tables to the device
+int celltype_create(const char *fn, hc_celltype **out, int model, int shape, const hc_params *P, const hc_material *M,
+                    const hc_wbc_material *W) {
+  if (hc::stream() == nullptr) { hc::set_error(std::string(fn) + ": hc_init() has not been called"); return HC_ERR_STATE; }
   hc_celltype *T = new hc_celltype();
-  std::string err = build_cell_tables(T->host, model, shape, *P, *M);
-  if (!err.empty()) { delete T; hc::set_error("hcp_celltype_create: " + err); return HC_ERR_ARG; }
+  std::string err = build_cell_tables(T->host, model, shape, *P, *M, W);
+  if (!err.empty()) { delete T; hc::set_error(std::string(fn) + ": " + err); return HC_ERR_ARG; }
   const CellTables &H = T->host;
   int rc = HC_OK;
   auto up_i = [&](int **d, const std::vector<int> &v) { if (rc == HC_OK) rc = upload_vec(d, v); };
@@ -259,6 +256,28 @@ int hcp_celltype_create(hc_celltype **out, int model, int shape, const hc_params
   up_d(&T->d_edge_angle_eq, H.edge_angle_eq); up_d(&T->d_patch_eq, H.patch_dist_eq); up_d(&T->d_iedge_len_eq, H.inner_edge_length_eq);
   if (rc != HC_OK) return rc;
   *out = T;
+  return HC_OK;
+}
+
+}  // namespace hcc
+
+extern "C" {
+
+int hcp_celltype_create(hc_celltype **out, int model, int shape, const hc_params *P, const hc_material *M) {
+  HC_REQUIRE(out && P && M, "hcp_celltype_create: null pointer");
+  HC_REQUIRE(model != HC_MODEL_WBC_HO, "hcp_celltype_create: HC_MODEL_WBC_HO needs its inner-link constants: use hcp_celltype_create_wbc");
+  return hcc::celltype_create("hcp_celltype_create", out, model, shape, P, M, nullptr);
+}
+
+int hcp_celltype_create_wbc(hc_celltype **out, int shape, const hc_params *P, const hc_material *M, const hc_wbc_material *W) {
+  HC_REQUIRE(out && P && M && W, "hcp_celltype_create_wbc: null pointer");
+  return hcc::celltype_create("hcp_celltype_create_wbc", out, HC_MODEL_WBC_HO, shape, P, M, W);
+}
+
+int hcp_celltype_wbc_constants(const hc_celltype *T, double out[4]) {
+  HC_REQUIRE(T && out, "hcp_celltype_wbc_constants: null pointer");
+  const CellTables &H = T->host;
+  out[0] = H.k_inner_rigid; out[1] = H.k_cytoskeleton; out[2] = H.core_radius; out[3] = H.wbc_radius;
   return HC_OK;
 }
 

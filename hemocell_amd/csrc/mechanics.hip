@@ -1,8 +1,8 @@
-// Membrane mechanics on the GPU: rbcHighOrderModel and pltSimpleModel forces, per-cell information.
+// Membrane mechanics on the GPU: rbcHighOrderModel, wbcHighOrderModel and pltSimpleModel forces, per-cell information.
 //
 // Replaces (file:line in the HemoCell tree):
 //   core/hemoCellParticleField.cpp:633-675        applyConstitutiveModel
-//   mechanics/rbcHighOrderModel.cpp:38-207, mechanics/pltSimpleModel.cpp:44-208
+//   mechanics/rbcHighOrderModel.cpp:38-207, mechanics/wbcHighOrderModel.cpp:42-225, mechanics/pltSimpleModel.cpp:44-208
 //   helper/cellInfo.cpp                           volume, area, position, bounding box per cell
 //
 // The membrane models are evaluated in GATHER form: one workgroup per cell,
@@ -29,6 +29,8 @@ struct MechArgs {
   double *comp;        // optional [6][ncells*nv][3]
   long ncv;            // ncells*nv (stride of comp)
   const int *tag;      // per cell of this type: 0 complete, 1 gone, 2 incomplete
+  // WBC only (wbcHighOrderModel.cpp:242-262), lattice units; last so that the other models' argument layout is unchanged
+  double k_inner_rigid, k_cytoskeleton, core_radius, radius;
 };
 
 #define MaxCellVolumetricChange 0.01   // config/constant_defaults.h:157-173
@@ -63,12 +65,14 @@ __device__ __forceinline__ double tri_signed_volume(const double *xs, const doub
   return (-v210 + v120 + v201 - v021 - v102 + v012);
 }
 
-// one workgroup = one cell.  LDS: positions and the per-triangle signed-volume terms; RBC: per-vertex bending vector;
+// one workgroup = one cell.  LDS: positions and the per-triangle signed-volume terms; RBC / WBC: per-vertex bending vector;
 // PLT (small mesh): per-triangle {area, unit normal, area-force magnitude} and per-edge {link, visc, bending} vectors.
+// WBC_HO is the RBC_HO path with the membrane viscosity always evaluated, followed by the two-threshold inner links.
 template <int MODEL, bool SEPARATE>
 __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
   extern __shared__ double lds[];
-  constexpr bool PLT = MODEL != HC_MODEL_RBC_HO;
+  constexpr bool PLT = MODEL == HC_MODEL_PLT_SIMPLE;
+  constexpr bool WBC = MODEL == HC_MODEL_WBC_HO;
   const int nv = m.nv, nt = m.nt, ne = m.ne;
   double *xs = lds, *ys = xs + nv, *zs = ys + nv;
   double *tV = zs + nv;
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
     s_volume_force = -m.k_volume * vf / fabs(MaxCellVolumetricChange - vf * vf);
   }
 
-  if (MODEL == HC_MODEL_RBC_HO) {
+  if (!PLT) {
     // ---- per-vertex bending vector (rbcHighOrderModel.cpp:127-160)
     double *Bx = ex, *By = ex + nv, *Bz = ex + 2 * nv;
     for (int i = tid; i < nv; i += nth) {
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
       const double sc = g.area / m.area_mean_eq;
       ACC(0)[0] += (volume_force * g.nx) * sc; ACC(0)[1] += (volume_force * g.ny) * sc; ACC(0)[2] += (volume_force * g.nz) * sc;
     }
-    if (MODEL == HC_MODEL_RBC_HO) {
+    if (!PLT) {
       const double *Bx = ex, *By = ex + nv, *Bz = ex + 2 * nv;
       for (int k = 0; k < MD; k++) {  // bending: own vector, or -B/n of a ring neighbour, ascending source id
         const int src = m.bsrc[MD * i + k];
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
         if (src == i) { ACC(2)[0] += Bx[i]; ACC(2)[1] += By[i]; ACC(2)[2] += Bz[i]; }
         else { const int nn = m.nring[src]; ACC(2)[0] += -Bx[src] / nn; ACC(2)[1] += -By[src] / nn; ACC(2)[2] += -Bz[src] / nn; }
       }
-      for (int k = 0; k < MD; k++) {  // links (rbcHighOrderModel.cpp:169-204)
+      for (int k = 0; k < MD; k++) {  // links (rbcHighOrderModel.cpp:169-204, wbcHighOrderModel.cpp:166-198)
         const int e = m.vedge[MD * i + k];
         if (e < 0) break;
         const int e0 = m.edge[2 * e], e1 = m.edge[2 * e + 1];
@@ -224,13 +228,34 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
         const double frx = ux * fs, fry = uy * fs, frz = uz * fs;
         const bool first = m.vedge_s[MD * i + k] > 0;
         if (first) { ACC(3)[0] += frx; ACC(3)[1] += fry; ACC(3)[2] += frz; } else { ACC(3)[0] -= frx; ACC(3)[1] -= fry; ACC(3)[2] -= frz; }
-        if (m.eta_m != 0.0) {
+        if (WBC || m.eta_m != 0.0) {   // the WBC model has no eta_m test (wbcHighOrderModel.cpp:183-197)
           const double rvx = m.vx[base + e1] - m.vx[base + e0], rvy = m.vy[base + e1] - m.vy[base + e0], rvz = m.vz[base + e1] - m.vz[base + e0];
           const double pr = dot3(rvx, rvy, rvz, ux, uy, uz);
           double wx = m.eta_m * (pr * ux), wy = m.eta_m * (pr * uy), wz = m.eta_m * (pr * uz);
           const double wm = norm3(wx, wy, wz);
           if (wm > FORCE_LIMIT_PN / 4.0) { const double sc = (FORCE_LIMIT_PN / 4.0) / wm; wx *= sc; wy *= sc; wz *= sc; }
           if (first) { ACC(4)[0] += wx; ACC(4)[1] += wy; ACC(4)[2] += wz; } else { ACC(4)[0] -= wx; ACC(4)[1] -= wy; ACC(4)[2] -= wz; }
+        }
+      }
+      if (WBC) {
+        // inner links (wbcHighOrderModel.cpp:199-223), ascending inner-edge id: edge[0] receives -f, edge[1] +f, the
+        // cytoskeleton term and the rigid-core term added one after the other as the scatter loop adds them
+        const double d_cyto = 2 * m.radius, d_core = 2 * m.core_radius;
+        for (int k = 0; k < MD; k++) {
+          const int e = m.vinner[MD * i + k];
+          if (e < 0) break;
+          const int e0 = m.iedge[2 * e], e1 = m.iedge[2 * e + 1];
+          const double evx = xs[e1] - xs[e0], evy = ys[e1] - ys[e0], evz = zs[e1] - zs[e0];
+          const double el = norm3(evx, evy, evz);
+          const double ux = evx / el, uy = evy / el, uz = evz / el;
+          const bool first = m.vinner_s[MD * i + k] > 0;
+          for (int term = 0; term < 2; term++) {   // cytoskeleton (l < 2 radius), then rigid core (l < 2 core_radius)
+            const double d = term == 0 ? d_cyto : d_core, kk = term == 0 ? m.k_cytoskeleton : m.k_inner_rigid;
+            if (!(el < d)) continue;
+            const double s = 1.0 - (el / d);
+            const double frx = (ux * s) * kk, fry = (uy * s) * kk, frz = (uz * s) * kk;
+            if (first) { ACC(5)[0] -= frx; ACC(5)[1] -= fry; ACC(5)[2] -= frz; } else { ACC(5)[0] += frx; ACC(5)[1] += fry; ACC(5)[2] += frz; }
+          }
         }
       }
     } else {
@@ -337,11 +362,12 @@ static MechArgs mech_args(const hc_cells *C, int t) {
   m.fx = C->frc[0] + f; m.fy = C->frc[1] + f; m.fz = C->frc[2] + f;
   m.comp = nullptr; m.ncv = C->ncells[t] * T->host.nv;
   m.tag = C->d_tag + C->cell0[t];
+  m.k_inner_rigid = T->host.k_inner_rigid; m.k_cytoskeleton = T->host.k_cytoskeleton; m.core_radius = T->host.core_radius; m.radius = T->host.wbc_radius;
   return m;
 }
 
 static size_t mech_lds_bytes(const CellTables &T) {
-  if (T.model == HC_MODEL_RBC_HO) return (6 * (size_t)T.nv + (size_t)T.nt) * sizeof(double);   // positions, bending vectors, signed-volume terms
+  if (T.model != HC_MODEL_PLT_SIMPLE) return (6 * (size_t)T.nv + (size_t)T.nt) * sizeof(double);   // positions, bending vectors, signed-volume terms
   return (3 * (size_t)T.nv + 6 * (size_t)T.nt + 9 * (size_t)T.ne) * sizeof(double);
 }
 
@@ -360,6 +386,7 @@ static int launch_mechanics(hc_cells *C, int t, double *comp) {
     hipLaunchKernelGGL((mechanics_kernel<MODEL, SEP>), grid, dim3(threads), lds, hc::stream(), m);                \
   } while (0)
   if (T.model == HC_MODEL_RBC_HO) { if (comp) LAUNCH(HC_MODEL_RBC_HO, true); else LAUNCH(HC_MODEL_RBC_HO, false); }
+  else if (T.model == HC_MODEL_WBC_HO) { if (comp) LAUNCH(HC_MODEL_WBC_HO, true); else LAUNCH(HC_MODEL_WBC_HO, false); }
   else { if (comp) LAUNCH(HC_MODEL_PLT_SIMPLE, true); else LAUNCH(HC_MODEL_PLT_SIMPLE, false); }
 #undef LAUNCH
   HC_HIP(hipGetLastError());

@@ -1,6 +1,6 @@
 // Cell-type construction on the host: mesh generation, equilibrium tables,
 // moduli.  Mirrors (does not copy) the reference's setup path:
-//   helper/meshGeneratingFunctions.hh:32-271   sphere -> RBC / ellipsoid surface
+//   helper/meshGeneratingFunctions.hh:32-271   sphere -> WBC sphere / RBC / ellipsoid surface
 //   core/hemoCellField.cpp:38-118              triangle list from the mesh
 //   mechanics/commonCellConstants.cpp:70-409   equilibrium tables
 //   mechanics/cellMechanics.h:50-78            moduli in lattice units
@@ -102,7 +102,12 @@ std::vector<Tri> octasphere(long min_triangles) {
 
 void build_mesh(CellTables &T, int shape, double radius, long min_triangles, double aspect) {
   std::vector<Tri> t;
-  if (shape == HC_SHAPE_RBC_FROM_SPHERE) {
+  if (shape == HC_SHAPE_WBC_SPHERE) {
+    // constructSphereIcosahedron(centre 0, radius), helper/meshGeneratingFunctions.h:73-74 and .hh:32-150: the unit
+    // icosphere scaled by the radius, no rotation
+    t = icosphere(min_triangles);
+    for (auto &tr : t) for (auto &p : tr.p) for (int d = 0; d < 3; d++) p[d] *= radius;
+  } else if (shape == HC_SHAPE_RBC_FROM_SPHERE) {
     // constructRBCFromSphere, helper/meshGeneratingFunctions.hh:217-243
     t = icosphere(min_triangles);
     rotate_zxz(t, kPi / 2.0, kPi / 2.0, 0.);
@@ -178,9 +183,11 @@ void rotation_matrix_xyz(double alpha, double beta, double gamma, double a[3][3]
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { a[i][j] = 0; for (int k = 0; k < 3; k++) a[i][j] += c[k][j] * b[i][k]; }
 }
 
-std::string build_cell_tables(CellTables &T, int model, int shape, const hc_params &P, const hc_material &M) {
-  if (model != HC_MODEL_RBC_HO && model != HC_MODEL_PLT_SIMPLE) return "unknown mechanics model";
-  if (shape != HC_SHAPE_RBC_FROM_SPHERE && shape != HC_SHAPE_ELLIPSOID_FROM_SPHERE) return "unsupported construct type";
+std::string build_cell_tables(CellTables &T, int model, int shape, const hc_params &P, const hc_material &M,
+                              const hc_wbc_material *W) {
+  if (model != HC_MODEL_RBC_HO && model != HC_MODEL_PLT_SIMPLE && model != HC_MODEL_WBC_HO) return "unknown mechanics model";
+  if (model == HC_MODEL_WBC_HO && !W) return "the WBC_HO model needs its hc_wbc_material";
+  if (shape != HC_SHAPE_WBC_SPHERE && shape != HC_SHAPE_RBC_FROM_SPHERE && shape != HC_SHAPE_ELLIPSOID_FROM_SPHERE) return "unsupported construct type";
   if (!(M.radius > 0) || M.min_triangles < 8) return "material: radius must be > 0 and min_triangles >= 8";
   T.model = model;
   build_mesh(T, shape, M.radius / P.dx, M.min_triangles, M.aspect_ratio);
@@ -343,6 +350,12 @@ std::string build_cell_tables(CellTables &T, int model, int shape, const hc_para
   T.k_volume = M.kVolume * NfacesScaling * P.kBT_lbm / eqLength;
   T.k_area = M.kArea * NfacesScaling * P.kBT_lbm / (eqLength);
   T.eta_m = M.eta_m * P.dx / P.dt / P.df;
+  if (model == HC_MODEL_WBC_HO) {   // mechanics/wbcHighOrderModel.cpp:242-262
+    T.k_inner_rigid = W->kInnerRigid / P.df;
+    T.k_cytoskeleton = W->kCytoskeleton / P.df;
+    T.core_radius = W->coreRadius / P.dx;
+    T.wbc_radius = W->radius / P.dx;
+  }
   return "";
 }
 

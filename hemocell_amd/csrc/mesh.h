@@ -2,6 +2,7 @@
 // tables in gather form, moduli.  Product code (not the oracle).
 #pragma once
 #include <array>
+#include <string>
 #include <vector>
 #include "../../include/hemocell_amd.h"
 
@@ -24,6 +25,7 @@ struct CellTables {
   double volume_eq = 0, area_mean_eq = 0, edge_mean_eq = 0, angle_mean_eq = 0;
   double diameter = 0;                         // of the undeformed mesh, lattice units
   double k_volume = 0, k_area = 0, k_link = 0, k_bend = 0, eta_m = 0;
+  double k_inner_rigid = 0, k_cytoskeleton = 0, core_radius = 0, wbc_radius = 0;   // WBC_HO only, lattice units
 
   // ---- gather form used by the kernels (all int32, -1 padded) ----
   static constexpr int MAXD = 8;                    // max incident elements kept per vertex
@@ -39,7 +41,9 @@ struct CellTables {
 };
 
 // builds everything from the material description; returns non-empty error on failure
-std::string build_cell_tables(CellTables &T, int model, int shape, const hc_params &P, const hc_material &M);
+// (W: the WBC_HO constants, required for that model and ignored by the others)
+std::string build_cell_tables(CellTables &T, int model, int shape, const hc_params &P, const hc_material &M,
+                              const hc_wbc_material *W = nullptr);
 
 // rotateTriangularMeshXYZ of io/readPositionsBloodCells.cpp:40-111 as a 3x3 matrix
 void rotation_matrix_xyz(double alpha, double beta, double gamma, double R[3][3]);

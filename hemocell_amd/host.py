@@ -7,18 +7,26 @@ applyConstitutiveModel, iterate, setMaterialTimeScaleSeparation ...  Every
 method is one call into libhemocell_amd.so; nothing is computed here.
 """
 import ctypes as C
+import os
+import xml.etree.ElementTree as ET
 
 import numpy as np
 
 from . import capi
-from .capi import HcError, Material, Params, check, dptr, lptr
+from .capi import HcError, Material, Params, WbcMaterial, check, dptr, lptr
 
 HALO = 2
 
 MODEL_RBC_HO = 0
 MODEL_PLT_SIMPLE = 1
+MODEL_WBC_HO = 2
+WBC_SPHERE = 0             # config/constant_defaults.h:83
 RBC_FROM_SPHERE = 1        # config/constant_defaults.h:80
 ELLIPSOID_FROM_SPHERE = 6  # config/constant_defaults.h:81
+
+# examples/cell_shapes/WBC_HO.xml, kept as a data file with the test fixtures
+WBC_HO_XML = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "wbc_case",
+                          "WBC_HO.xml")
 
 # examples/pipeflow/PLT.xml:14-38
 PLT_INNER_EDGES = np.array([[60, 65], [62, 64], [37, 42], [54, 56], [34, 40], [25, 46], [50, 59], [29, 47],
@@ -26,6 +34,24 @@ PLT_INNER_EDGES = np.array([[60, 65], [62, 64], [37, 42], [54, 56], [34, 40], [2
                             [6, 10], [53, 55], [19, 21], [57, 58], [15, 13]], dtype=np.int64)
 
 _initialised = False
+
+
+def read_material(path):
+    """<MaterialModel> of a cell XML: {tag: float} for the numeric tags and "inner_edges" as an [n][2] int64 array
+    (mechanics/commonCellConstants.cpp:139-153 reads <InnerEdges><Edge> a b </Edge>...)"""
+    mm = ET.parse(path).getroot().find("MaterialModel")
+    if mm is None:
+        raise HcError("%s has no <MaterialModel>" % path)
+    out = {}
+    for el in mm:
+        if el.tag == "InnerEdges":
+            out["inner_edges"] = np.array([[int(v) for v in e.text.split()] for e in el.iter("Edge")], np.int64).reshape(-1, 2)
+            continue
+        try:
+            out[el.tag] = float(el.text)
+        except (TypeError, ValueError):
+            pass
+    return out
 
 
 def init(device=0):
@@ -170,7 +196,8 @@ class CellType:
     """hemocell.addCellType<Mechanics>(name, constructType) for one type."""
 
     def __init__(self, P, model, shape, radius, min_triangles, kLink, kArea, kVolume, kBend, eta_m=0.0,
-                 aspect_ratio=0.3, inner_edges=None):
+                 aspect_ratio=0.3, inner_edges=None, wbc=None):
+        """wbc: (kInnerRigid, kCytoskeleton, coreRadius, radius) in SI units, for MODEL_WBC_HO only"""
         ensure_init()
         self.lib = capi.lib()
         M = Material()
@@ -185,7 +212,13 @@ class CellType:
             M.inner_edges = None
             M.n_inner = 0
         self.ptr = C.c_void_p()
-        check(self.lib.hcp_celltype_create(C.byref(self.ptr), int(model), int(shape), C.byref(P), C.byref(M)))
+        if model == MODEL_WBC_HO:
+            if wbc is None:
+                raise HcError("MODEL_WBC_HO needs wbc=(kInnerRigid, kCytoskeleton, coreRadius, radius)")
+            W = WbcMaterial(*[float(v) for v in wbc])
+            check(self.lib.hcp_celltype_create_wbc(C.byref(self.ptr), int(shape), C.byref(P), C.byref(M), C.byref(W)))
+        else:
+            check(self.lib.hcp_celltype_create(C.byref(self.ptr), int(model), int(shape), C.byref(P), C.byref(M)))
         sz = (C.c_int * 4)()
         check(self.lib.hcp_celltype_sizes(self.ptr, sz))
         self.nv, self.nt, self.ne, self.nie = [int(x) for x in sz]
@@ -205,6 +238,29 @@ class CellType:
                  aspect_ratio=0.434782608696, inner_edges=PLT_INNER_EDGES)
         d.update(kw)
         return cls(P, MODEL_PLT_SIMPLE, ELLIPSOID_FROM_SPHERE, **d)
+
+    @classmethod
+    def wbc(cls, P, xml=None, shape=WBC_SPHERE, **kw):
+        """WbcHighOrderModel on WBC_SPHERE with the moduli, WBC constants and inner edges of a WBC XML
+        (default: examples/cell_shapes/WBC_HO.xml); keyword arguments override single values, including
+        kInnerRigid, kCytoskeleton, coreRadius and wbc_radius (the cytoskeleton radius, default the mesh radius)"""
+        m = read_material(xml or WBC_HO_XML)
+        d = dict(radius=m["radius"], min_triangles=int(m["minNumTriangles"]), kLink=m["kLink"], kArea=m["kArea"],
+                 kVolume=m["kVolume"], kBend=m["kBend"], eta_m=m["eta_m"], aspect_ratio=m.get("aspectRatio", 0.3),
+                 inner_edges=m.get("inner_edges"))
+        w = dict(kInnerRigid=m["kInnerRigid"], kCytoskeleton=m["kCytoskeleton"], coreRadius=m["coreRadius"],
+                 wbc_radius=m["radius"])
+        for k in list(kw):
+            if k in w:
+                w[k] = kw.pop(k)
+        d.update(kw)
+        return cls(P, MODEL_WBC_HO, shape, wbc=(w["kInnerRigid"], w["kCytoskeleton"], w["coreRadius"], w["wbc_radius"]), **d)
+
+    def wbc_constants(self):
+        """lattice-unit (k_inner_rigid, k_cytoskeleton, core_radius, radius) of a WBC_HO type"""
+        out = np.zeros(4)
+        check(self.lib.hcp_celltype_wbc_constants(self.ptr, dptr(out)))
+        return dict(zip(("k_inner_rigid", "k_cytoskeleton", "core_radius", "radius"), out.tolist()))
 
     def tables(self):
         t = dict(vertices=np.empty((self.nv, 3)), triangles=np.empty((self.nt, 3), np.int64),

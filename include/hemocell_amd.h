@@ -4,7 +4,7 @@
  * Drop-in boundary for the one data-parallel path of HemoCell:
  * the D3Q19 Guo-BGK collide-stream, the phi2 immersed-boundary spread /
  * interpolate, the Euler vertex advance and the rbcHighOrderModel /
- * pltSimpleModel membrane forces.  Every entry point names the reference
+ * wbcHighOrderModel / pltSimpleModel membrane forces.  Every entry point names the reference
  * interface it replaces (file:line relative to the HemoCell tree).  Plain
  * pointers and sizes only; no C++/torch types cross this boundary.  All
  * functions return 0 on success and a non-zero code on failure, with the
@@ -206,6 +206,8 @@ double hcl_mlups_bytes_per_node(const hc_lattice *L); /* algorithmic bytes per n
 /* --------------------------------------------------------------- cell types */
 #define HC_MODEL_RBC_HO 0     /* mechanics/rbcHighOrderModel.cpp */
 #define HC_MODEL_PLT_SIMPLE 1 /* mechanics/pltSimpleModel.cpp    */
+#define HC_MODEL_WBC_HO 2     /* mechanics/wbcHighOrderModel.cpp: hcp_celltype_create_wbc */
+#define HC_SHAPE_WBC_SPHERE 0            /* config/constant_defaults.h:83 */
 #define HC_SHAPE_RBC_FROM_SPHERE 1       /* config/constant_defaults.h:80 */
 #define HC_SHAPE_ELLIPSOID_FROM_SPHERE 6 /* config/constant_defaults.h:81 */
 
@@ -228,6 +230,19 @@ typedef struct hc_material { /* <MaterialModel> of RBC.xml / PLT.xml */
  * (helper/meshGeneratingFunctions.hh), CommonCellConstants (mechanics/commonCellConstants.cpp:70-409) and
  * the moduli (mechanics/cellMechanics.h:50-78), and uploads the tables. */
 int hcp_celltype_create(hc_celltype **out, int model, int shape, const hc_params *P, const hc_material *M);
+
+/* the extra <MaterialModel> tags of WBC_HO.xml (mechanics/wbcHighOrderModel.cpp:242-262), SI units */
+typedef struct hc_wbc_material {
+  double kInnerRigid;   /* [N]  rigid-core inner-link modulus */
+  double kCytoskeleton; /* [N]  cytoskeleton inner-link modulus */
+  double coreRadius;    /* [m] */
+  double radius;        /* [m]  cell radius of the cytoskeleton law (the same tag as hc_material.radius in the XML) */
+} hc_wbc_material;
+/* hemocell.addCellType<WbcHighOrderModel>(name, constructType): the RBC_HO moduli of M plus the inner-link law over
+ * M->inner_edges (wbcHighOrderModel.cpp:199-223).  hcp_celltype_create refuses HC_MODEL_WBC_HO and names this entry point. */
+int hcp_celltype_create_wbc(hc_celltype **out, int shape, const hc_params *P, const hc_material *M, const hc_wbc_material *W);
+/* lattice-unit WBC constants: out = k_inner_rigid, k_cytoskeleton, core_radius, radius (0 for the other models) */
+int hcp_celltype_wbc_constants(const hc_celltype *T, double out[4]);
 int hcp_celltype_destroy(hc_celltype *T);
 /* table sizes: out[0..3] = vertices, triangles, edges, inner edges */
 int hcp_celltype_sizes(const hc_celltype *T, int out[4]);
