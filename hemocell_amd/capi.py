@@ -37,6 +37,12 @@ class WbcMaterial(C.Structure):
                 ("radius", C.c_double)]
 
 
+class CellTypeSpec(C.Structure):
+    """hc_celltype_spec == everything addCellType<Model>(name, constructType) reads from a cell XML"""
+    _fields_ = [("model", C.c_int), ("shape", C.c_int), ("material", Material), ("wbc", C.POINTER(WbcMaterial)),
+                ("kInnerLink", C.c_double), ("stl_path", C.c_char_p)]
+
+
 # every symbol include/hemocell_amd.h declares: name -> (restype, argtypes)
 VP = C.c_void_p
 SIGNATURES = {
@@ -110,6 +116,8 @@ SIGNATURES = {
     "hcp_celltype_create_wbc": (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(Params), C.POINTER(Material),
                                           C.POINTER(WbcMaterial)]),
     "hcp_celltype_wbc_constants": (C.c_int, [VP, c_double_p]),
+    "hcp_celltype_create_ex": (C.c_int, [C.POINTER(VP), C.POINTER(Params), C.POINTER(CellTypeSpec)]),
+    "hcp_celltype_malaria_constants": (C.c_int, [VP, c_double_p]),
     "hcp_celltype_destroy": (C.c_int, [VP]),
     "hcp_celltype_sizes": (C.c_int, [VP, c_int_p]),
     "hcp_celltype_tables": (C.c_int, [VP, c_double_p, c_long_p, c_long_p, c_double_p, c_double_p, c_double_p,

@@ -28,7 +28,7 @@ inline bool read_stl(const std::string &fn, std::vector<std::array<double, 9>> &
 }
 
 inline void getFlagMatrixFromSTL(std::string meshFileName, plint /*extendedEnvelopeWidth*/, plint refDirLength, plint refDir,
-                                 VoxelizedDomain3D<T> *&voxelizedDomain, MultiScalarField3D<int> *&flagMatrix, plint /*blockSize*/, int /*particleEnvelope*/) {
+                                 VoxelizedDomain3D<T> *&voxelizedDomain, MultiScalarField3D<int> *&flagMatrix, plint /*blockSize*/, int /*particleEnvelope*/ = 0) {
   std::vector<std::array<double, 9>> tris;
   if (!read_stl(meshFileName, tris)) { hlog << "(Voxelizer) Error: " << meshFileName << " is not an existing stl file." << endl; std::exit(1); }
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
@@ -69,7 +69,7 @@ inline void getFlagMatrixFromSTL(std::string meshFileName, plint /*extendedEnvel
 #if __cplusplus < 201703L
 inline void getFlagMatrixFromSTL(std::string meshFileName, plint extendedEnvelopeWidth, plint refDirLength, plint refDir,
                                  std::auto_ptr<VoxelizedDomain3D<T>> &voxelizedDomain, std::auto_ptr<MultiScalarField3D<int>> &flagMatrix,
-                                 plint blockSize, int particleEnvelope) {
+                                 plint blockSize, int particleEnvelope = 0) {
   VoxelizedDomain3D<T> *v = nullptr; MultiScalarField3D<int> *f = nullptr;
   getFlagMatrixFromSTL(meshFileName, extendedEnvelopeWidth, refDirLength, refDir, v, f, blockSize, particleEnvelope);
   voxelizedDomain = std::auto_ptr<VoxelizedDomain3D<T>>(v);

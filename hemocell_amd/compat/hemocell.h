@@ -399,6 +399,27 @@ class WbcHighOrderModel : public DeviceMechanics<HC_MODEL_WBC_HO> {
   T k_inner_rigid = 0, k_cytoskeleton = 0, core_radius = 0, radius = 0;
 };
 
+// mechanics/rbcMalariaModel.h: the RBC_HO laws, the membrane viscosity without the eta_m test and the linear inner links,
+// evaluated by mechanics_kernel<HC_MODEL_RBC_MALARIA>; k_inner_link comes from <kInnerLink>, read by create_device_type
+class RbcMalariaModel : public DeviceMechanics<HC_MODEL_RBC_MALARIA> {
+ public:
+  RbcMalariaModel(Config &modelCfg_, HemoCellField &field) : DeviceMechanics<HC_MODEL_RBC_MALARIA>(modelCfg_, field) {
+    double k[1];
+    hc_check(hcp_celltype_malaria_constants(field.dev, k), "hcp_celltype_malaria_constants");
+    k_inner_link = k[0];
+  }
+  void statistics() override {   // mechanics/rbcMalariaModel.cpp:221-230
+    pcout << "(Cell-mechanics model) Malaria model parameters for " << cellField.name << " cellfield" << std::endl;
+    pcout << "\t k_link:   " << k_link << std::endl;
+    pcout << "\t k_area:   " << k_area << std::endl;
+    pcout << "\t k_bend: : " << k_bend << std::endl;
+    pcout << "\t k_inner_link:   " << k_inner_link << std::endl;
+    pcout << "\t k_volume: " << k_volume << std::endl;
+    pcout << "\t eta_m:    " << eta_m << std::endl;
+  }
+  T k_inner_link = 0;
+};
+
 // ------------------------------------------------------------------ core/hemoCellParticleField.h:39-207
 // The reference keeps std::vector<HemoCellParticle> per atomic block; here the vertices live on the GPU and this object is
 // a host VIEW of this rank's block: refresh() fills `particles` from the device in the reference's record
@@ -703,7 +724,11 @@ inline void HemoCellField::create_device_type(int model) {
   M.kLink = m["MaterialModel"]["kLink"].read<T>(); M.kArea = m["MaterialModel"]["kArea"].read<T>();
   M.kVolume = m["MaterialModel"]["kVolume"].read<T>(); M.kBend = m["MaterialModel"]["kBend"].read<T>();
   M.eta_m = m["MaterialModel"]["eta_m"].read<T>(); M.radius = m["MaterialModel"]["radius"].read<T>();
-  M.min_triangles = (int)m["MaterialModel"]["minNumTriangles"].read<T>();
+  // core/hemoCellField.cpp:57-66: a mesh from <StlFile> (relative to the working directory) for MESH_FROM_STL, whose
+  // minNumTriangles is not used; a missing <StlFile> throws std::invalid_argument
+  string stl;
+  if (constructType == MESH_FROM_STL) stl = m["MaterialModel"]["StlFile"].read<string>();
+  else M.min_triangles = (int)m["MaterialModel"]["minNumTriangles"].read<T>();
   M.aspect_ratio = 0.3;
   if (constructType == ELLIPSOID_FROM_SPHERE) M.aspect_ratio = m["MaterialModel"]["aspectRatio"].read<T>();
   vector<long> inner;
@@ -713,11 +738,20 @@ inline void HemoCellField::create_device_type(int model) {
   } catch (std::invalid_argument &) {}
   M.inner_edges = inner.empty() ? nullptr : inner.data(); M.n_inner = (int)inner.size() / 2;
   innerEdges = inner;
-  if (constructType != WBC_SPHERE && constructType != RBC_FROM_SPHERE && constructType != ELLIPSOID_FROM_SPHERE) { hlog << "(HemoCell) (AddCellType) construct type " << constructType << " is not supported by the GPU back end" << endl; std::exit(1); }
+  if (constructType != WBC_SPHERE && constructType != RBC_FROM_SPHERE && constructType != ELLIPSOID_FROM_SPHERE && constructType != MESH_FROM_STL) { hlog << "(HemoCell) (AddCellType) construct type " << constructType << " is not supported by the GPU back end" << endl; std::exit(1); }
+  hc_wbc_material W;
   if (model == HC_MODEL_WBC_HO) {   // WbcHighOrderModel::calculate_* (mechanics/wbcHighOrderModel.cpp:242-262)
-    hc_wbc_material W;
     W.kInnerRigid = m["MaterialModel"]["kInnerRigid"].read<T>(); W.kCytoskeleton = m["MaterialModel"]["kCytoskeleton"].read<T>();
     W.coreRadius = m["MaterialModel"]["coreRadius"].read<T>(); W.radius = m["MaterialModel"]["radius"].read<T>();
+  }
+  if (constructType == MESH_FROM_STL || model == HC_MODEL_RBC_MALARIA) {
+    hc_celltype_spec S; std::memset(&S, 0, sizeof(S));
+    S.model = model; S.shape = constructType; S.material = M;
+    S.wbc = model == HC_MODEL_WBC_HO ? &W : nullptr;
+    if (model == HC_MODEL_RBC_MALARIA) S.kInnerLink = m["MaterialModel"]["kInnerLink"].read<T>();   // RbcMalariaModel::calculate_kInnerLink
+    S.stl_path = constructType == MESH_FROM_STL ? stl.c_str() : nullptr;
+    hc_check(hcp_celltype_create_ex(&dev, &Parameters::raw(), &S), "hcp_celltype_create_ex");
+  } else if (model == HC_MODEL_WBC_HO) {
     hc_check(hcp_celltype_create_wbc(&dev, constructType, &Parameters::raw(), &M, &W), "hcp_celltype_create_wbc");
   } else {
     hc_check(hcp_celltype_create(&dev, model, constructType, &Parameters::raw(), &M), "hcp_celltype_create");

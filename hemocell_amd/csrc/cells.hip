@@ -235,12 +235,11 @@ void host_append_state(hc_cells *C, int type, long cell_id) {
   C->host_dirty = true;
 }
 
-// hcp_celltype_create / hcp_celltype_create_wbc: mesh, tables and moduli on the host, then the tables to the device
-int celltype_create(const char *fn, hc_celltype **out, int model, int shape, const hc_params *P, const hc_material *M,
-                    const hc_wbc_material *W) {
+// hcp_celltype_create / _create_wbc / _create_ex: mesh, tables and moduli on the host, then the tables to the device
+int celltype_create(const char *fn, hc_celltype **out, const hc_params *P, const hc_celltype_spec &S) {
   if (hc::stream() == nullptr) { hc::set_error(std::string(fn) + ": hc_init() has not been called"); return HC_ERR_STATE; }
   hc_celltype *T = new hc_celltype();
-  std::string err = build_cell_tables(T->host, model, shape, *P, *M, W);
+  std::string err = build_cell_tables(T->host, *P, S);
   if (!err.empty()) { delete T; hc::set_error(std::string(fn) + ": " + err); return HC_ERR_ARG; }
   const CellTables &H = T->host;
   int rc = HC_OK;
@@ -265,13 +264,31 @@ extern "C" {
 
 int hcp_celltype_create(hc_celltype **out, int model, int shape, const hc_params *P, const hc_material *M) {
   HC_REQUIRE(out && P && M, "hcp_celltype_create: null pointer");
-  HC_REQUIRE(model != HC_MODEL_WBC_HO, "hcp_celltype_create: HC_MODEL_WBC_HO needs its inner-link constants: use hcp_celltype_create_wbc");
-  return hcc::celltype_create("hcp_celltype_create", out, model, shape, P, M, nullptr);
+  HC_REQUIRE(model != HC_MODEL_WBC_HO, "hcp_celltype_create: HC_MODEL_WBC_HO needs its inner-link constants: use hcp_celltype_create_wbc or hcp_celltype_create_ex");
+  HC_REQUIRE(model != HC_MODEL_RBC_MALARIA, "hcp_celltype_create: HC_MODEL_RBC_MALARIA needs kInnerLink: use hcp_celltype_create_ex");
+  HC_REQUIRE(shape != HC_SHAPE_MESH_FROM_STL, "hcp_celltype_create: HC_SHAPE_MESH_FROM_STL needs the STL file: use hcp_celltype_create_ex");
+  hc_celltype_spec S{};
+  S.model = model; S.shape = shape; S.material = *M;
+  return hcc::celltype_create("hcp_celltype_create", out, P, S);
 }
 
 int hcp_celltype_create_wbc(hc_celltype **out, int shape, const hc_params *P, const hc_material *M, const hc_wbc_material *W) {
   HC_REQUIRE(out && P && M && W, "hcp_celltype_create_wbc: null pointer");
-  return hcc::celltype_create("hcp_celltype_create_wbc", out, HC_MODEL_WBC_HO, shape, P, M, W);
+  HC_REQUIRE(shape != HC_SHAPE_MESH_FROM_STL, "hcp_celltype_create_wbc: HC_SHAPE_MESH_FROM_STL needs the STL file: use hcp_celltype_create_ex");
+  hc_celltype_spec S{};
+  S.model = HC_MODEL_WBC_HO; S.shape = shape; S.material = *M; S.wbc = W;
+  return hcc::celltype_create("hcp_celltype_create_wbc", out, P, S);
+}
+
+int hcp_celltype_create_ex(hc_celltype **out, const hc_params *P, const hc_celltype_spec *S) {
+  HC_REQUIRE(out && P && S, "hcp_celltype_create_ex: null pointer");
+  return hcc::celltype_create("hcp_celltype_create_ex", out, P, *S);
+}
+
+int hcp_celltype_malaria_constants(const hc_celltype *T, double out[1]) {
+  HC_REQUIRE(T && out, "hcp_celltype_malaria_constants: null pointer");
+  out[0] = T->host.k_inner_link;
+  return HC_OK;
 }
 
 int hcp_celltype_wbc_constants(const hc_celltype *T, double out[4]) {

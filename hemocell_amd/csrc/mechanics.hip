@@ -1,8 +1,10 @@
-// Membrane mechanics on the GPU: rbcHighOrderModel, wbcHighOrderModel and pltSimpleModel forces, per-cell information.
+// Membrane mechanics on the GPU: rbcHighOrderModel, wbcHighOrderModel, rbcMalariaModel and pltSimpleModel forces,
+// per-cell information.
 //
 // Replaces (file:line in the HemoCell tree):
 //   core/hemoCellParticleField.cpp:633-675        applyConstitutiveModel
-//   mechanics/rbcHighOrderModel.cpp:38-207, mechanics/wbcHighOrderModel.cpp:42-225, mechanics/pltSimpleModel.cpp:44-208
+//   mechanics/rbcHighOrderModel.cpp:38-207, mechanics/wbcHighOrderModel.cpp:42-225, mechanics/pltSimpleModel.cpp:44-208,
+//   mechanics/rbcMalariaModel.cpp:40-218
 //   helper/cellInfo.cpp                           volume, area, position, bounding box per cell
 //
 // The membrane models are evaluated in GATHER form: one workgroup per cell,
@@ -31,6 +33,7 @@ struct MechArgs {
   const int *tag;      // per cell of this type: 0 complete, 1 gone, 2 incomplete
   // WBC only (wbcHighOrderModel.cpp:242-262), lattice units; last so that the other models' argument layout is unchanged
   double k_inner_rigid, k_cytoskeleton, core_radius, radius;
+  double k_inner_link;   // RBC_MALARIA only (rbcMalariaModel.cpp:233-240), lattice units
 };
 
 #define MaxCellVolumetricChange 0.01   // config/constant_defaults.h:157-173
@@ -39,8 +42,6 @@ struct MechArgs {
 #define MaxPLTBendingAngle 2.467
 #define MaxCellPersistenceLength 9.0
 #define FORCE_LIMIT_PN 50.0
-
-constexpr int MD = CellTables::MAXD;
 
 __device__ __forceinline__ double norm3(double a, double b, double c) { double r = 0.0; r += a * a; r += b * b; r += c * c; return sqrt(r); }
 __device__ __forceinline__ double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { double r = 0.0; r += a0 * b0; r += a1 * b1; r += a2 * b2; return r; }
@@ -65,14 +66,17 @@ __device__ __forceinline__ double tri_signed_volume(const double *xs, const doub
   return (-v210 + v120 + v201 - v021 - v102 + v012);
 }
 
-// one workgroup = one cell.  LDS: positions and the per-triangle signed-volume terms; RBC / WBC: per-vertex bending vector;
+// one workgroup = one cell.  LDS: positions and the per-triangle signed-volume terms; RBC / WBC / malaria: per-vertex bending vector;
 // PLT (small mesh): per-triangle {area, unit normal, area-force magnitude} and per-edge {link, visc, bending} vectors.
-// WBC_HO is the RBC_HO path with the membrane viscosity always evaluated, followed by the two-threshold inner links.
-template <int MODEL, bool SEPARATE>
+// WBC_HO is the RBC_HO path with the membrane viscosity always evaluated, followed by the two-threshold inner links;
+// RBC_MALARIA is the same path followed by the linear inner links.  MD: row width of the per-vertex lists
+// (CellTables::md, MAXD or MAXD_WIDE).
+template <int MODEL, bool SEPARATE, int MD>
 __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
   extern __shared__ double lds[];
   constexpr bool PLT = MODEL == HC_MODEL_PLT_SIMPLE;
   constexpr bool WBC = MODEL == HC_MODEL_WBC_HO;
+  constexpr bool MAL = MODEL == HC_MODEL_RBC_MALARIA;
   const int nv = m.nv, nt = m.nt, ne = m.ne;
   double *xs = lds, *ys = xs + nv, *zs = ys + nv;
   double *tV = zs + nv;
@@ -228,7 +232,8 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
         const double frx = ux * fs, fry = uy * fs, frz = uz * fs;
         const bool first = m.vedge_s[MD * i + k] > 0;
         if (first) { ACC(3)[0] += frx; ACC(3)[1] += fry; ACC(3)[2] += frz; } else { ACC(3)[0] -= frx; ACC(3)[1] -= fry; ACC(3)[2] -= frz; }
-        if (WBC || m.eta_m != 0.0) {   // the WBC model has no eta_m test (wbcHighOrderModel.cpp:183-197)
+        if (WBC || MAL || m.eta_m != 0.0) {   // no eta_m test in the WBC and malaria models (wbcHighOrderModel.cpp:183-197,
+                                               // rbcMalariaModel.cpp:181-195)
           const double rvx = m.vx[base + e1] - m.vx[base + e0], rvy = m.vy[base + e1] - m.vy[base + e0], rvz = m.vz[base + e1] - m.vz[base + e0];
           const double pr = dot3(rvx, rvy, rvz, ux, uy, uz);
           double wx = m.eta_m * (pr * ux), wy = m.eta_m * (pr * uy), wz = m.eta_m * (pr * uz);
@@ -256,6 +261,23 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
             const double frx = (ux * s) * kk, fry = (uy * s) * kk, frz = (uz * s) * kk;
             if (first) { ACC(5)[0] -= frx; ACC(5)[1] -= fry; ACC(5)[2] -= frz; } else { ACC(5)[0] += frx; ACC(5)[1] += fry; ACC(5)[2] += frz; }
           }
+        }
+      }
+      if (MAL) {
+        // inner links (rbcMalariaModel.cpp:198-217), ascending inner-edge id: linear law 5 k_inner_link (l - l0) / l0,
+        // edge[0] receives +f, edge[1] -f
+        for (int k = 0; k < MD; k++) {
+          const int e = m.vinner[MD * i + k];
+          if (e < 0) break;
+          const int e0 = m.iedge[2 * e], e1 = m.iedge[2 * e + 1];
+          const double evx = xs[e1] - xs[e0], evy = ys[e1] - ys[e0], evz = zs[e1] - zs[e0];
+          const double el = sqrt(evx * evx + evy * evy + evz * evz);
+          const double ux = evx / el, uy = evy / el, uz = evz / el;
+          const double leq = m.iedge_len_eq[e];
+          const double ef = (el - leq) / leq;
+          const double fs = m.k_inner_link * 5.0 * ef;
+          if (m.vinner_s[MD * i + k] > 0) { ACC(5)[0] += ux * fs; ACC(5)[1] += uy * fs; ACC(5)[2] += uz * fs; }
+          else { ACC(5)[0] -= ux * fs; ACC(5)[1] -= uy * fs; ACC(5)[2] -= uz * fs; }
         }
       }
     } else {
@@ -363,6 +385,7 @@ static MechArgs mech_args(const hc_cells *C, int t) {
   m.comp = nullptr; m.ncv = C->ncells[t] * T->host.nv;
   m.tag = C->d_tag + C->cell0[t];
   m.k_inner_rigid = T->host.k_inner_rigid; m.k_cytoskeleton = T->host.k_cytoskeleton; m.core_radius = T->host.core_radius; m.radius = T->host.wbc_radius;
+  m.k_inner_link = T->host.k_inner_link;
   return m;
 }
 
@@ -380,15 +403,22 @@ static int launch_mechanics(hc_cells *C, int t, double *comp) {
   HC_REQUIRE(lds <= 160 * 1024 - 64, "mechanics: cell type does not fit the 160 KiB LDS of a CU");
   const int threads = T.nv > 128 ? 256 : 128;
   const dim3 grid((unsigned)C->ncells[t]);
+  HC_REQUIRE(T.md == CellTables::MAXD || T.md == CellTables::MAXD_WIDE, "mechanics: unsupported per-vertex table width");
+#define LAUNCH1(MODEL, SEP, W)                                                                                    \
+  do {                                                                                                            \
+    HC_HIP(hipFuncSetAttribute((const void *)mechanics_kernel<MODEL, SEP, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL((mechanics_kernel<MODEL, SEP, W>), grid, dim3(threads), lds, hc::stream(), m);             \
+  } while (0)
 #define LAUNCH(MODEL, SEP)                                                                                        \
   do {                                                                                                            \
-    HC_HIP(hipFuncSetAttribute((const void *)mechanics_kernel<MODEL, SEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((mechanics_kernel<MODEL, SEP>), grid, dim3(threads), lds, hc::stream(), m);                \
+    if (T.md == CellTables::MAXD) LAUNCH1(MODEL, SEP, CellTables::MAXD); else LAUNCH1(MODEL, SEP, CellTables::MAXD_WIDE); \
   } while (0)
   if (T.model == HC_MODEL_RBC_HO) { if (comp) LAUNCH(HC_MODEL_RBC_HO, true); else LAUNCH(HC_MODEL_RBC_HO, false); }
   else if (T.model == HC_MODEL_WBC_HO) { if (comp) LAUNCH(HC_MODEL_WBC_HO, true); else LAUNCH(HC_MODEL_WBC_HO, false); }
+  else if (T.model == HC_MODEL_RBC_MALARIA) { if (comp) LAUNCH(HC_MODEL_RBC_MALARIA, true); else LAUNCH(HC_MODEL_RBC_MALARIA, false); }
   else { if (comp) LAUNCH(HC_MODEL_PLT_SIMPLE, true); else LAUNCH(HC_MODEL_PLT_SIMPLE, false); }
 #undef LAUNCH
+#undef LAUNCH1
   HC_HIP(hipGetLastError());
   return HC_OK;
 }

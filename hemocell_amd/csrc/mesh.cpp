@@ -1,6 +1,7 @@
 // Cell-type construction on the host: mesh generation, equilibrium tables,
 // moduli.  Mirrors (does not copy) the reference's setup path:
 //   helper/meshGeneratingFunctions.hh:32-271   sphere -> WBC sphere / RBC / ellipsoid surface
+//   helper/meshGeneratingFunctions.hh:275-288  constructCell: surface from an STL file
 //   core/hemoCellField.cpp:38-118              triangle list from the mesh
 //   mechanics/commonCellConstants.cpp:70-409   equilibrium tables
 //   mechanics/cellMechanics.h:50-78            moduli in lattice units
@@ -12,7 +13,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
 #include <map>
+#include <sstream>
 #include <string>
 #include <tuple>
 
@@ -100,9 +106,61 @@ std::vector<Tri> octasphere(long min_triangles) {
   return t;
 }
 
-void build_mesh(CellTables &T, int shape, double radius, long min_triangles, double aspect) {
+// triangle soup of an STL file: binary when the size is 84 + 50 n for the n of its header (float32 corners widened to
+// double), ASCII otherwise (every "vertex x y z", parsed as double)
+std::string read_stl(const char *path, std::vector<Tri> &t) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f.is_open()) return std::string("cannot open STL file '") + path + "'";
+  const std::string all((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  t.clear();
+  uint32_t n = 0;
+  if (all.size() >= 84) std::memcpy(&n, all.data() + 80, 4);
+  if (all.size() >= 84 && all.size() == 84 + 50 * (size_t)n) {
+    for (size_t i = 0; i < n; i++) {
+      const char *r = all.data() + 84 + 50 * i + 12;   // skip the facet normal
+      Tri tr;
+      for (int k = 0; k < 3; k++) for (int d = 0; d < 3; d++) { float v; std::memcpy(&v, r + 4 * (3 * k + d), 4); tr.p[k][d] = (double)v; }
+      t.push_back(tr);
+    }
+  } else {
+    std::istringstream in(all);
+    std::string w;
+    std::vector<Vec3> corners;
+    while (in >> w) {
+      if (w != "vertex") continue;
+      Vec3 p;
+      for (int d = 0; d < 3; d++) {
+        std::string x;
+        char *end = nullptr;
+        if (!(in >> x)) return std::string("STL file '") + path + "': truncated vertex";
+        p[d] = std::strtod(x.c_str(), &end);
+        if (end == x.c_str() || *end != 0) return std::string("STL file '") + path + "': bad coordinate '" + x + "'";
+      }
+      corners.push_back(p);
+    }
+    if (corners.size() % 3 != 0) return std::string("STL file '") + path + "': vertex count is not a multiple of 3";
+    for (size_t i = 0; i < corners.size(); i += 3) t.push_back(Tri{{corners[i], corners[i + 1], corners[i + 2]}});
+  }
+  if (t.empty()) return std::string("STL file '") + path + "' holds no triangles (neither binary nor ASCII STL)";
+  return "";
+}
+
+std::string build_mesh(CellTables &T, int shape, double radius, long min_triangles, double aspect, const char *stl) {
   std::vector<Tri> t;
-  if (shape == HC_SHAPE_WBC_SPHERE) {
+  if (shape == HC_SHAPE_MESH_FROM_STL) {
+    // constructCell(centre 0, radius, file, angles 0), helper/meshGeneratingFunctions.hh:275-288: the largest extent of the
+    // bounding box becomes 2 radius, then rotate(pi/2, pi/2, 0); translating by the zero centre changes nothing
+    std::string err = read_stl(stl, t);
+    if (!err.empty()) return err;
+    Vec3 lo = t[0].p[0], hi = t[0].p[0];
+    for (const auto &tr : t) for (const auto &p : tr.p) for (int d = 0; d < 3; d++) { lo[d] = std::min(lo[d], p[d]); hi[d] = std::max(hi[d], p[d]); }
+    const double dr[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const double scaleFactor = std::max(dr[0], std::max(dr[1], dr[2]));
+    if (!(scaleFactor > 0)) return std::string("STL file '") + stl + "': zero extent";
+    const double alpha = radius * 2.0 / scaleFactor;
+    for (auto &tr : t) for (auto &p : tr.p) for (int d = 0; d < 3; d++) p[d] *= alpha;
+    rotate_zxz(t, kPi / 2.0, kPi / 2.0, 0.);
+  } else if (shape == HC_SHAPE_WBC_SPHERE) {
     // constructSphereIcosahedron(centre 0, radius), helper/meshGeneratingFunctions.h:73-74 and .hh:32-150: the unit
     // icosphere scaled by the radius, no rotation
     t = icosphere(min_triangles);
@@ -136,19 +194,30 @@ void build_mesh(CellTables &T, int shape, double radius, long min_triangles, dou
     }
     rotate_zxz(t, kPi / 2.0, kPi / 2.0, 0.);
   }
-  // weld: first-occurrence numbering
+  // weld: first-occurrence numbering (generated meshes on coordinates rounded to 1e-8, STL meshes on exact coordinates)
   using Key = std::tuple<int64_t, int64_t, int64_t>;
   std::map<Key, long> seen;
+  std::map<Vec3, long> seen_exact;
   T.vertices.clear(); T.triangles.clear();
   for (const auto &tr : t) {
     std::array<long, 3> ids;
     for (int k = 0; k < 3; k++) {
       const Vec3 &p = tr.p[k];
-      Key key{std::llround(p[0] * 1e8), std::llround(p[1] * 1e8), std::llround(p[2] * 1e8)};
-      auto it = seen.find(key);
-      if (it == seen.end()) { it = seen.emplace(key, (long)T.vertices.size()).first; T.vertices.push_back(p); }
-      ids[k] = it->second;
+      if (shape == HC_SHAPE_MESH_FROM_STL) {
+        auto it = seen_exact.find(p);
+        if (it == seen_exact.end()) { it = seen_exact.emplace(p, (long)T.vertices.size()).first; T.vertices.push_back(p); }
+        ids[k] = it->second;
+      } else {
+        Key key{std::llround(p[0] * 1e8), std::llround(p[1] * 1e8), std::llround(p[2] * 1e8)};
+        auto it = seen.find(key);
+        if (it == seen.end()) { it = seen.emplace(key, (long)T.vertices.size()).first; T.vertices.push_back(p); }
+        ids[k] = it->second;
+      }
     }
+    if (ids[0] == ids[1] || ids[1] == ids[2] || ids[2] == ids[0]) return "degenerate triangle " + std::to_string(T.triangles.size()) + " (repeated corner)";
+    double area = 0;
+    unit_normal(T.vertices[ids[0]], T.vertices[ids[1]], T.vertices[ids[2]], &area);
+    if (!(area > 0)) return "degenerate triangle " + std::to_string(T.triangles.size()) + " (zero area)";
     T.triangles.push_back(ids);
   }
   T.nv = (int)T.vertices.size(); T.nt = (int)T.triangles.size();
@@ -163,6 +232,7 @@ void build_mesh(CellTables &T, int shape, double radius, long min_triangles, dou
     const double l = norm(vn[i]);
     for (int d = 0; d < 3; d++) T.vertices[i][d] += 1.e-3 * (vn[i][d] / l);
   }
+  return "";
 }
 
 }  // namespace
@@ -183,21 +253,47 @@ void rotation_matrix_xyz(double alpha, double beta, double gamma, double a[3][3]
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { a[i][j] = 0; for (int k = 0; k < 3; k++) a[i][j] += c[k][j] * b[i][k]; }
 }
 
-std::string build_cell_tables(CellTables &T, int model, int shape, const hc_params &P, const hc_material &M,
-                              const hc_wbc_material *W) {
-  if (model != HC_MODEL_RBC_HO && model != HC_MODEL_PLT_SIMPLE && model != HC_MODEL_WBC_HO) return "unknown mechanics model";
+std::string build_cell_tables(CellTables &T, const hc_params &P, const hc_celltype_spec &S) {
+  const int model = S.model, shape = S.shape;
+  const hc_material &M = S.material;
+  const hc_wbc_material *W = S.wbc;
+  if (model != HC_MODEL_RBC_HO && model != HC_MODEL_PLT_SIMPLE && model != HC_MODEL_WBC_HO && model != HC_MODEL_RBC_MALARIA) return "unknown mechanics model";
   if (model == HC_MODEL_WBC_HO && !W) return "the WBC_HO model needs its hc_wbc_material";
-  if (shape != HC_SHAPE_WBC_SPHERE && shape != HC_SHAPE_RBC_FROM_SPHERE && shape != HC_SHAPE_ELLIPSOID_FROM_SPHERE) return "unsupported construct type";
-  if (!(M.radius > 0) || M.min_triangles < 8) return "material: radius must be > 0 and min_triangles >= 8";
+  if (shape != HC_SHAPE_WBC_SPHERE && shape != HC_SHAPE_RBC_FROM_SPHERE && shape != HC_SHAPE_ELLIPSOID_FROM_SPHERE && shape != HC_SHAPE_MESH_FROM_STL)
+    return "unsupported construct type";
+  if (shape == HC_SHAPE_MESH_FROM_STL && (!S.stl_path || !S.stl_path[0])) return "MESH_FROM_STL needs the path of its STL file";
+  if (!(M.radius > 0)) return "material: radius must be > 0";
+  if (shape != HC_SHAPE_MESH_FROM_STL && M.min_triangles < 8) return "material: min_triangles must be >= 8";
+  if (M.n_inner < 0 || (M.n_inner > 0 && !M.inner_edges)) return "material: bad inner-edge list";
   T.model = model;
-  build_mesh(T, shape, M.radius / P.dx, M.min_triangles, M.aspect_ratio);
+  std::string err = build_mesh(T, shape, M.radius / P.dx, M.min_triangles, M.aspect_ratio, S.stl_path);
+  if (!err.empty()) return err;
   const int nv = T.nv, nt = T.nt;
   const auto &V = T.vertices;
 
   // directed half-edge -> triangle
   std::map<std::pair<long, long>, long> half;
   for (long t = 0; t < nt; t++) for (int k = 0; k < 3; k++) half[{T.triangles[t][k], T.triangles[t][(k + 1) % 3]}] = t;
-  if ((long)half.size() != 3L * nt) return "mesh is not an oriented manifold";
+  if ((long)half.size() != 3L * nt) return "mesh is not an oriented manifold: a directed edge is shared by two triangles";
+  for (const auto &h : half)
+    if (!half.count({h.first.second, h.first.first}))
+      return "open mesh: edge " + std::to_string(h.first.first) + "-" + std::to_string(h.first.second) + " has a single adjacent triangle";
+  {   // every vertex must have one closed fan (no two cones meeting in a vertex)
+    std::vector<int> ntri(nv, 0);
+    std::vector<long> any(nv, -1);
+    for (long t = 0; t < nt; t++) for (int k = 0; k < 3; k++) { ntri[T.triangles[t][k]]++; any[T.triangles[t][k]] = T.triangles[t][(k + 1) % 3]; }
+    for (long v = 0; v < nv; v++) {
+      if (ntri[v] == 0) return "vertex " + std::to_string(v) + " belongs to no triangle";
+      long cur = any[v];
+      int n = 0;
+      do {
+        const auto &tr = T.triangles[half.at({v, cur})];
+        for (int k = 0; k < 3; k++) if (tr[k] == v) { cur = tr[(k + 2) % 3]; break; }
+        n++;
+      } while (cur != any[v] && n <= ntri[v]);
+      if (n != ntri[v]) return "non-manifold mesh: the triangles around vertex " + std::to_string(v) + " form more than one fan";
+    }
+  }
 
   // edges (a < b) in triangle order
   T.edges.clear();
@@ -244,34 +340,73 @@ std::string build_cell_tables(CellTables &T, int model, int shape, const hc_para
   T.triangle_area_eq.resize(nt);
   for (long t = 0; t < nt; t++) unit_normal(V[T.triangles[t][0]], V[T.triangles[t][1]], V[T.triangles[t][2]], &T.triangle_area_eq[t]);
 
-  // gather lists (ascending ids by construction)
-  const int D = CellTables::MAXD;
+  // neighbour rings: the first six neighbours in edge-list order, then walk the fan from the first one
+  // (mechanics/commonCellConstants.cpp:201-271: a vertex of higher valence keeps six, as in the reference)
+  T.vertex_vertexes.assign(nv, {-1, -1, -1, -1, -1, -1});
+  T.vertex_n_vertexes.assign(nv, 0);
+  for (int e = 0; e < ne; e++) {
+    const long a = T.edges[e][0], b = T.edges[e][1];
+    if (T.vertex_n_vertexes[a] < 6) T.vertex_vertexes[a][T.vertex_n_vertexes[a]++] = b;
+    if (T.vertex_n_vertexes[b] < 6) T.vertex_vertexes[b][T.vertex_n_vertexes[b]++] = a;
+  }
+  for (long v = 0; v < nv; v++) {
+    long cur = T.vertex_vertexes[v][0];
+    for (int n = 1; n < T.vertex_n_vertexes[v]; n++) {
+      auto it = half.find({v, cur});
+      if (it == half.end()) return "ring walk failed";
+      const auto &tr = T.triangles[it->second];
+      long next = -1;
+      for (int k = 0; k < 3; k++) if (tr[k] == v) next = tr[(k + 2) % 3];
+      cur = next;
+      T.vertex_vertexes[v][n] = cur;
+    }
+  }
+
+  // gather lists (ascending ids by construction).  Bending sources: vertex i receives its own bending force and -B/n of
+  // every vertex whose ring holds i (rbcHighOrderModel.cpp:157-160); with truncated rings that relation is not symmetric
+  std::vector<std::vector<int>> src(nv);
+  for (long j = 0; j < nv; j++) {
+    src[j].push_back((int)j);
+    for (int k = 0; k < T.vertex_n_vertexes[j]; k++) src[T.vertex_vertexes[j][k]].push_back((int)j);
+  }
+  for (auto &l : src) std::sort(l.begin(), l.end());
+  std::vector<int> cnt(nv, 0);
+  int need = 0;   // longest per-vertex list: incident triangles (= outer-point edges), edges, bending sources, inner edges
+  for (long t = 0; t < nt; t++) for (int k = 0; k < 3; k++) need = std::max(need, ++cnt[T.triangles[t][k]]);
+  std::fill(cnt.begin(), cnt.end(), 0);
+  for (int e = 0; e < ne; e++) for (int s = 0; s < 2; s++) need = std::max(need, ++cnt[T.edges[e][s]]);
+  std::fill(cnt.begin(), cnt.end(), 0);
+  for (int e = 0; e < T.nie; e++) for (int s = 0; s < 2; s++) need = std::max(need, ++cnt[T.inner_edges[e][s]]);
+  for (const auto &l : src) need = std::max(need, (int)l.size());
+  if (need > CellTables::MAXD_WIDE)
+    return "a vertex has " + std::to_string(need) + " incident elements (triangles, edges, bending sources or inner edges); at most " +
+           std::to_string(CellTables::MAXD_WIDE) + " are supported";
+  const int D = need > CellTables::MAXD ? CellTables::MAXD_WIDE : CellTables::MAXD;
+  T.md = D;
   auto fill = [&](std::vector<int> &v) { v.assign((size_t)nv * D, -1); };
   fill(T.vtri); fill(T.vtri_k); fill(T.vedge); fill(T.vedge_s); fill(T.bsrc); fill(T.vouter); fill(T.vinner); fill(T.vinner_s);
-  std::vector<int> cnt(nv, 0);
+  std::fill(cnt.begin(), cnt.end(), 0);
   for (long t = 0; t < nt; t++) for (int k = 0; k < 3; k++) {
     const long v = T.triangles[t][k];
-    if (cnt[v] >= D) return "vertex valence exceeds MAXD";
     T.vtri[v * D + cnt[v]] = (int)t; T.vtri_k[v * D + cnt[v]] = k; cnt[v]++;
   }
   std::fill(cnt.begin(), cnt.end(), 0);
   for (int e = 0; e < ne; e++) for (int s = 0; s < 2; s++) {
     const long v = T.edges[e][s];
-    if (cnt[v] >= D) return "vertex valence exceeds MAXD";
     T.vedge[v * D + cnt[v]] = e; T.vedge_s[v * D + cnt[v]] = s == 0 ? 1 : -1; cnt[v]++;
   }
   std::fill(cnt.begin(), cnt.end(), 0);
   for (int e = 0; e < ne; e++) for (int s = 0; s < 2; s++) {
     const long v = T.edge_bending_outer[e][s];
-    if (cnt[v] >= D) return "vertex valence exceeds MAXD";
+    if (cnt[v] >= D) return "vertex is the outer point of more edges than its valence";
     T.vouter[v * D + cnt[v]++] = e;
   }
   std::fill(cnt.begin(), cnt.end(), 0);
   for (int e = 0; e < T.nie; e++) for (int s = 0; s < 2; s++) {
     const long v = T.inner_edges[e][s];
-    if (cnt[v] >= D) return "too many inner edges on one vertex";
     T.vinner[v * D + cnt[v]] = e; T.vinner_s[v * D + cnt[v]] = s == 0 ? 1 : -1; cnt[v]++;
   }
+  for (long i = 0; i < nv; i++) for (size_t k = 0; k < src[i].size(); k++) T.bsrc[i * D + k] = src[i][k];
 
   // volume_eq: MeshMetrics::getVolume, helper/meshMetrics.h:167-177
   double vol = 0.0;
@@ -293,28 +428,6 @@ std::string build_cell_tables(CellTables &T, int model, int shape, const hc_para
   s = 0; for (double l : T.edge_length_eq) s += l; T.edge_mean_eq = s / ne;
   s = 0; for (double a : T.edge_angle_eq) s += a; T.angle_mean_eq = s / ne;
 
-  // neighbour rings: first neighbour in edge-list order, then walk the fan
-  // (mechanics/commonCellConstants.cpp:201-271)
-  T.vertex_vertexes.assign(nv, {-1, -1, -1, -1, -1, -1});
-  T.vertex_n_vertexes.assign(nv, 0);
-  for (int e = 0; e < ne; e++) {
-    const long a = T.edges[e][0], b = T.edges[e][1];
-    if (T.vertex_n_vertexes[a] >= 6 || T.vertex_n_vertexes[b] >= 6) return "vertex with more than 6 neighbours";
-    T.vertex_vertexes[a][T.vertex_n_vertexes[a]++] = b;
-    T.vertex_vertexes[b][T.vertex_n_vertexes[b]++] = a;
-  }
-  for (long v = 0; v < nv; v++) {
-    long cur = T.vertex_vertexes[v][0];
-    for (int n = 1; n < T.vertex_n_vertexes[v]; n++) {
-      auto it = half.find({v, cur});
-      if (it == half.end()) return "ring walk failed";
-      const auto &tr = T.triangles[it->second];
-      long next = -1;
-      for (int k = 0; k < 3; k++) if (tr[k] == v) next = tr[(k + 2) % 3];
-      cur = next;
-      T.vertex_vertexes[v][n] = cur;
-    }
-  }
   // equilibrium patch-centre distance (:274-305)
   T.patch_dist_eq.resize(nv);
   for (long i = 0; i < nv; i++) {
@@ -333,13 +446,6 @@ std::string build_cell_tables(CellTables &T, int model, int shape, const hc_para
     pn[0] /= l; pn[1] /= l; pn[2] /= l;
     T.patch_dist_eq[i] = dot(pn, dev);
   }
-  // bending sources for the gather form: {self} U ring, ascending
-  for (long i = 0; i < nv; i++) {
-    std::vector<long> src(T.vertex_vertexes[i].begin(), T.vertex_vertexes[i].begin() + T.vertex_n_vertexes[i]);
-    src.push_back(i);
-    std::sort(src.begin(), src.end());
-    for (size_t k = 0; k < src.size(); k++) T.bsrc[i * D + k] = (int)src[k];
-  }
 
   // moduli, mechanics/cellMechanics.h:50-78
   const double plc = 7.5e-9 / P.dx;
@@ -355,6 +461,9 @@ std::string build_cell_tables(CellTables &T, int model, int shape, const hc_para
     T.k_cytoskeleton = W->kCytoskeleton / P.df;
     T.core_radius = W->coreRadius / P.dx;
     T.wbc_radius = W->radius / P.dx;
+  }
+  if (model == HC_MODEL_RBC_MALARIA) {   // RbcMalariaModel::calculate_kInnerLink, mechanics/rbcMalariaModel.cpp:233-240
+    T.k_inner_link = S.kInnerLink * (P.kBT_lbm / plc);
   }
   return "";
 }

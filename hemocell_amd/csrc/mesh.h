@@ -26,24 +26,26 @@ struct CellTables {
   double diameter = 0;                         // of the undeformed mesh, lattice units
   double k_volume = 0, k_area = 0, k_link = 0, k_bend = 0, eta_m = 0;
   double k_inner_rigid = 0, k_cytoskeleton = 0, core_radius = 0, wbc_radius = 0;   // WBC_HO only, lattice units
+  double k_inner_link = 0;                     // RBC_MALARIA only, lattice units
 
   // ---- gather form used by the kernels (all int32, -1 padded) ----
-  static constexpr int MAXD = 8;                    // max incident elements kept per vertex
-  std::vector<int> vtri;      // [nv][MAXD] incident triangles, ascending id
-  std::vector<int> vtri_k;    // [nv][MAXD] corner index (0,1,2) of the vertex in that triangle
-  std::vector<int> vedge;     // [nv][MAXD] incident edges, ascending id
-  std::vector<int> vedge_s;   // [nv][MAXD] +1 if vertex is edge[0], -1 if edge[1]
-  std::vector<int> bsrc;      // [nv][MAXD] RBC bending sources: {self} U ring, ascending vertex id
+  // Row width md of every per-vertex list: MAXD, or MAXD_WIDE when one list of the mesh needs more than MAXD entries
+  // (general meshes, e.g. STL files with vertices of valence 9 or 10); the kernels are instantiated for both widths.
+  static constexpr int MAXD = 8, MAXD_WIDE = 16;
+  int md = MAXD;
+  std::vector<int> vtri;      // [nv][md] incident triangles, ascending id
+  std::vector<int> vtri_k;    // [nv][md] corner index (0,1,2) of the vertex in that triangle
+  std::vector<int> vedge;     // [nv][md] incident edges, ascending id
+  std::vector<int> vedge_s;   // [nv][md] +1 if vertex is edge[0], -1 if edge[1]
+  std::vector<int> bsrc;      // [nv][md] RBC bending sources: itself and every vertex whose ring holds it, ascending id
   // PLT: per vertex, edges that touch it as an outer point of the dihedral pair
-  std::vector<int> vouter;    // [nv][MAXD] ascending edge id
-  std::vector<int> vinner;    // [nv][MAXD] inner edges, ascending
-  std::vector<int> vinner_s;  // [nv][MAXD]
+  std::vector<int> vouter;    // [nv][md] ascending edge id
+  std::vector<int> vinner;    // [nv][md] inner edges, ascending
+  std::vector<int> vinner_s;  // [nv][md]
 };
 
-// builds everything from the material description; returns non-empty error on failure
-// (W: the WBC_HO constants, required for that model and ignored by the others)
-std::string build_cell_tables(CellTables &T, int model, int shape, const hc_params &P, const hc_material &M,
-                              const hc_wbc_material *W = nullptr);
+// builds everything from the cell description (hcp_celltype_create_ex); returns non-empty error on failure
+std::string build_cell_tables(CellTables &T, const hc_params &P, const hc_celltype_spec &S);
 
 // rotateTriangularMeshXYZ of io/readPositionsBloodCells.cpp:40-111 as a 3x3 matrix
 void rotation_matrix_xyz(double alpha, double beta, double gamma, double R[3][3]);

@@ -13,20 +13,25 @@ import xml.etree.ElementTree as ET
 import numpy as np
 
 from . import capi
-from .capi import HcError, Material, Params, WbcMaterial, check, dptr, lptr
+from .capi import CellTypeSpec, HcError, Material, Params, WbcMaterial, check, dptr, lptr
 
 HALO = 2
 
 MODEL_RBC_HO = 0
 MODEL_PLT_SIMPLE = 1
 MODEL_WBC_HO = 2
+MODEL_RBC_MALARIA = 3
 WBC_SPHERE = 0             # config/constant_defaults.h:83
 RBC_FROM_SPHERE = 1        # config/constant_defaults.h:80
+MESH_FROM_STL = 2          # config/constant_defaults.h:84
 ELLIPSOID_FROM_SPHERE = 6  # config/constant_defaults.h:81
 
 # examples/cell_shapes/WBC_HO.xml, kept as a data file with the test fixtures
 WBC_HO_XML = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "wbc_case",
                           "WBC_HO.xml")
+# cases/stretchMalaria/RBC_MALARIA.xml; its <StlFile> is resolved next to it
+MALARIA_XML = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "malaria_case",
+                           "RBC_MALARIA.xml")
 
 # examples/pipeflow/PLT.xml:14-38
 PLT_INNER_EDGES = np.array([[60, 65], [62, 64], [37, 42], [54, 56], [34, 40], [25, 46], [50, 59], [29, 47],
@@ -52,6 +57,12 @@ def read_material(path):
         except (TypeError, ValueError):
             pass
     return out
+
+
+def read_stl_file_tag(path):
+    """<MaterialModel><StlFile> of a cell XML, or None"""
+    el = ET.parse(path).getroot().find("MaterialModel/StlFile")
+    return None if el is None or not (el.text or "").strip() else el.text.strip()
 
 
 def init(device=0):
@@ -196,8 +207,11 @@ class CellType:
     """hemocell.addCellType<Mechanics>(name, constructType) for one type."""
 
     def __init__(self, P, model, shape, radius, min_triangles, kLink, kArea, kVolume, kBend, eta_m=0.0,
-                 aspect_ratio=0.3, inner_edges=None, wbc=None):
-        """wbc: (kInnerRigid, kCytoskeleton, coreRadius, radius) in SI units, for MODEL_WBC_HO only"""
+                 aspect_ratio=0.3, inner_edges=None, wbc=None, kInnerLink=None, stl=None, ex=False):
+        """wbc: (kInnerRigid, kCytoskeleton, coreRadius, radius) in SI units, for MODEL_WBC_HO only;
+        kInnerLink: for MODEL_RBC_MALARIA only; stl: the STL file of shape MESH_FROM_STL (any model).
+        The malaria model, STL meshes and ex=True go through hcp_celltype_create_ex, the rest through the entry point
+        of their model"""
         ensure_init()
         self.lib = capi.lib()
         M = Material()
@@ -212,7 +226,22 @@ class CellType:
             M.inner_edges = None
             M.n_inner = 0
         self.ptr = C.c_void_p()
+        if (stl is not None) != (shape == MESH_FROM_STL):
+            raise HcError("an STL file goes with shape MESH_FROM_STL, and that shape needs one")
+        if (kInnerLink is not None) != (model == MODEL_RBC_MALARIA):
+            raise HcError("kInnerLink goes with MODEL_RBC_MALARIA, and that model needs it")
+        W = None
         if model == MODEL_WBC_HO:
+            if wbc is None:
+                raise HcError("MODEL_WBC_HO needs wbc=(kInnerRigid, kCytoskeleton, coreRadius, radius)")
+            W = WbcMaterial(*[float(v) for v in wbc])
+        if ex or model == MODEL_RBC_MALARIA or shape == MESH_FROM_STL:
+            S = CellTypeSpec(model=int(model), shape=int(shape), material=M, kInnerLink=float(kInnerLink or 0.0),
+                             stl_path=None if stl is None else os.fsencode(stl))
+            S.wbc = C.pointer(W) if W is not None else None
+            self._spec = (S, W)
+            check(self.lib.hcp_celltype_create_ex(C.byref(self.ptr), C.byref(P), C.byref(S)))
+        elif model == MODEL_WBC_HO:
             if wbc is None:
                 raise HcError("MODEL_WBC_HO needs wbc=(kInnerRigid, kCytoskeleton, coreRadius, radius)")
             W = WbcMaterial(*[float(v) for v in wbc])
@@ -226,18 +255,42 @@ class CellType:
 
     @classmethod
     def rbc(cls, P, **kw):
-        """examples/pipeflow/RBC.xml with RbcHighOrderModel / RBC_FROM_SPHERE"""
+        """examples/pipeflow/RBC.xml with RbcHighOrderModel / RBC_FROM_SPHERE (MESH_FROM_STL when stl= is given)"""
         d = dict(radius=3.91e-6, min_triangles=600, kLink=15.0, kArea=5.0, kVolume=20.0, kBend=80.0, eta_m=0.0)
         d.update(kw)
-        return cls(P, MODEL_RBC_HO, RBC_FROM_SPHERE, **d)
+        return cls(P, MODEL_RBC_HO, MESH_FROM_STL if d.get("stl") is not None else RBC_FROM_SPHERE, **d)
 
     @classmethod
     def plt(cls, P, **kw):
-        """examples/pipeflow/PLT.xml with PltSimpleModel / ELLIPSOID_FROM_SPHERE"""
+        """examples/pipeflow/PLT.xml with PltSimpleModel / ELLIPSOID_FROM_SPHERE (MESH_FROM_STL when stl= is given)"""
         d = dict(radius=1.25e-6, min_triangles=66, kLink=25.0, kArea=8.0, kVolume=100.0, kBend=250.0, eta_m=0.0,
                  aspect_ratio=0.434782608696, inner_edges=PLT_INNER_EDGES)
         d.update(kw)
-        return cls(P, MODEL_PLT_SIMPLE, ELLIPSOID_FROM_SPHERE, **d)
+        return cls(P, MODEL_PLT_SIMPLE, MESH_FROM_STL if d.get("stl") is not None else ELLIPSOID_FROM_SPHERE, **d)
+
+    @classmethod
+    def malaria(cls, P, xml=None, stl=None, **kw):
+        """RbcMalariaModel on MESH_FROM_STL with the moduli, kInnerLink and inner edges of a malaria XML (default:
+        cases/stretchMalaria/RBC_MALARIA.xml) and the STL file its <StlFile> names, found next to the XML unless stl= is
+        given; keyword arguments override single values, kInnerLink included"""
+        xml = xml or MALARIA_XML
+        m = read_material(xml)
+        if stl is None:
+            tag = read_stl_file_tag(xml)
+            if tag is None:
+                raise HcError("%s has no <StlFile>" % xml)
+            stl = os.path.join(os.path.dirname(os.path.abspath(xml)), tag)
+        d = dict(radius=m["radius"], min_triangles=int(m.get("minNumTriangles", 0)), kLink=m["kLink"], kArea=m["kArea"],
+                 kVolume=m["kVolume"], kBend=m["kBend"], eta_m=m["eta_m"], inner_edges=m.get("inner_edges"),
+                 kInnerLink=m["kInnerLink"])
+        d.update(kw)
+        return cls(P, MODEL_RBC_MALARIA, MESH_FROM_STL, stl=stl, **d)
+
+    def malaria_constants(self):
+        """lattice-unit k_inner_link of an RBC_MALARIA type (0 for the other models)"""
+        out = np.zeros(1)
+        check(self.lib.hcp_celltype_malaria_constants(self.ptr, dptr(out)))
+        return dict(k_inner_link=float(out[0]))
 
     @classmethod
     def wbc(cls, P, xml=None, shape=WBC_SPHERE, **kw):

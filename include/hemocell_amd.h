@@ -4,7 +4,7 @@
  * Drop-in boundary for the one data-parallel path of HemoCell:
  * the D3Q19 Guo-BGK collide-stream, the phi2 immersed-boundary spread /
  * interpolate, the Euler vertex advance and the rbcHighOrderModel /
- * wbcHighOrderModel / pltSimpleModel membrane forces.  Every entry point names the reference
+ * wbcHighOrderModel / rbcMalariaModel / pltSimpleModel membrane forces.  Every entry point names the reference
  * interface it replaces (file:line relative to the HemoCell tree).  Plain
  * pointers and sizes only; no C++/torch types cross this boundary.  All
  * functions return 0 on success and a non-zero code on failure, with the
@@ -206,9 +206,11 @@ double hcl_mlups_bytes_per_node(const hc_lattice *L); /* algorithmic bytes per n
 /* --------------------------------------------------------------- cell types */
 #define HC_MODEL_RBC_HO 0     /* mechanics/rbcHighOrderModel.cpp */
 #define HC_MODEL_PLT_SIMPLE 1 /* mechanics/pltSimpleModel.cpp    */
-#define HC_MODEL_WBC_HO 2     /* mechanics/wbcHighOrderModel.cpp: hcp_celltype_create_wbc */
+#define HC_MODEL_WBC_HO 2     /* mechanics/wbcHighOrderModel.cpp: hcp_celltype_create_wbc or _ex */
+#define HC_MODEL_RBC_MALARIA 3 /* mechanics/rbcMalariaModel.cpp: hcp_celltype_create_ex */
 #define HC_SHAPE_WBC_SPHERE 0            /* config/constant_defaults.h:83 */
 #define HC_SHAPE_RBC_FROM_SPHERE 1       /* config/constant_defaults.h:80 */
+#define HC_SHAPE_MESH_FROM_STL 2         /* config/constant_defaults.h:84: hcp_celltype_create_ex */
 #define HC_SHAPE_ELLIPSOID_FROM_SPHERE 6 /* config/constant_defaults.h:81 */
 
 typedef struct hc_params { /* Parameters::lbm_base_parameters, mechanics/constantConversion.cpp:36-59 */
@@ -243,6 +245,24 @@ typedef struct hc_wbc_material {
 int hcp_celltype_create_wbc(hc_celltype **out, int shape, const hc_params *P, const hc_material *M, const hc_wbc_material *W);
 /* lattice-unit WBC constants: out = k_inner_rigid, k_cytoskeleton, core_radius, radius (0 for the other models) */
 int hcp_celltype_wbc_constants(const hc_celltype *T, double out[4]);
+
+/* everything hemocell.addCellType<Model>(name, constructType) reads from a cell XML, for any model and construct type */
+typedef struct hc_celltype_spec {
+  int model;                  /* HC_MODEL_* */
+  int shape;                  /* HC_SHAPE_* */
+  hc_material material;       /* min_triangles is not read for HC_SHAPE_MESH_FROM_STL */
+  const hc_wbc_material *wbc; /* HC_MODEL_WBC_HO only, else NULL */
+  double kInnerLink;          /* HC_MODEL_RBC_MALARIA only: <kInnerLink>, in kBT per persistence length (may be 0) */
+  const char *stl_path;       /* HC_SHAPE_MESH_FROM_STL only: <StlFile>, binary or ASCII STL, opened as given */
+} hc_celltype_spec;
+/* the general creation call: accepts every model x shape pair.  MESH_FROM_STL follows constructCell
+ * (helper/meshGeneratingFunctions.hh:275-288): largest bounding-box extent scaled to 2 radius, rotate_zxz(pi/2, pi/2, 0),
+ * centre 0, vertices welded by first occurrence on exact coordinates, inflated 1e-3 along the vertex normals.  A missing
+ * file, an open or non-manifold mesh and a degenerate triangle are refused.  RBC_MALARIA is the RBC_HO model with the
+ * membrane viscosity always evaluated plus the linear inner links of mechanics/rbcMalariaModel.cpp:198-217. */
+int hcp_celltype_create_ex(hc_celltype **out, const hc_params *P, const hc_celltype_spec *S);
+/* lattice-unit malaria constant: out[0] = k_inner_link (mechanics/rbcMalariaModel.cpp:233-240; 0 for the other models) */
+int hcp_celltype_malaria_constants(const hc_celltype *T, double out[1]);
 int hcp_celltype_destroy(hc_celltype *T);
 /* table sizes: out[0..3] = vertices, triangles, edges, inner edges */
 int hcp_celltype_sizes(const hc_celltype *T, int out[4]);
