@@ -7,7 +7,9 @@
 //   core/hemoCell.cpp:299-376                                                 iterate
 #include "cells.h"
 #include <cstddef>
+#include <unordered_map>
 #include <utility>
+#include <vector>
 
 namespace {
 
@@ -665,7 +667,36 @@ int hcp_download_cell_ids(hc_cells *C, long *ids) {
 int hcp_add_vertex_force(hc_cells *C, const long *vertex_index, int n, const double *f) {
   HC_REQUIRE(C && vertex_index && f && n >= 0, "hcp_add_vertex_force: bad arguments");
   if (n == 0) return HC_OK;
-  int rc = sync_to_device(C); if (rc != HC_OK) return rc;
+  // vertex_index counts vertices in download order, which no longer lists a cell the device deleted in the last hc_iterate
+  int rc = settle(C); if (rc != HC_OK) return rc;
+  rc = sync_to_device(C); if (rc != HC_OK) return rc;
+  // download order (types packed back to back) -> device slot (regions have gaps); nothing is touched before all are valid
+  std::vector<long> slot((size_t)n);
+  for (int i = 0; i < n; i++) {
+    long v = vertex_index[i], packed0 = 0; bool found = false;
+    for (int t = 0; t < C->ntypes && !found; t++) {
+      const long nt = C->ncells[t] * C->types[t]->host.nv;
+      if (v >= packed0 && v < packed0 + nt) { slot[(size_t)i] = C->first[t] + (v - packed0); found = true; }
+      packed0 += nt;
+    }
+    HC_REQUIRE(found, "hcp_add_vertex_force: vertex index out of range");
+  }
+  // The entries act one after another in list order (helper/hemoCellStretch.cpp:63-78), a vertex listed twice included.
+  // The k-th entry of a vertex goes into round k; one launch per round, so no two threads of a launch share a vertex and
+  // the adds to one vertex land in list order.  A list without repeats is one round, one launch.
+  std::vector<int> round((size_t)n);
+  std::vector<long> start(2, 0);   // start[k] = first entry of round k in the staged list
+  {
+    std::unordered_map<long, int> seen;
+    seen.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+      const int k = seen[slot[(size_t)i]]++;
+      round[(size_t)i] = k;
+      if (k + 2 > (int)start.size()) start.push_back(0);
+      start[(size_t)k + 1]++;
+    }
+  }
+  for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
   const size_t bytes = (size_t)n * (sizeof(long) + 3 * sizeof(double));
   if (bytes > C->vf_cap) {
     HC_HIP(hipStreamSynchronize(hc::stream()));
@@ -679,24 +710,27 @@ int hcp_add_vertex_force(hc_cells *C, const long *vertex_index, int n, const dou
   } else {
     HC_HIP(hipEventSynchronize(C->vf_done));   // the previous call's copy has left the pinned block
   }
-  // vertex_index counts vertices in download order (types packed back to back); device regions have gaps
+  // staged round by round, list order within a round
   long *h_idx = reinterpret_cast<long *>(C->h_vf);
   double *h_f = reinterpret_cast<double *>(C->h_vf + (size_t)n * sizeof(long));
-  for (int i = 0; i < n; i++) {
-    long v = vertex_index[i], packed0 = 0; bool found = false;
-    for (int t = 0; t < C->ntypes && !found; t++) {
-      const long nt = C->ncells[t] * C->types[t]->host.nv;
-      if (v >= packed0 && v < packed0 + nt) { h_idx[i] = C->first[t] + (v - packed0); found = true; }
-      packed0 += nt;
+  {
+    std::vector<long> next(start.begin(), start.end() - 1);
+    for (int i = 0; i < n; i++) {
+      const long j = next[(size_t)round[(size_t)i]]++;
+      h_idx[j] = slot[(size_t)i];
+      for (int d = 0; d < 3; d++) h_f[3 * j + d] = f[3 * (size_t)i + d];
     }
-    HC_REQUIRE(found, "hcp_add_vertex_force: vertex index out of range");
   }
-  std::memcpy(h_f, f, (size_t)3 * n * sizeof(double));
   HC_HIP(hipMemcpyAsync(C->d_vf, C->h_vf, bytes, hipMemcpyHostToDevice, hc::stream()));
   HC_HIP(hipEventRecord(C->vf_done, hc::stream()));
-  hipLaunchKernelGGL(add_vertex_force_kernel, dim3((n + 255) / 256), dim3(256), 0, hc::stream(), n, (const long *)C->d_vf,
-                     (const double *)(C->d_vf + (size_t)n * sizeof(long)), C->frc[0], C->frc[1], C->frc[2]);
-  HC_HIP(hipGetLastError());
+  const long *d_idx = (const long *)C->d_vf;
+  const double *d_f = (const double *)(C->d_vf + (size_t)n * sizeof(long));
+  for (size_t k = 0; k + 1 < start.size(); k++) {
+    const int m = (int)(start[k + 1] - start[k]);
+    hipLaunchKernelGGL(add_vertex_force_kernel, dim3((m + 255) / 256), dim3(256), 0, hc::stream(), m, d_idx + start[k], d_f + 3 * start[k],
+                       C->frc[0], C->frc[1], C->frc[2]);
+    HC_HIP(hipGetLastError());
+  }
   return HC_OK;
 }
 

@@ -339,7 +339,10 @@ int hcp_download_cell_ids(hc_cells *C, long *ids);
  * upload replaces the whole population by the given records, in any order, every cell complete. */
 int hcp_download_records(hc_cells *C, void *records, long n_records);
 int hcp_upload_records(hc_cells *C, const void *records, long n_records);
-/* HemoCellStretch::ForceForcedLsps (helper/hemoCellStretch.cpp:63-78): sv.force += f on listed vertices */
+/* HemoCellStretch::ForceForcedLsps (helper/hemoCellStretch.cpp:63-78): sv.force += f on listed vertices.  vertex_index
+ * counts vertices in hcp_download order at the time of the call (cells deleted by the last hc_iterate are not counted).
+ * The result is bit for bit that of `force[vertex_index[i]] += f[i]` for i = 0 .. n-1 in list order, also when a vertex
+ * is listed more than once; an index outside [0, number of vertices) refuses the whole call and changes nothing. */
 int hcp_add_vertex_force(hc_cells *C, const long *vertex_index, int n, const double *f /*[n][3]*/);
 /* hemocell.setRepulsion(k, cutoff) + setRepulsionTimeScaleSeperation (core/hemoCell.cpp:394-397,420-426); the
  * cutoff is given in lattice units (the facade converts from micrometres).  hc_iterate then evaluates
