@@ -91,6 +91,10 @@ SIGNATURES = {
     "hcl_set_body_force": (C.c_int, [VP, c_double_p]),
     "hcl_set_wall_velocity": (C.c_int, [VP, C.c_int, c_double_p]),
     "hcl_collide_stream": (C.c_int, [VP, C.c_int]),
+    "hcl_set_lees_edwards": (C.c_int, [VP, C.c_double, C.c_double]),
+    "hcl_set_lees_edwards_displacement": (C.c_int, [VP, C.c_double, C.c_double]),
+    "hcl_lees_edwards_apply": (C.c_int, [VP]),
+    "hcl_lees_edwards_state": (C.c_int, [VP, c_double_p]),
     "hcl_collide_stream_part": (C.c_int, [VP, C.c_int]),
     "hcl_step_end": (C.c_int, [VP]),
     "hcl_download_populations": (C.c_int, [VP, c_double_p]),

@@ -157,7 +157,7 @@ class Config {
 
 // ------------------------------------------------------------------ mechanics/constantConversion.h
 struct Parameters {
-  static T dt, dx, dm, df, nu_p, rho_p, tau, re, nu_lbm, u_lbm_max, shearrate_lbm, kBT_lbm, kBT_p, ef_lbm, f_limit, pipe_radius;
+  static T dt, dx, dm, df, nu_p, rho_p, tau, re, nu_lbm, u_lbm_max, shearrate_lbm, kBT_lbm, kBT_p, ef_lbm, f_limit, pipe_radius, LE_force;
   static hc_params &raw() { static hc_params p; return p; }
   static void lbm_base_parameters(Config &cfg) {
     hc_params &P = raw();
@@ -191,6 +191,14 @@ struct Parameters {
     shearrate_lbm = shearrate_p * dt;
     u_lbm_max = shearrate_lbm;
   }
+  static void lbm_LE_parameters(Config &cfg, T nz) {        // :92-100
+    lbm_base_parameters(cfg);
+    T shearrate_p = cfg["domain"]["shearrate"].read<T>();
+    re = (nz * (shearrate_p * (nz * 0.5))) / nu_p;
+    shearrate_lbm = shearrate_p * dt;
+    T Vmax = shearrate_lbm * nz * 0.5;
+    LE_force = 8 * nu_lbm * Vmax * 0.5 / std::pow(nz / 4, 2);
+  }
   static void printParameters() {                            // :104-116
     hlog << "(HemoCell) System parameters:" << endl;
     hlog << "\t dx: \t" << dx << endl << "\t dt: \t" << dt << endl << "\t dm: \t" << dm << endl << "\t dN: \t" << df << endl;
@@ -200,7 +208,7 @@ struct Parameters {
 #ifdef HEMOCELL_COMPAT_MAIN
 T Parameters::dt = 0, Parameters::dx = 0, Parameters::dm = 0, Parameters::df = 0, Parameters::nu_p = 0, Parameters::rho_p = 0, Parameters::tau = 0,
   Parameters::re = 0, Parameters::nu_lbm = 0, Parameters::u_lbm_max = 0, Parameters::shearrate_lbm = 0, Parameters::kBT_lbm = 0, Parameters::kBT_p = 0,
-  Parameters::ef_lbm = 0, Parameters::f_limit = 0, Parameters::pipe_radius = 0;
+  Parameters::ef_lbm = 0, Parameters::f_limit = 0, Parameters::pipe_radius = 0, Parameters::LE_force = 0;
 #endif
 
 // helper/profiler.h:46-77 / config/config.h:80-96: hemo::global.statistics; backed by the library's hipEvent timers
@@ -579,7 +587,8 @@ class HemoCell {
     global.checkpointDirectory = outDir + "/" + chk + "/";
   }
 
-  void latticeEquilibrium(T rho, hemo::Array<T, 3> vel) { lattice->eq_rho = rho; for (int d = 0; d < 3; d++) lattice->eq_u[d] = vel[d]; lattice->dirty_layout = true; }
+  // (the equilibrium replaces whatever an earlier lattice->initialize() did to the populations: its Lees-Edwards pass too)
+  void latticeEquilibrium(T rho, hemo::Array<T, 3> vel) { lattice->eq_rho = rho; for (int d = 0; d < 3; d++) lattice->eq_u[d] = vel[d]; lattice->le.init_pass = false; lattice->dirty_layout = true; }
   void initializeCellfield() {
     cellfields = new HemoCellFields(*this);
     int env = 25;   // core/hemoCell.cpp:139 reads it here; core/hemoCellFields.cpp:43 prints it.  Used by loadParticles() on slab runs
@@ -656,6 +665,7 @@ class HemoCell {
   void doLoadBalance() { hlog << "(HemoCell) (LoadBalancer) one x-slab per rank: nothing to balance" << endl; }
   void doRestructure(bool = true) { hlog << "(HemoCell) (LoadBalancer) one x-slab per rank: nothing to restructure" << endl; }
   bool loadParticlesIsCalled = false, sanityCheckDone = false, partOfpreInlet = false, leesEdwardsBC = false;
+  double *LEcurrentDisplacement = nullptr;   // hemocell.h:147: LeesEdwardsBC's constructor points it at its displacement
   unsigned int lastOutputAt = 0;
   void loadParticles();
   void loadCheckPoint();
@@ -666,10 +676,19 @@ class HemoCell {
   // 4a).  So the call only queues the iteration; the queue is run -- one hc_iterate for all of it -- before anything can
   // observe or change the state: every path to the device goes through lattice->device() / cellfields->device(), which
   // flush first.  What a driver sees (iter, statistics, output, forces it adds between iterations) is unchanged.
+  //
+  // Lees-Edwards: a step uses the displacement the driver's LeesEdwardsBC holds when it calls iterate().  The library advances
+  // D after every step as updateLECurDisplacement(iter) would; as long as the driver's value is the one that schedule gives,
+  // the queue goes on, otherwise it is run first and D is set explicitly.
   void iterate() {
     if (!lattice->before_access) lattice->before_access = [this] { flush(); };
     lattice->sync_force();   // what the driver wrote since the last iteration zeroed the field; usually the same force again
+    if (lattice->le.on) {
+      if (leesEdwardsBC) refuse("the Lees-Edwards x-shift of particle envelopes (leesEdwardsBC = true)");
+      if (pending && !(*lattice->le.cur == le_scheduled_D())) flush();
+    }
     if (!pending) {   // first queued iteration: make sure everything it needs exists and settings are pushed
+      if (lattice->le.on) { lattice->device(); lattice->le_sync(); le_set_D = *lattice->le.cur; }
       hc_cells *c = cellfields->device();
       if (boundaryRepulsionEnabled && !boundaryRepulsionPushed) { hc_check(hcp_set_boundary_repulsion(c, boundaryRepulsionConstant_, boundaryRepulsionCutoff_, (int)boundaryRepulsionTimescale), "hcp_set_boundary_repulsion"); boundaryRepulsionPushed = true; }
       if (repulsionEnabled && !repulsionPushed) { hc_check(hcp_set_repulsion(c, repulsionConstant_, repulsionCutoff_, (int)repulsionTimescale), "hcp_set_repulsion"); repulsionPushed = true; }
@@ -697,6 +716,9 @@ class HemoCell {
     flushing = false;
   }
   unsigned int pending = 0, queued_timescale = 1; bool flushing = false;
+  // what the library's schedule has made D after the queued steps (hcl_set_lees_edwards_displacement)
+  double le_set_D = 0;
+  double le_scheduled_D() const { return lattice->le.d != 0 ? std::fmod(lattice->le.d * (double)iter, (double)lattice->nx) : le_set_D; }
 
   bool outputInSiUnits = true;
   bool repulsionEnabled = false, repulsionPushed = false; T repulsionConstant_ = 0, repulsionCutoff_ = 0; unsigned int repulsionTimescale = 1;

@@ -180,8 +180,26 @@ class MultiBlockLattice3D {
   plint getNz() const { return nz; }
   void toggleInternalStatistics(bool) {}
   Periodicity3D &periodicity() { return per; }
-  void initialize() {}
-  void collideAndStream() { device(); hc_check(hcl_collide_stream(dev, 1), "collideAndStream"); }
+  // Palabos' initialize() runs the integrated data processors once: with a Lees-Edwards boundary installed
+  // (hemo::LeesEdwardsBC::initialize) that is one pass, applied when the device lattice is created, or at once if it exists
+  void initialize() {
+    if (!le.on) return;
+    le.init_pass = true; le.init_D = *le.cur;
+    if (dev && !dirty_layout) { device(); le_pass_now(); }
+  }
+  void collideAndStream() { device(); le_sync(); hc_check(hcl_collide_stream(dev, 1), "collideAndStream"); }
+
+  // ---- Lees-Edwards boundary (helper/leesEdwardsBC.h): the pass runs inside the library after every stream
+  struct LeesEdwards {
+    bool on = false, init_pass = false;
+    double v_top = 0, v_bottom = 0, d = 0, init_D = 0;
+    double *cur = nullptr;   // LeesEdwardsBC::LEcurrentDisplacement, what the driver updates
+  } le;
+  void le_sync() { if (le.on) hc_check(hcl_set_lees_edwards_displacement(dev, *le.cur, le.d), "hcl_set_lees_edwards_displacement"); }
+  void le_pass_now() {
+    hc_check(hcl_set_lees_edwards_displacement(dev, le.init_D, le.d), "hcl_set_lees_edwards_displacement");
+    hc_check(hcl_lees_edwards_apply(dev), "hcl_lees_edwards_apply");
+  }
 
   // ---- used by the shims below and by hemo::HemoCell
   // The device lattice of THIS rank: the whole domain on one GPU, or -- when the run was started as several ranks
@@ -225,6 +243,10 @@ class MultiBlockLattice3D {
     for (size_t k = 0; k < wall_u.size(); k++) { double w[3] = {wall_u[k][0], wall_u[k][1], wall_u[k][2]}; hc_check(hcl_set_wall_velocity(dev, 3 + (int)k, w), "hcl_set_wall_velocity"); }
     double u[3] = {eq_u[0], eq_u[1], eq_u[2]};
     hc_check(hcl_init_equilibrium(dev, eq_rho, u), "hcl_init_equilibrium");
+    if (le.on) {
+      hc_check(hcl_set_lees_edwards(dev, le.v_top, le.v_bottom), "hcl_set_lees_edwards");
+      if (le.init_pass) le_pass_now();
+    }
     dirty_layout = false; dirty_force = true;
     push_force();
     return dev;

@@ -906,6 +906,10 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     if (overlap && (rc = hc::fork()) != HC_OK) return rc;
     if ((rc = hcl_collide_stream_part(L, 0)) != HC_OK) return rc;               // :317
     hcl_step_end(L);
+    if (L->le_on) {   // the Lees-Edwards processors of collideAndStream, on the main stream: they touch populations only
+      if ((rc = hc::lees_edwards_step(L)) != HC_OK) return rc;
+      if (L->le_d != 0.0) L->le_D = fmod(L->le_d * (double)(it + 1), (double)L->nx);   // LeesEdwardsBC::updateLECurDisplacement(iter)
+    }
     if (particle_step) { if ((rc = hcp_interpolate(C)) != HC_OK) return rc; }   // :327-332
     if (overlap) hc::route(1);
     if ((rc = hcp_advance(C, 0)) != HC_OK) return rc;                           // :342

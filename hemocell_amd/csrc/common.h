@@ -34,7 +34,7 @@ bool forked();   // between fork() and join()
   } while (0)
 
 // per-kernel hipEvent timing (hc_profile_*)
-enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them
+enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them
 struct ProfScope {
   int k; bool on;
   hipEvent_t a, b;
@@ -134,7 +134,16 @@ struct hc_lattice {
   // instead of gathering 19 populations there.  Valid from the exchange until the next hcl_step_end.
   double *halo_u[2] = {nullptr, nullptr};
   bool halo_u_valid = false;
+  // Lees-Edwards pass (hcl_set_lees_edwards): run after every hcl_step_end of hcl_collide_stream / hc_iterate.  le_D is the
+  // current displacement; with le_d != 0, hc_iterate sets it to fmod(le_d * iter, nx) after each step
+  bool le_on = false;
+  double le_D = 0.0, le_d = 0.0, le_v_top = 0.0, le_v_bottom = 0.0;
+  double *le_buf = nullptr;   // [2][19][nx ny] post-pass values of the top and bottom layers
 };
+
+namespace hc {
+int lees_edwards_step(hc_lattice *L);   // lattice.hip: the pass after a step, when enabled
+}
 
 // slab.hip: HemoCell::iterate / collideAndStream on one x-slab of a multi-GPU run (halo and envelope exchange inside)
 namespace hcs {

@@ -391,6 +391,93 @@ __global__ __launch_bounds__(256) void fluid_stats_kernel(LatArgs a, int what, d
   stat_block_store(acc, partial);
 }
 
+// ---- Lees-Edwards pass (helper/leesEdwardsBC.h): LeesEdwardsBCGetPopulations / LeesEdwardsBCSetPopulations, the two data
+// processors Palabos runs after the stream of collideAndStream().  Only lattices with hcl_set_lees_edwards run it.
+// Thread t -> layer t / (nx ny) (0: top z = nz-1, 1: bottom z = 0), x, y.  le_buf is [2][19][nx ny].
+
+// BGKdynamics::collideExternal(cell, rhoBar, j, thetaBar = 0): bgk_ma2 relaxation towards the equilibrium of the given rhoBar
+// and j, no forcing term; the operation order of collide_guo's relaxation loop
+__device__ __forceinline__ void collide_external(double f[HC_Q], double rhoBar, double j0, double j1, double j2, double omega) {
+  const double invRho = 1.0 / (1.0 + rhoBar);
+  const double jSqr = j0 * j0 + j1 * j1 + j2 * j2;
+  const double one_m_omega = 1.0 - omega;
+#define M(Q, CX, CY, CZ)                                                                     \
+  {                                                                                          \
+    const double c_j = cdot<CX, CY, CZ>(j0, j1, j2);                                         \
+    const double feq = tq(Q) * (rhoBar + 3.0 * c_j + invRho * (4.5 * c_j * c_j - 1.5 * jSqr)); \
+    f[Q] *= one_m_omega;                                                                     \
+    f[Q] += omega * feq;                                                                     \
+  }
+  FOR_Q(M)
+#undef M
+}
+
+__device__ __forceinline__ long modp(long a, long b) { return (a % b + b) % b; }
+
+// the Get processor: every value from the state before the pass
+__global__ __launch_bounds__(256) void le_gather_kernel(LatArgs a, double *buf, double D, double v_top, double v_bottom) {
+  const long nxy = (long)a.nx * a.ny;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 2 * nxy) return;
+  const int top = t < nxy ? 1 : 0;
+  const long r = top ? t : t - nxy;
+  const int x = (int)(r / a.ny), y = (int)(r - (long)x * a.ny);
+  const int z = top ? a.nz - 1 : 0;
+  const long row = (long)y * a.nz + z;
+  const long node = (long)(x + HALO) * a.xs + row;
+  double f[HC_Q];
+  pull(a.fin, a.qs, node, neighbours(a, x, y, z), f);
+  double rhoBar = 0.0;
+#pragma unroll
+  for (int q = 0; q < HC_Q; q++) rhoBar += f[q];
+  collide_external(f, rhoBar, top ? v_top : v_bottom, 0.0, 0.0, a.omega);
+  // the two source nodes of the same layer; the fraction g of s1 and (1 - g) of s2 (D < 0: g < 0, an extrapolation)
+  const double g = fmod(D, 1.0);
+  const long s1 = top ? modp((long)ceil(D + (double)x), a.nx) : modp((long)floor(-D + (double)x), a.nx);
+  const long s2 = top ? modp((long)floor(D + (double)x), a.nx) : modp((long)ceil(-D + (double)x), a.nx);
+  double f1[HC_Q], f2[HC_Q];   // only the five populations used below are loaded
+  pull(a.fin, a.qs, (s1 + HALO) * a.xs + row, neighbours(a, (int)s1, y, z), f1);
+  pull(a.fin, a.qs, (s2 + HALO) * a.xs + row, neighbours(a, (int)s2, y, z), f2);
+  if (top) {   // 3 <- 3, 6 <- 16, 8 <- 8, 16 <- 6, 18 <- 18
+    f[3] = g * f1[3] + (1 - g) * f2[3];
+    f[6] = g * f1[16] + (1 - g) * f2[16];
+    f[8] = g * f1[8] + (1 - g) * f2[8];
+    f[16] = g * f1[6] + (1 - g) * f2[6];
+    f[18] = g * f1[18] + (1 - g) * f2[18];
+  } else {     // 7 <- 15, 9 <- 9, 12 <- 12, 15 <- 7, 17 <- 17
+    f[7] = g * f1[15] + (1 - g) * f2[15];
+    f[9] = g * f1[9] + (1 - g) * f2[9];
+    f[12] = g * f1[12] + (1 - g) * f2[12];
+    f[15] = g * f1[7] + (1 - g) * f2[7];
+    f[17] = g * f1[17] + (1 - g) * f2[17];
+  }
+  double *o = buf + (long)(1 - top) * HC_Q * nxy + r;
+#pragma unroll
+  for (int q = 0; q < HC_Q; q++) o[(long)q * nxy] = f[q];
+}
+
+// the Set processor: S(n, q) is stored in the slot P(n - c_q, q) that pull() reads for node n.  Each slot has exactly one
+// reader, so this changes the post-stream state of the two layers and nothing else.
+__global__ __launch_bounds__(256) void le_scatter_kernel(LatArgs a, const double *buf) {
+  const long nxy = (long)a.nx * a.ny;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 2 * nxy) return;
+  const int top = t < nxy ? 1 : 0;
+  const long r = top ? t : t - nxy;
+  const int x = (int)(r / a.ny), y = (int)(r - (long)x * a.ny);
+  const int z = top ? a.nz - 1 : 0;
+  const long node = (long)(x + HALO) * a.xs + (long)y * a.nz + z;
+  const Nbr n = neighbours(a, x, y, z);
+  const double *in = buf + (long)(1 - top) * HC_Q * nxy + r;
+#define M(Q, CX, CY, CZ)                                                       \
+  {                                                                            \
+    bool ok; const long off = src_off<CX, CY, CZ>(n, ok);                      \
+    if (ok) a.fout[(long)Q * a.qs + node + off] = in[(long)Q * nxy];           \
+  }
+  FOR_Q(M)
+#undef M
+}
+
 struct HaloArgs {
   double *f;          // population buffer
   double *buf;        // contiguous staging
@@ -529,7 +616,33 @@ int launch_collide(hc_lattice *L, int x_begin, int nplanes, int x2 = 0, int n2 =
   return HC_OK;
 }
 
+int launch_lees_edwards(hc_lattice *L) {
+  hc::ProfScope prof(hc::PK_LEES_EDWARDS);
+  LatArgs a = make_args(L);
+  a.fout = L->f[L->cur];   // the buffer the next collide reads: a.fin
+  const long nthreads = 2L * L->nx * L->ny;
+  const dim3 grid((unsigned)((nthreads + 255) / 256));
+  hipLaunchKernelGGL(le_gather_kernel, grid, dim3(256), 0, hc::stream(), a, L->le_buf, L->le_D, L->le_v_top, L->le_v_bottom);
+  HC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(le_scatter_kernel, grid, dim3(256), 0, hc::stream(), a, (const double *)L->le_buf);
+  HC_HIP(hipGetLastError());
+  return HC_OK;
+}
+
 }  // namespace
+
+int hc::lees_edwards_step(hc_lattice *L) { return L->le_on ? launch_lees_edwards(L) : HC_OK; }
+
+// the four z-layers a Lees-Edwards pass reads or writes populations of (z = 0, 1, nz-2, nz-1): every bulk node there must
+// be fluid, so that each stored slot the pass writes has the one reader the pass means (mask: device numbering)
+static bool le_layers_fluid(const hc_lattice *L, const uint8_t *mask, size_t xs) {
+  const int zs[4] = {0, 1, L->nz - 2, L->nz - 1};
+  for (int x = HALO; x < L->nx + HALO; x++)
+    for (int y = 0; y < L->ny; y++)
+      for (int k = 0; k < 4; k++)
+        if (mask[(size_t)x * xs + (size_t)y * L->nz + zs[k]] != 0) return false;
+  return true;
+}
 
 static int g_force_plane_padding = 0;   // tests / A-B runs: 1 = pad the planes of every lattice, -1 = of none, 0 = by size
 
@@ -609,6 +722,7 @@ int hcl_destroy(hc_lattice *L) {
   if (L->row_cum) hipFree(L->row_cum);
   if (L->blk_row) hipFree(L->blk_row);
   if (L->wallbrick) hipFree(L->wallbrick);
+  if (L->le_buf) hipFree(L->le_buf);
   delete L;
   return HC_OK;
 }
@@ -633,6 +747,10 @@ int hcl_node_counts(const hc_lattice *L, long counts[3]) {
 
 int hcl_set_mask(hc_lattice *L, const uint8_t *mask_with_halo) {
   HC_REQUIRE(L && mask_with_halo, "hcl_set_mask: null pointer");
+  if (L->le_on && !le_layers_fluid(L, mask_with_halo, L->plane)) {
+    hc::set_error("hcl_set_mask: the lattice has a Lees-Edwards boundary; the layers z = 0, 1, nz-2 and nz-1 must hold fluid nodes only");
+    return HC_ERR_STATE;
+  }
   // host copy in the device numbering (x-planes xs apart); the padding between planes is inert solid
   L->hmask.assign(L->npad, 2);
   for (int x = 0; x < L->nx + 2 * HALO; x++)
@@ -761,7 +879,42 @@ int hcl_collide_stream(hc_lattice *L, int nsteps) {
     int rc = hcl_collide_stream_part(L, 0);
     if (rc != HC_OK) return rc;
     hcl_step_end(L);
+    if ((rc = hc::lees_edwards_step(L)) != HC_OK) return rc;   // Palabos runs the LE processors after the stream; D stays as it is
   }
+  return HC_OK;
+}
+
+int hcl_set_lees_edwards(hc_lattice *L, double v_top, double v_bottom) {
+  HC_REQUIRE(L, "hcl_set_lees_edwards: null lattice");
+  HC_REQUIRE(L->n_slabs == 1, "hcl_set_lees_edwards: the Lees-Edwards boundary needs the whole domain on one GPU (n_slabs = 1)");
+  HC_REQUIRE(L->periodic[0] && L->periodic[1] && L->periodic[2], "hcl_set_lees_edwards: the lattice must be periodic on all three axes");
+  HC_REQUIRE(L->nz >= 4, "hcl_set_lees_edwards: nz must be at least 4");
+  if (!le_layers_fluid(L, L->hmask.data(), L->xs)) {
+    hc::set_error("hcl_set_lees_edwards: the layers z = 0, 1, nz-2 and nz-1 must hold fluid nodes only");
+    return HC_ERR_STATE;
+  }
+  if (!L->le_buf) HC_HIP(hipMalloc((void **)&L->le_buf, (size_t)2 * HC_Q * L->nx * L->ny * sizeof(double)));
+  L->le_on = true; L->le_v_top = v_top; L->le_v_bottom = v_bottom; L->le_D = 0.0; L->le_d = 0.0;
+  return HC_OK;
+}
+
+int hcl_set_lees_edwards_displacement(hc_lattice *L, double D, double d_per_iteration) {
+  HC_REQUIRE(L, "hcl_set_lees_edwards_displacement: null lattice");
+  if (!L->le_on) { hc::set_error("hcl_set_lees_edwards_displacement: no Lees-Edwards boundary (hcl_set_lees_edwards)"); return HC_ERR_STATE; }
+  L->le_D = D; L->le_d = d_per_iteration;
+  return HC_OK;
+}
+
+int hcl_lees_edwards_apply(hc_lattice *L) {
+  HC_REQUIRE(L, "hcl_lees_edwards_apply: null lattice");
+  if (!L->le_on) { hc::set_error("hcl_lees_edwards_apply: no Lees-Edwards boundary (hcl_set_lees_edwards)"); return HC_ERR_STATE; }
+  return launch_lees_edwards(L);
+}
+
+int hcl_lees_edwards_state(const hc_lattice *L, double out[4]) {
+  HC_REQUIRE(L && out, "hcl_lees_edwards_state: null pointer");
+  if (!L->le_on) { hc::set_error("hcl_lees_edwards_state: no Lees-Edwards boundary (hcl_set_lees_edwards)"); return HC_ERR_STATE; }
+  out[0] = L->le_D; out[1] = L->le_v_top; out[2] = L->le_v_bottom; out[3] = L->le_d;
   return HC_OK;
 }
 

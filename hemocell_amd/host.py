@@ -7,6 +7,7 @@ applyConstitutiveModel, iterate, setMaterialTimeScaleSeparation ...  Every
 method is one call into libhemocell_amd.so; nothing is computed here.
 """
 import ctypes as C
+import math
 import os
 import xml.etree.ElementTree as ET
 
@@ -142,6 +143,24 @@ class Lattice:
     def collideAndStream(self, steps=1):
         check(self.lib.hcl_collide_stream(self.ptr, int(steps)))
 
+    # helper/leesEdwardsBC.h: the pass after every stream (hcl_set_lees_edwards)
+    def setLeesEdwards(self, v_top, v_bottom):
+        check(self.lib.hcl_set_lees_edwards(self.ptr, float(v_top), float(v_bottom)))
+
+    def setLeesEdwardsDisplacement(self, D, d_per_iteration=0.0):
+        """D for the next pass; d_per_iteration != 0: hc_iterate sets D = fmod(d * iter, nx) after every step"""
+        check(self.lib.hcl_set_lees_edwards_displacement(self.ptr, float(D), float(d_per_iteration)))
+
+    def applyLeesEdwards(self):
+        """one pass on the current state (what Palabos' lattice->initialize() runs)"""
+        check(self.lib.hcl_lees_edwards_apply(self.ptr))
+
+    def leesEdwardsState(self):
+        """(D, v_top, v_bottom, d_per_iteration)"""
+        o = np.zeros(4)
+        check(self.lib.hcl_lees_edwards_state(self.ptr, dptr(o)))
+        return tuple(float(v) for v in o)
+
     def collide_part(self, part):
         check(self.lib.hcl_collide_stream_part(self.ptr, int(part)))
 
@@ -201,6 +220,31 @@ class Lattice:
         if self.ptr:
             check(self.lib.hcl_destroy(self.ptr))
             self.ptr = C.c_void_p()
+
+
+class LeesEdwardsBC:
+    """hemo::LeesEdwardsBC (helper/leesEdwardsBC.h): shear along x between the z faces of an all-periodic lattice.
+    shear_rate_lbm is param::shearrate_lbm; the displacement per iteration is shear_rate_lbm * dt, as the reference has it."""
+
+    def __init__(self, lattice, shear_rate_lbm, dt):
+        self.lattice = lattice
+        self.nx, self.ny, self.nz = lattice.nx_global, lattice.ny, lattice.nz
+        self.dt = dt
+        self.LEdisplacement = shear_rate_lbm * dt
+        v_half = (self.nz - 1) * shear_rate_lbm * 0.5
+        self.topVelocity = -v_half
+        self.bottomVelocity = v_half
+        self.LEcurrentDisplacement = 0.0
+
+    def initialize(self, schedule=True):
+        """periodicity is the lattice's (all three axes); the pass starts with D = 0.  schedule: hc_iterate advances D as
+        updateLECurDisplacement(iter) after every iteration would"""
+        self.lattice.setLeesEdwards(self.topVelocity, self.bottomVelocity)
+        self.lattice.setLeesEdwardsDisplacement(0.0, self.LEdisplacement if schedule else 0.0)
+
+    def updateLECurDisplacement(self, it):
+        self.LEcurrentDisplacement = math.fmod(self.LEdisplacement * it, float(self.nx))
+        self.lattice.setLeesEdwardsDisplacement(self.LEcurrentDisplacement, self.lattice.leesEdwardsState()[3])
 
 
 class CellType:

@@ -58,7 +58,7 @@ int hc_side_stream(void **hip_stream);  /* the side stream's hipStream_t, for a 
 int hc_set_overlap(int on);
 /* per-launch hipEvent timing of the dominant kernel (helper/profiler.h:46-77 "collideAndStream" timer) */
 int hc_profile_enable(int on);
-int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics" */
+int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics", "lees_edwards" (both kernels of the pass) */
 int hc_profile_reset(void);
 /* identifies the build of the dominant kernel: first 16 hex digits of the SHA-256 of csrc/lattice.hip (a committed PMC
  * traffic figure is only quoted next to a timing when it was measured on the same kernel) */
@@ -145,6 +145,21 @@ int hcl_set_wall_velocity(hc_lattice *L, int wall_class, const double u[3]);
 /* lattice->collideAndStream() (core/hemoCell.cpp:317), n times (fluid-only stepping).  On a slab of a multi-rank run
  * (n_slabs > 1, hc_comm_init* done) the faces are exchanged inside, interior planes colliding meanwhile. */
 int hcl_collide_stream(hc_lattice *L, int nsteps);
+/* Lees-Edwards shear boundary on the two z faces (helper/leesEdwardsBC.h).  After every step of hcl_collide_stream and
+ * hc_iterate (after hcl_step_end, before the interpolation) the top layer z = nz-1 and the bottom layer z = 0 of the
+ * post-stream state are replaced: collideExternal(rhoBar, j = (v, 0, 0)) on a copy of each node, then five populations
+ * interpolated between the nodes s1, s2 of the same layer shifted by the displacement D along x.  Needs n_slabs = 1, a
+ * lattice periodic on all three axes, nz >= 4 and fluid nodes only in the layers z = 0, 1, nz-2, nz-1 (a later hcl_set_mask
+ * that breaks this is refused).  Enabling sets D = 0 and no schedule. */
+int hcl_set_lees_edwards(hc_lattice *L, double v_top, double v_bottom);
+/* the displacement the next pass uses.  d_per_iteration != 0: hc_iterate sets D = fmod(d * (it + 1), nx) after the step that
+ * ends at iteration it + 1 (LeesEdwardsBC::updateLECurDisplacement after every HemoCell::iterate); hcl_collide_stream never
+ * changes D */
+int hcl_set_lees_edwards_displacement(hc_lattice *L, double D, double d_per_iteration);
+/* one pass on the current state (Palabos' lattice->initialize() runs the integrated processors once) */
+int hcl_lees_edwards_apply(hc_lattice *L);
+/* out = {D, v_top, v_bottom, d_per_iteration} */
+int hcl_lees_edwards_state(const hc_lattice *L, double out[4]);
 /* bring the x-halo planes of a slab up to date (width 1 or 2, see hcl_halo_doubles) through the data plane; the
  * download / statistics entry points do it by themselves */
 int hcl_slab_refresh_halos(hc_lattice *L, int width);
