@@ -1076,12 +1076,16 @@ struct CellInformationFunctionals {
     const double g = std::floor(cx + 0.5);
     return g >= (double)L->x0 && g < (double)(L->x0 + L->nxl);
   }
-  static void fill(HemoCell *h, bool vol, bool area, bool pos, bool bbox, bool stretch, bool vel = false) {
+  // complete_only: allCellInformation (helper/cellInfo.cpp:167-260) leaves a cell that lost particles out of its output
+  // ("incomplete cell detected, removing from output"); the single-property functionals skip the removed particles instead
+  // (CellPosition :82-100, CellStretch :101-118), and velocity follows them here
+  static void fill(HemoCell *h, bool vol, bool area, bool pos, bool bbox, bool stretch, bool vel = false, bool complete_only = false) {
     hc_cells *c = h->cellfields->device();
     long nvt = 0, nct = 0; hcp_counts(c, &nvt, &nct, nullptr);
     vector<long> ids((size_t)nct); if (nct) hcp_download_cell_ids(c, ids.data());
     vector<double> allpos; if (stretch) { allpos.resize(3 * (size_t)nvt); if (nvt) hcp_download(c, 0, allpos.data()); }
     vector<double> allvel; if (vel) { allvel.resize(3 * (size_t)nvt); if (nvt) hcp_download(c, 1, allvel.data()); }
+    vector<unsigned char> alive((size_t)nvt, 1); if (nvt) hc_check(hcp_download_alive(c, alive.data()), "hcp_download_alive");
     long first_cell = 0;
     for (unsigned int t = 0; t < h->cellfields->size(); t++) {
       long fv = 0, nc = 0; hcp_type_range(c, (int)t, &fv, &nc);
@@ -1090,6 +1094,10 @@ struct CellInformationFunctionals {
       hc_check(hcp_cell_info(c, (int)t, V.data(), A.data(), B.data(), P.data()), "hcp_cell_info");
       const int nv = (*h->cellfields)[t]->numVertex;
       for (long k = 0; k < nc; k++) {
+        const unsigned char *al = alive.data() + (size_t)(fv + k * nv);
+        int left = 0; for (int i = 0; i < nv; i++) left += al[i] ? 1 : 0;
+        if (complete_only && left < nv) continue;
+        if (left == 0) continue;
         if (!centre_local(h, &P[3 * (size_t)k])) continue;   // the other holder reports it
         CellInformation &ci = info()[(int)ids[(size_t)(first_cell + k)]];
         ci.cellType = t; ci.base_cell_id = ids[(size_t)(first_cell + k)]; ci.blockId = global.rank;
@@ -1099,13 +1107,17 @@ struct CellInformationFunctionals {
         if (bbox) for (int d = 0; d < 6; d++) ci.bbox[d] = B[6 * (size_t)k + d];
         if (vel) {
           const double *vv = allvel.data() + 3 * (size_t)(fv + k * nv);
-          for (int d = 0; d < 3; d++) { T sum = 0; for (int i = 0; i < nv; i++) sum += vv[3 * i + d]; ci.velocity[d] = sum / T(nv); }
+          for (int d = 0; d < 3; d++) { T sum = 0; for (int i = 0; i < nv; i++) if (al[i]) sum += vv[3 * i + d]; ci.velocity[d] = sum / T(left); }
         }
-        if (stretch) {   // helper/cellInfo.cpp:124-138: largest vertex-vertex distance
+        if (stretch) {   // helper/cellInfo.cpp:101-118: largest vertex-vertex distance, pairs with a removed particle skipped
           T mx = 0; const double *pp = allpos.data() + 3 * (size_t)(fv + k * nv);
-          for (int i = 0; i < nv - 1; i++) for (int jv = i + 1; jv < nv; jv++) {
-            const T d2 = (pp[3 * i] - pp[3 * jv]) * (pp[3 * i] - pp[3 * jv]) + (pp[3 * i + 1] - pp[3 * jv + 1]) * (pp[3 * i + 1] - pp[3 * jv + 1]) + (pp[3 * i + 2] - pp[3 * jv + 2]) * (pp[3 * i + 2] - pp[3 * jv + 2]);
-            mx = std::max(mx, d2);
+          for (int i = 0; i < nv - 1; i++) {
+            if (!al[i]) continue;
+            for (int jv = i + 1; jv < nv; jv++) {
+              if (!al[jv]) continue;
+              const T d2 = (pp[3 * i] - pp[3 * jv]) * (pp[3 * i] - pp[3 * jv]) + (pp[3 * i + 1] - pp[3 * jv + 1]) * (pp[3 * i + 1] - pp[3 * jv + 1]) + (pp[3 * i + 2] - pp[3 * jv + 2]) * (pp[3 * i + 2] - pp[3 * jv + 2]);
+              mx = std::max(mx, d2);
+            }
           }
           ci.stretch = std::sqrt(mx);
         }
@@ -1113,17 +1125,22 @@ struct CellInformationFunctionals {
       first_cell += nc;
     }
   }
-  static void calculateCellVolume(HemoCell *h) { fill(h, true, false, false, false, false); }
-  static void calculateCellArea(HemoCell *h) { fill(h, false, true, false, false, false); }
-  static void calculateCellPosition(HemoCell *h) { fill(h, false, false, true, false, false); }
-  static void calculateCellBoundingBox(HemoCell *h) { fill(h, false, false, false, true, false); }
-  static void calculateCellStretch(HemoCell *h) { fill(h, false, false, false, false, true); }
+  // the single-property functionals of the reference run syncEnvelopes and deleteIncompleteCells(false) first
+  // (helper/cellInfo.cpp:263-319): a cell that lost particles at a wall is gone before they look
+  static void prepare(HemoCell *h) { h->cellfields->deleteIncompleteCells(false); }
+  static void calculateCellVolume(HemoCell *h) { prepare(h); fill(h, true, false, false, false, false); }
+  static void calculateCellArea(HemoCell *h) { prepare(h); fill(h, false, true, false, false, false); }
+  static void calculateCellPosition(HemoCell *h) { prepare(h); fill(h, false, false, true, false, false); }
+  static void calculateCellBoundingBox(HemoCell *h) { prepare(h); fill(h, false, false, false, true, false); }
+  static void calculateCellStretch(HemoCell *h) { prepare(h); fill(h, false, false, false, false, true); }
   static void calculateCellVelocity(HemoCell *h) { fill(h, false, false, false, false, false, true); }
-  static void calculateCellAtomicBlock(HemoCell *h) { fill(h, false, false, false, false, false); }   // blockId and cellType come with every entry
-  static void calculateCellType(HemoCell *h) { fill(h, false, false, false, false, false); }
-  static void calculate_vol_pos_area(HemoCell *h) { fill(h, true, true, true, false, false); }        // helper/cellInfo.h:107: "excludes Stretch"
-  static void calculateCellInformation(HemoCell *h) { fill(h, true, true, true, true, false, true); }
-  static void calculateCellInformation(HemoCell *h, map<int, CellInformation> &out) { clear_list(); calculateCellInformation(h); out = info(); clear_list(); }   // :121
+  static void calculateCellAtomicBlock(HemoCell *h) { prepare(h); fill(h, false, false, false, false, false); }   // blockId and cellType come with every entry
+  static void calculateCellType(HemoCell *h) { prepare(h); fill(h, false, false, false, false, false); }
+  static void calculate_vol_pos_area(HemoCell *h) { prepare(h); fill(h, true, true, true, false, false); }        // helper/cellInfo.h:107: "excludes Stretch"
+  // allCellInformation (helper/cellInfo.cpp:167-260, :366-374): every value of the complete cells; the two-argument call fills
+  // stretch as the reference does, the one-argument call (the CSV writer, drivers) leaves that O(nv^2) pass out
+  static void calculateCellInformation(HemoCell *h, bool with_stretch = false) { fill(h, true, true, true, true, with_stretch, true, true); }
+  static void calculateCellInformation(HemoCell *h, map<int, CellInformation> &out) { clear_list(); calculateCellInformation(h, true); out = info(); clear_list(); }   // :366
   static void clear_list() { info().clear(); }
   // helper/cellInfo.cpp:324-365: centre-local cells of every rank, summed (HemoCellGatheringFunctional)
   static vector<double> counts_per_type(HemoCell *h) {

@@ -324,13 +324,18 @@ __global__ __launch_bounds__(256) void mechanics_kernel(MechArgs m) {
   }
 }
 
-// per-cell volume / area / bbox / centroid (helper/cellInfo.cpp:39-80,140-180)
+// per-cell volume / area / bbox / centroid (helper/cellInfo.cpp:39-80,140-180).  A cell that lost particles at a wall
+// (tag 2, "particle" deletion mode) stays listed until deleteIncompleteCells: its centroid is the mean of the particles left
+// (CellPosition, :82-100) and its bbox spans them; volume and area stay the triangle sums at the stored positions (the
+// reference has no value for an incomplete surface, allCellInformation leaves such a cell out)
 __global__ __launch_bounds__(256) void cell_info_kernel(int nv, int nt, const int *tri, const double *px, const double *py, const double *pz,
-                                                        double *volume, double *area, double *bbox, double *centroid) {
-  __shared__ double red[256][11];
+                                                        const int *tag, const unsigned char *dead, double *volume, double *area, double *bbox,
+                                                        double *centroid) {
+  __shared__ double red[256][12];
   const int tid = threadIdx.x;
   const long base = (long)blockIdx.x * nv;
-  double vol = 0, ar = 0, lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, cs[3] = {0, 0, 0};
+  const bool incomplete = tag[blockIdx.x] == 2;
+  double vol = 0, ar = 0, lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, cs[3] = {0, 0, 0}, cnt = 0;
   for (int t = tid; t < nt; t += 256) {
     const long i0 = base + tri[3 * t], i1 = base + tri[3 * t + 1], i2 = base + tri[3 * t + 2];
     const double v0x = px[i0], v0y = py[i0], v0z = pz[i0], v1x = px[i1], v1y = py[i1], v1z = pz[i1], v2x = px[i2], v2y = py[i2], v2z = pz[i2];
@@ -340,15 +345,17 @@ __global__ __launch_bounds__(256) void cell_info_kernel(int nv, int nt, const in
     ar += 0.5 * sqrt(nx * nx + ny * ny + nz * nz);
   }
   for (int i = tid; i < nv; i += 256) {
+    if (incomplete && dead[base + i]) continue;
     const double p[3] = {px[base + i], py[base + i], pz[base + i]};
     for (int d = 0; d < 3; d++) { lo[d] = fmin(lo[d], p[d]); hi[d] = fmax(hi[d], p[d]); cs[d] += p[d]; }
+    cnt += 1.0;
   }
-  red[tid][0] = vol; red[tid][1] = ar;
+  red[tid][0] = vol; red[tid][1] = ar; red[tid][11] = cnt;
   for (int d = 0; d < 3; d++) { red[tid][2 + d] = lo[d]; red[tid][5 + d] = hi[d]; red[tid][8 + d] = cs[d]; }
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if (tid < s) {
-      red[tid][0] += red[tid + s][0]; red[tid][1] += red[tid + s][1];
+      red[tid][0] += red[tid + s][0]; red[tid][1] += red[tid + s][1]; red[tid][11] += red[tid + s][11];
       for (int d = 0; d < 3; d++) {
         red[tid][2 + d] = fmin(red[tid][2 + d], red[tid + s][2 + d]);
         red[tid][5 + d] = fmax(red[tid][5 + d], red[tid + s][5 + d]);
@@ -361,7 +368,7 @@ __global__ __launch_bounds__(256) void cell_info_kernel(int nv, int nt, const in
     const long c = blockIdx.x;
     volume[c] = red[0][0] / 6.0; area[c] = red[0][1];
     // bbox order x0 x1 y0 y1 z0 z1 (helper/cellInfo.cpp:148-160)
-    for (int d = 0; d < 3; d++) { bbox[6 * c + 2 * d] = red[0][2 + d]; bbox[6 * c + 2 * d + 1] = red[0][5 + d]; centroid[3 * c + d] = red[0][8 + d] / nv; }
+    for (int d = 0; d < 3; d++) { bbox[6 * c + 2 * d] = red[0][2 + d]; bbox[6 * c + 2 * d + 1] = red[0][5 + d]; centroid[3 * c + d] = red[0][8 + d] / red[0][11]; }
   }
 }
 
@@ -477,7 +484,8 @@ int hcp_cell_info(hc_cells *C, int type, double *volume, double *area, double *b
   double *d = C->d_info;
   const long f = C->first[type];
   hipLaunchKernelGGL(cell_info_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), T.nv, T.nt, (const int *)C->types[type]->d_tri,
-                     (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f), d, d + nc, d + 2 * nc, d + 8 * nc);
+                     (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
+                     (const int *)(C->d_tag + C->cell0[type]), (const unsigned char *)(C->d_vdead + f), d, d + nc, d + 2 * nc, d + 8 * nc);
   HC_HIP(hipGetLastError());
   HC_HIP(hipMemcpyAsync(C->h_info, d, (size_t)(11 * nc) * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));

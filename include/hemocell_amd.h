@@ -421,7 +421,9 @@ int hcp_unpack_cells(hc_cells *C, int type, const int *slots, const long *cell_i
 int hcp_remove_cells(hc_cells *C, int type, const int *slots, int n);
 int hcp_owned_vertices(hc_cells *C, long *n_owned); /* vertices whose nearest node lies in this slab */
 
-/* CellInformationFunctionals (helper/cellInfo.cpp:39-80,140-180): per cell volume, area, bbox[6], centroid[3] */
+/* CellInformationFunctionals (helper/cellInfo.cpp:39-80,140-180): per cell volume, area, bbox[6], centroid[3].  For a cell that
+ * lost particles at a wall (not yet deleteIncompleteCells'd) bbox and centroid cover the particles left (CellPosition);
+ * volume and area are the triangle sums at the stored positions. */
 int hcp_cell_info(hc_cells *C, int type, double *volume, double *area, double *bbox, double *centroid);
 
 #ifdef __cplusplus

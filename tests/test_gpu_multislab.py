@@ -103,7 +103,8 @@ def _worker(rank, world, port, out, kw, steps, q):
         cid, vid, pos = r.owned_vertex_table(0)
         pcid, pvid, ppos = r.owned_vertex_table(1)
         gstats = (r.fluid_stats(0), r.vertex_stats(1), r.vertex_stats(2))    # reduced: every rank gets the global numbers
-        np.savez(os.path.join(out, "r%d.npz" % rank), f=r.populations(), cid=cid, vid=vid, pos=pos, pcid=pcid, pvid=pvid, ppos=ppos,
+        rho, u = r.lattice.rho_u()                                            # the face planes pull across the rank faces
+        np.savez(os.path.join(out, "r%d.npz" % rank), f=r.populations(), rho=rho, u=u, pi=r.lattice.pi_neq(), cid=cid, vid=vid, pos=pos, pcid=pcid, pvid=pvid, ppos=ppos,
                  held=r.cells.counts()[1], gstats=np.array(gstats), stats=np.array(list(r.slab_stats().values())),
                  deleted=r.cells.counts()[2], error=np.array(error), envelope=np.array(r.envelope()))
         slab.barrier()
@@ -132,6 +133,18 @@ def _spawn(world, tmp_path, kw, steps=STEPS, salt=0):
         z = dict(np.load(os.path.join(tmp_path, "r%d.npz" % k)))
         z["stats"] = dict(zip(names, z["stats"]))
         out.append(z)
+    return out
+
+
+def _observables_error(ref, res, nxg, fluid):
+    """rho, u and Pi_neq of the slabs put side by side against the single domain's, on the fluid nodes: the face planes evaluate
+    them from populations pulled across the rank face (hi_ok / lo_ok)"""
+    rho_r, u_r = ref.lattice.rho_u()
+    pi_r = ref.lattice.pi_neq()
+    out = []
+    for key, want, c in (("rho", rho_r, 1), ("u", u_r, 3), ("pi", pi_r, 6)):
+        got = np.concatenate([r[key].reshape(nxg // len(res), NY * NZ, c) for r in res], axis=0)
+        out.append(float(np.abs(got - want.reshape(nxg, NY * NZ, c))[fluid].max()))
     return out
 
 
@@ -189,6 +202,9 @@ def test_slabs_equal_single_domain_bit_for_bit(tmp_path, gpu, reproducible_sprea
         assert err_f <= 1e-12 and worst <= 1e-11, (err_f, worst)
     else:
         assert err_f == 0.0 and worst == 0.0, (err_f, worst)
+    if world in (2, 3):
+        err_o = _observables_error(ref, res, nxg, fluid)
+        assert max(err_o) <= (1e-12 if seam else 0.0), err_o
     assert sum(r["stats"]["cells_new"] + r["stats"]["cells_dropped"] for r in res) > 0
 
 
@@ -206,6 +222,9 @@ def test_slabs_match_single_domain(tmp_path, gpu, world, rep, padded):
     f_two = np.concatenate([r["f"].reshape(nxg // world, NY * NZ, 19) for r in res], axis=0)
     fluid = (mask.reshape(nxg, NY * NZ) == 0)
     err_f = np.abs(f_two - f_ref)[fluid].max()
+    if world in (2, 3):
+        err_o = _observables_error(ref, res, nxg, fluid)
+        assert max(err_o) <= 5e-12, err_o
     # both runs add the spread forces with fp64 atomics in whatever order the hardware takes them, so two runs of the SAME
     # configuration already differ in the last bits and drift apart over the 250 steps: seen 0.3e-12 ... 1.2e-12 from run to run
     # (populations are O(0.1); north_star asks for 1e-6).  The comparison without that noise is
