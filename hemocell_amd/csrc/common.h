@@ -104,7 +104,7 @@ struct hc_lattice {
   size_t qstride;        // doubles from population q to q+1 of the same node: npad + padding (see hcl_create)
   double *f[2];          // [19][npad] post-collision populations (fBar), ping-pong
   int cur;               // f[cur] is read by the next collide
-  double *force[3];      // [3][npad] IBM force accumulators, rotated: fcur -> (fcur+1)%3 every step
+  double *force[3];      // [npad][3] IBM force accumulators (a node's three components side by side), rotated: fcur -> (fcur+1)%3 every step
   int fcur;              // force[fcur] is the one spread adds to / collide reads; force[(fcur+2)%3] is the previous
                          // step's (what the interpolation after a collide reads, and what the NEXT collide zeroes);
                          // force[(fcur+1)%3] is already clean, so the spread of the next step may run beside this collide

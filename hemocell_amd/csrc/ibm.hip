@@ -36,9 +36,10 @@ __global__ __launch_bounds__(256) void ibm_spread_kernel(LatView v, long n, cons
     if (s.node[k] < 0) continue;
     v.dirty[s.node[k] >> 4] = v.epoch;
     // external.data[d] += (force_repulsion[d] + force[d]) * weight  (:857-859)
-    unsafeAtomicAdd(&F[s.node[k]], ((rx ? rx[i] : 0.0) + f0) * s.w[k]);
-    unsafeAtomicAdd(&F[v.npad + s.node[k]], ((ry ? ry[i] : 0.0) + f1) * s.w[k]);
-    unsafeAtomicAdd(&F[2 * v.npad + s.node[k]], ((rz ? rz[i] : 0.0) + f2) * s.w[k]);
+    double *Fn = F + 3 * s.node[k];
+    unsafeAtomicAdd(Fn, ((rx ? rx[i] : 0.0) + f0) * s.w[k]);
+    unsafeAtomicAdd(Fn + 1, ((ry ? ry[i] : 0.0) + f1) * s.w[k]);
+    unsafeAtomicAdd(Fn + 2, ((rz ? rz[i] : 0.0) + f2) * s.w[k]);
   }
 }
 
@@ -89,7 +90,8 @@ __global__ __launch_bounds__(256) void spread_gather_kernel(LatView v, long n, c
   double a0 = 0.0, a1 = 0.0, a2 = 0.0;
   for (long q = s; q < n && keys[q] == key; q++) { const int e = vals[q]; a0 += c0[e]; a1 += c1[e]; a2 += c2[e]; }
   v.dirty[key >> 4] = v.epoch;
-  F[key] += a0; F[v.npad + key] += a1; F[2 * v.npad + key] += a2;   // this thread alone touches the node
+  double *Fn = F + 3 * (long)key;
+  Fn[0] += a0; Fn[1] += a1; Fn[2] += a2;   // this thread alone touches the node
 }
 
 // ----------------------------------------------------------------------------
@@ -143,9 +145,9 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const PopView &p
     if (xg < 0) xg += v.nx_global; else if (xg >= v.nx_global) xg -= v.nx_global;
     region_force(pv.reg, xg, ly, lz, bx, by, bz);
   }
-  u[0] = jx * invRho + (bx + pv.F[node]) / 2.0;
-  u[1] = jy * invRho + (by + pv.F[v.npad + node]) / 2.0;
-  u[2] = jz * invRho + (bz + pv.F[2 * v.npad + node]) / 2.0;
+  u[0] = jx * invRho + (bx + pv.F[3 * node]) / 2.0;
+  u[1] = jy * invRho + (by + pv.F[3 * node + 1]) / 2.0;
+  u[2] = jz * invRho + (bz + pv.F[3 * node + 2]) / 2.0;
 }
 
 // node velocities of one face plane of a slab (lx = 0 or nx - 1), for the neighbour whose first halo plane it is
@@ -184,12 +186,12 @@ __global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, PopView
 // ----------------------------------------------------------------------------
 // LDS-tiled IBM kernels: one workgroup per cell.
 //
-// All 8-node stencils of a cell fall into the cell's bounding box (+1).  Spread: the workgroup
-// accumulates one force component at a time on an LDS tile of that box (ds_add_f64), then flushes only the
-// touched nodes to HBM with one fp64 atomic each, z-contiguous -- several times fewer, better shaped
-// global atomics than one per (vertex, node, component).  Interpolate: the nodes the cell touches are
-// compacted, the node velocity (19-population gather + moments) is evaluated once per node into LDS, and
-// every vertex then blends its 8 values from LDS.
+// All 8-node stencils of a cell fall into the cell's bounding box (+1); the nodes the cell touches are compacted
+// into a list (compact_nodes).  Spread: the workgroup accumulates the three force components per listed node in
+// LDS (ds_add_f64), then flushes them to HBM with one fp64 atomic per (node, component) -- several times fewer,
+// better shaped global atomics than one per (vertex, node, component).  Interpolate: the node velocity
+// (19-population gather + moments) is evaluated once per listed node into LDS, and every vertex then blends its
+// 8 values from LDS.
 constexpr int TILE_CAP = 5832;       // nodes per tile: 18 x 18 x 18, any orientation of a 642-vertex RBC; three workgroups per CU fit the 160 KB LDS
 constexpr int NODE_CAP = 1536;       // distinct nodes of one cell for the interpolation (an RBC touches ~1300)
 
@@ -399,12 +401,68 @@ __device__ __forceinline__ bool cell_prologue(const LatView &v, int nv, long bas
   return true;
 }
 
+// Compacts the nodes the cell's stencils admit: slot[tile index] = rank of the node, list[rank] = tile index, in tile order within
+// each wave's 256 tile entries (runs along z stay runs).  One LDS atomic per wave, ranks within the wave from its ballot.  Returns
+// the node count (uniform); a count above NODE_CAP means the list is incomplete and the caller takes its fallback path.
+constexpr unsigned short SLOT_FREE = 0xFFFF, SLOT_MARK = 0xFFFE;
+__device__ __forceinline__ int compact_nodes(const Tile &t, const VStencil vs[NVPT], unsigned short *slot, unsigned short *list, int *s_count) {
+  const int tid = threadIdx.x, nth = blockDim.x;
+  const int sy = t.e[2], sx = t.e[1] * t.e[2];
+  for (int i = tid; i < t.vol; i += nth) slot[i] = SLOT_FREE;
+  if (tid == 0) *s_count = 0;
+  __syncthreads();   // also: every thread is done reading the mask tile, list may overwrite it
+#pragma unroll
+  for (int j = 0; j < NVPT; j++)   // mark the admitted nodes
+#pragma unroll
+    for (int k = 0; k < 8; k++) if (vs[j].adm & (1u << k)) slot[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)] = SLOT_MARK;
+  __syncthreads();
+  for (int i0 = 0; i0 < t.vol; i0 += nth) {
+    const int i = i0 + tid;
+    const bool marked = i < t.vol && slot[i] == SLOT_MARK;
+    const unsigned long long b = __ballot(marked);
+    int first = 0;
+    if ((tid & 63) == 0 && b) first = atomicAdd(s_count, (int)__popcll(b));
+    first = __shfl(first, 0);
+    if (marked) {
+      const int n = first + (int)__popcll(b & ((1ull << (tid & 63)) - 1ull));
+      if (n < NODE_CAP) { slot[i] = (unsigned short)n; list[n] = (unsigned short)i; }
+    }
+  }
+  __syncthreads();
+  return *s_count;
+}
+
+// per-vertex spread with direct global atomics: cells larger than the tile or touching more than NODE_CAP nodes
+__device__ void spread_direct(const LatView &v, int nv, long base, const double *px, const double *py, const double *pz, const double *fx,
+                              const double *fy, const double *fz, const double *rx, const double *ry, const double *rz, double *F,
+                              const unsigned char *dead) {
+  for (int i = threadIdx.x; i < nv; i += blockDim.x) {
+    if (dead && dead[base + i]) continue;
+    Stencil s;
+    phi2_stencil(v, px[base + i], py[base + i], pz[base + i], s);
+    const double f0 = (rx ? rx[base + i] : 0.0) + fx[base + i], f1 = (ry ? ry[base + i] : 0.0) + fy[base + i], f2 = (rz ? rz[base + i] : 0.0) + fz[base + i];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      if (s.node[k] < 0) continue;
+      v.dirty[s.node[k] >> 4] = v.epoch;
+      double *Fn = F + 3 * s.node[k];
+      unsafeAtomicAdd(Fn, f0 * s.w[k]);
+      unsafeAtomicAdd(Fn + 1, f1 * s.w[k]);
+      unsafeAtomicAdd(Fn + 2, f2 * s.w[k]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv, const double *px, const double *py, const double *pz,
                                                               double *fx, double *fy, double *fz, const double *rx, const double *ry, const double *rz,
                                                               double *F, int limit_on, double f_limit, int xcd_ranges, const int *tag, const unsigned char *vdead) {
-  __shared__ double tile[TILE_CAP];
-  __shared__ unsigned char mt[TILE_CAP];
-  __shared__ int s_red[6 * MAXW], s_near;
+  // 54 KB in all, so that three workgroups share a CU: 16-bit slots, the node list reuses the mask tile, and the three force
+  // components of a touched node side by side (acc[3 * rank + component], the layout of F)
+  __shared__ unsigned short slot[TILE_CAP];
+  __shared__ __attribute__((aligned(16))) unsigned char raw[TILE_CAP > 2 * NODE_CAP ? TILE_CAP : 2 * NODE_CAP];
+  unsigned char *mt = raw; unsigned short *list = reinterpret_cast<unsigned short *>(raw);
+  __shared__ double acc[3 * NODE_CAP];
+  __shared__ int s_red[6 * MAXW], s_count, s_near;
   const int tid = threadIdx.x, nth = blockDim.x;
   PH_INIT
   const int cell = xcd_ranges ? xcd_contiguous((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
@@ -446,58 +504,39 @@ __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv,
       }
     }
   }
-  if (!tiled) {
-    // cell larger than the tile (or mesh larger than the register budget): direct global atomics
-    for (int i = tid; i < nv; i += nth) {
-      if (dead && dead[base + i]) continue;
-      Stencil s;
-      phi2_stencil(v, px[base + i], py[base + i], pz[base + i], s);
-      const double f0 = (rx ? rx[base + i] : 0.0) + fx[base + i], f1 = (ry ? ry[base + i] : 0.0) + fy[base + i], f2 = (rz ? rz[base + i] : 0.0) + fz[base + i];
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        if (s.node[k] < 0) continue;
-        v.dirty[s.node[k] >> 4] = v.epoch;
-        unsafeAtomicAdd(&F[s.node[k]], f0 * s.w[k]);
-        unsafeAtomicAdd(&F[v.npad + s.node[k]], f1 * s.w[k]);
-        unsafeAtomicAdd(&F[2 * v.npad + s.node[k]], f2 * s.w[k]);
-      }
-    }
-    return;
-  }
-  // One force component at a time on the LDS tile (ds_add_f64), then one fp64 atomic to HBM per touched node.  (All three
-  // components in one pass over compacted per-node accumulators -- the interpolation's node list -- halves a workgroup's
-  // own time and LOSES 11-16 % of the kernel's: the atomics then leave in one burst, and it is their rate at the memory side
-  // that bounds the kernel)
-  const int sy = t.e[2], sx = t.e[1] * t.e[2];
-  for (int i = tid; i < t.vol; i += nth) tile[i] = 0.0;   // once: the flush below leaves the tile zeroed for the next component
-  __syncthreads();
+  // The touched nodes are compacted and all three components accumulated per node in LDS (ds_add_f64), then flushed with one
+  // fp64 atomic per (node, component), consecutive lanes on consecutive addresses: a z-run of a membrane across a row leaves as
+  // one 48-96 byte segment of F instead of three 16-32 byte segments in three component planes.
+  const int n = tiled ? compact_nodes(t, vs, slot, list, &s_count) : 0;
   STAMP(5);
+  if (!tiled || n > NODE_CAP) { spread_direct(v, nv, base, px, py, pz, fx, fy, fz, rx, ry, rz, F, dead); return; }   // uniform
+  const int sy = t.e[2], sx = t.e[1] * t.e[2];
+  for (int k = tid; k < 3 * n; k += nth) acc[k] = 0.0;
+  __syncthreads();
 #pragma unroll
-  for (int comp = 0; comp < 3; comp++) {
-    const double *rc = comp == 0 ? rx : comp == 1 ? ry : rz;
-    double *Fc = F + (long)comp * v.npad;
+  for (int j = 0; j < NVPT; j++) {
+    const int i = tid + j * nth;
+    if (i >= nv || !vs[j].adm) continue;
+    double fv[3];   // force_repulsion + force, :857-859
+    fv[0] = (rx ? rx[base + i] : 0.0) + f[j][0]; fv[1] = (ry ? ry[base + i] : 0.0) + f[j][1]; fv[2] = (rz ? rz[base + i] : 0.0) + f[j][2];
 #pragma unroll
-    for (int j = 0; j < NVPT; j++) {
-      const int i = tid + j * nth;
-      if (i >= nv || !vs[j].adm) continue;
-      const double fv = (rc ? rc[base + i] : 0.0) + f[j][comp];   // force_repulsion + force, :857-859
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if (vs[j].adm & (1u << k)) atomicAdd(&tile[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)], fv * vs[j].w[k]);
+    for (int k = 0; k < 8; k++) {
+      if (!(vs[j].adm & (1u << k))) continue;
+      double *a = &acc[3 * slot[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)]];
+      atomicAdd(a, fv[0] * vs[j].w[k]); atomicAdd(a + 1, fv[1] * vs[j].w[k]); atomicAdd(a + 2, fv[2] * vs[j].w[k]);
     }
-    __syncthreads();
-    STAMP(6 + 2 * comp);
-    for (int i = tid; i < t.vol; i += nth) {
-      const double val = tile[i];
-      if (val != 0.0) {
-        if (comp < 2) tile[i] = 0.0;
-        int lx, ly, lz; const long node = tile_node(v, t, i, lx, ly, lz); v.dirty[node >> 4] = v.epoch;
-        unsafeAtomicAdd(&Fc[node], val);
-      }
-    }
-    if (comp < 2) __syncthreads();
-    STAMP(7 + 2 * comp);
   }
+  __syncthreads();
+  STAMP(6);
+  for (int k = tid; k < 3 * n; k += nth) {
+    const double val = acc[k];
+    if (val != 0.0) {
+      const int q = k / 3;
+      int lx, ly, lz; const long node = tile_node(v, t, list[q], lx, ly, lz); v.dirty[node >> 4] = v.epoch;
+      unsafeAtomicAdd(&F[3 * node + (k - 3 * q)], val);
+    }
+  }
+  STAMP(7);
 }
 
 __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, PopView pv, int nv, const double *px, const double *py,
@@ -505,7 +544,6 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
                                                                    const int *tag, const unsigned char *vdead) {
   // 54 KB in all, so that three workgroups share a CU: 16-bit slots, and the node list reuses the mask tile
   // (the mask is only read while the stencils are formed)
-  constexpr unsigned short FREE = 0xFFFF, MARK = 0xFFFE;
   __shared__ unsigned short slot[TILE_CAP];
   __shared__ __attribute__((aligned(16))) unsigned char raw[TILE_CAP > 2 * NODE_CAP ? TILE_CAP : 2 * NODE_CAP];
   unsigned char *mt = raw; unsigned short *list = reinterpret_cast<unsigned short *>(raw);
@@ -522,29 +560,8 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
   bool tiled = cell_prologue(v, nv, base, px, py, pz, dead, s_red, &s_near, mt, t, vs PH_ARG);
   const int sy = t.e[2], sx = t.e[1] * t.e[2];
   if (tiled) {
-    for (int i = tid; i < t.vol; i += nth) slot[i] = FREE;
-    if (tid == 0) s_count = 0;
-    __syncthreads();   // also: every thread is done reading mt, list may overwrite it
-#pragma unroll
-    for (int j = 0; j < NVPT; j++)   // mark the admitted nodes
-#pragma unroll
-      for (int k = 0; k < 8; k++) if (vs[j].adm & (1u << k)) slot[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)] = MARK;
-    __syncthreads();
-    for (int i0 = 0; i0 < t.vol; i0 += nth) {   // compact: one LDS atomic per wave, ranks within the wave from its ballot
-      const int i = i0 + tid;
-      const bool marked = i < t.vol && slot[i] == MARK;
-      const unsigned long long b = __ballot(marked);
-      int first = 0;
-      if ((tid & 63) == 0 && b) first = atomicAdd(&s_count, (int)__popcll(b));
-      first = __shfl(first, 0);
-      if (marked) {
-        const int n = first + (int)__popcll(b & ((1ull << (tid & 63)) - 1ull));
-        if (n < NODE_CAP) { slot[i] = (unsigned short)n; list[n] = (unsigned short)i; }
-      }
-    }
-    __syncthreads();
+    if (compact_nodes(t, vs, slot, list, &s_count) > NODE_CAP) tiled = false;   // uniform: s_count is shared
     STAMP(12);
-    if (s_count > NODE_CAP) tiled = false;   // uniform: s_count is shared
   }
   if (tiled) {
     const int n = s_count;

@@ -29,8 +29,8 @@ namespace {
 struct LatArgs {
   const double *fin;
   double *fout;
-  const double *Fin;   // IBM force to read   [3][npad]
-  double *Fzero;       // IBM force to zero   [3][npad]
+  const double *Fin;   // IBM force to read   [npad][3]
+  double *Fzero;       // IBM force to zero   [npad][3]
   const uint8_t *mask;
   int nx, ny, nz;
   int plane;             // nodes of one x-plane
@@ -192,6 +192,12 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(LatArgs a) {
   const uint8_t m = a.mask[node];
   if (m == 2) return;   // solid node with no fluid neighbour: inert under full-way bounce-back
   const Nbr n = neighbours(a, x, y, z);
+  // the node's IBM force record (24 B) is loaded together with the populations, in one round trip.  This also keeps the
+  // kernel at 98 VGPRs, 4 waves per SIMD: loaded after the pull it compiles to 94 VGPRs and 5 waves, and the spread's
+  // waves beside it then wait for two collide waves to retire (spread 0.72 instead of 0.33 ms)
+  const bool fdirty = a.ibm && m == 0 && a.dirty_in[node >> 4] == a.epoch_in;
+  double F0 = 0.0, F1 = 0.0, F2 = 0.0;
+  if (fdirty) { F0 = a.Fin[3 * node]; F1 = a.Fin[3 * node + 1]; F2 = a.Fin[3 * node + 2]; }
   double f[HC_Q];
   pull(a.fin, a.qs, node, n, f);
   const bool wall = m != 0;
@@ -216,8 +222,8 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(LatArgs a) {
     double bx = a.bx, by = a.by, bz = a.bz;
     if (REGIONS) region_force(a.reg, a.x0 + x, y, z, bx, by, bz);
     double Fx = bx, Fy = by, Fz = bz;
-    if (a.ibm && a.dirty_in[node >> 4] == a.epoch_in) {   // x + 0.0 == x, so skipping untouched groups changes no bits
-      Fx = bx + a.Fin[node]; Fy = by + a.Fin[a.npad + node]; Fz = bz + a.Fin[2 * a.npad + node];
+    if (fdirty) {   // x + 0.0 == x, so skipping untouched groups changes no bits
+      Fx = bx + F0; Fy = by + F1; Fz = bz + F2;
     }
     collide_guo(f, Fx, Fy, Fz, a.omega);
   }
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(LatArgs a) {
   // streamed once and read again only after 5 GB of other traffic: non-temporal stores keep the lines out of the way
   // of the loads (measured: -3 % kernel time on the pipe and on the all-fluid box; non-temporal loads cost 4 %)
   for (int q = 0; q < HC_Q; q++) __builtin_nontemporal_store(f[q], &a.fout[(long)q * a.qs + node]);
-  if (a.ibm && a.dirty_zero[node >> 4] == a.epoch_zero) { a.Fzero[node] = 0.0; a.Fzero[a.npad + node] = 0.0; a.Fzero[2 * a.npad + node] = 0.0; }
+  if (a.ibm && a.dirty_zero[node >> 4] == a.epoch_zero) { a.Fzero[3 * node] = 0.0; a.Fzero[3 * node + 1] = 0.0; a.Fzero[3 * node + 2] = 0.0; }
 }
 
 // P(y,i) = mask[y+c_i] ? 0 : feq_i(rho,u): initializeAtEquilibrium in the shifted representation
@@ -306,9 +312,9 @@ __global__ void rho_u_kernel(LatArgs a, double *rho, double *u) {
   rho[o] = 1.0 + rhoBar;
   double bx, by, bz;
   body_at(a, x, y, z, bx, by, bz);
-  u[3 * o] = j0 * invRho + (bx + a.Fin[node]) / 2.0;
-  u[3 * o + 1] = j1 * invRho + (by + a.Fin[a.npad + node]) / 2.0;
-  u[3 * o + 2] = j2 * invRho + (bz + a.Fin[2 * a.npad + node]) / 2.0;
+  u[3 * o] = j0 * invRho + (bx + a.Fin[3 * node]) / 2.0;
+  u[3 * o + 1] = j1 * invRho + (by + a.Fin[3 * node + 1]) / 2.0;
+  u[3 * o + 2] = j2 * invRho + (bz + a.Fin[3 * node + 2]) / 2.0;
 }
 
 // Off-equilibrium part of the momentum-flux tensor, as Palabos' momentTemplates::compute_rhoBar_j_PiNeq forms it from the
@@ -352,7 +358,7 @@ __global__ void force_aos_kernel(LatArgs a, double *F) {
   const int x = a.x_begin + blockIdx.y;
   const long node = (long)(x + HALO) * a.xs + p;
   const long o = (long)x * a.plane + p;
-  for (int d = 0; d < 3; d++) F[3 * o + d] = a.Fin[d * a.npad + node];
+  for (int d = 0; d < 3; d++) F[3 * o + d] = a.Fin[3 * node + d];
 }
 
 // FluidInfo statistics (helper/fluidInfo.cpp:33-96): magnitude of Cell::computeVelocity (what 0) or of the external
@@ -375,7 +381,7 @@ __global__ __launch_bounds__(256) void fluid_stats_kernel(LatArgs a, int what, d
     double bx, by, bz;
     body_at(a, x, y, z, bx, by, bz);
     double Fx = bx, Fy = by, Fz = bz;
-    if (a.ibm) { Fx = bx + a.Fin[node]; Fy = by + a.Fin[a.npad + node]; Fz = bz + a.Fin[2 * a.npad + node]; }
+    if (a.ibm) { Fx = bx + a.Fin[3 * node]; Fy = by + a.Fin[3 * node + 1]; Fz = bz + a.Fin[3 * node + 2]; }
     double v0 = Fx, v1 = Fy, v2 = Fz;
     if (what == 0) {
       const Nbr n = neighbours(a, x, y, z);
@@ -497,13 +503,13 @@ __global__ void halo_copy_kernel(HaloArgs h) {
   if (h.to_buf) *b = h.f[li]; else h.f[li] = *b;
 }
 
-// clears the 2*HALO halo planes of the three IBM force components
-__global__ void zero_force_halo_kernel(double *F, long npad, long xs, int plane, int nx) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= plane) return;
-  const int comp = blockIdx.y / (2 * HALO), w = blockIdx.y % (2 * HALO);
+// clears the 2*HALO halo planes of the IBM force (3 doubles per node)
+__global__ void zero_force_halo_kernel(double *F, long xs, int plane, int nx) {
+  const int e = blockIdx.x * 256 + threadIdx.x;   // (node of the plane, component)
+  if (e >= 3 * plane) return;
+  const int w = blockIdx.y;
   const int xp = w < HALO ? w : nx + w;   // padded plane index: 0..HALO-1 and nx+HALO..nx+2*HALO-1
-  F[(long)comp * npad + (long)xp * xs + p] = 0.0;
+  F[3 * (long)xp * xs + e] = 0.0;
 }
 
 LatArgs make_args(const hc_lattice *L) {
@@ -858,8 +864,8 @@ int hcl_collide_stream_part(hc_lattice *L, int part) {
 int hcl_zero_force_halos(hc_lattice *L) {
   HC_REQUIRE(L, "hcl_zero_force_halos: null lattice");
   if (L->n_slabs <= 1 || !L->ibm) return HC_OK;
-  hipLaunchKernelGGL(zero_force_halo_kernel, dim3((unsigned)((L->plane + 255) / 256), (unsigned)(2 * HALO * 3), 1), dim3(256), 0, hc::stream(),
-                     L->force[(L->fcur + 2) % 3], (long)L->npad, (long)L->xs, (int)L->plane, L->nx);
+  hipLaunchKernelGGL(zero_force_halo_kernel, dim3((unsigned)((3 * L->plane + 255) / 256), (unsigned)(2 * HALO), 1), dim3(256), 0, hc::stream(),
+                     L->force[(L->fcur + 2) % 3], (long)L->xs, (int)L->plane, L->nx);
   HC_HIP(hipGetLastError());
   return HC_OK;
 }
