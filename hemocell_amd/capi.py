@@ -95,6 +95,14 @@ SIGNATURES = {
     "hcl_set_lees_edwards_displacement": (C.c_int, [VP, C.c_double, C.c_double]),
     "hcl_lees_edwards_apply": (C.c_int, [VP]),
     "hcl_lees_edwards_state": (C.c_int, [VP, c_double_p]),
+    "hcl_open_boundary_add": (C.c_int, [VP, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p]),
+    "hcl_open_boundary_add_box": (C.c_int, [VP, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p]),
+    "hcl_open_boundary_clear": (C.c_int, [VP]),
+    "hcl_open_boundary_slots": (C.c_int, [VP, c_int_p, C.c_int, c_int_p]),
+    "hcl_open_boundary_set_velocity": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int]),
+    "hcl_open_boundary_set_density": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int]),
+    "hcl_open_boundary_values": (C.c_int, [VP, C.c_int, C.c_int, c_double_p]),
+    "hcl_plane_velocity": (C.c_int, [VP, C.c_int, c_int_p, C.c_int, VP, C.c_int]),
     "hcl_collide_stream_part": (C.c_int, [VP, C.c_int]),
     "hcl_step_end": (C.c_int, [VP]),
     "hcl_download_populations": (C.c_int, [VP, c_double_p]),

@@ -139,6 +139,14 @@ struct hc_lattice {
   bool le_on = false;
   double le_D = 0.0, le_d = 0.0, le_v_top = 0.0, le_v_bottom = 0.0;
   double *le_buf = nullptr;   // [2][19][nx ny] post-pass values of the top and bottom layers
+  // Zou-He open boundaries, normal x (hcl_open_boundary_add): ob_code[node] = -1 for every other node, else slot << 2 | kind
+  // (HC_OB_*); ob_val[slot] = {u_x, u_y, u_z, rho}.  The collide runs its open-boundary instantiation while ob_n > 0.
+  int *ob_code = nullptr;           // [npad], device
+  std::vector<int> ob_hcode;        // host copy
+  double *ob_val = nullptr;         // [ob_cap][4], device
+  int ob_n = 0, ob_cap = 0;
+  int *ob_list = nullptr; int ob_list_cap = 0;   // staging of hcl_plane_velocity's node list
+  double *ob_out = nullptr; int ob_out_cap = 0;  // ... and of its output when the caller's buffer is on the host
 };
 
 namespace hc {

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "comm.h"
 #include <algorithm>
+#include <type_traits>
 
 using namespace hc;
 
@@ -49,6 +50,12 @@ struct LatArgs {
   double wall_u[4][3];   // moving-wall classes 3..6
   int x0, nx_global;     // global x of plane 0 (body-force regions are given in global coordinates)
   BodyRegions reg;
+};
+
+// the arguments of the open-boundary instantiation: the other instantiations keep LatArgs, and with it their kernel-argument block
+struct OpenArgs : LatArgs {
+  const int *ob_code;    // Zou-He open boundaries: -1 or slot << 2 | kind
+  const double *ob_val;  // [slot][4] {u_x, u_y, u_z, rho}
 };
 
 // uniform body force, or that of the last region holding the node
@@ -175,8 +182,53 @@ __device__ __forceinline__ void collide_guo(double f[HC_Q], double Fx, double Fy
 #undef M
 }
 
-template <bool REGIONS>
-__global__ __launch_bounds__(256) void collide_stream_kernel(LatArgs a) {
+// Zou-He completion with normal x on the gathered populations f (stored form f - t_q; the opposite populations of a pair share
+// t_q, so the completed ones are formed in that form directly).  code & 3: 0 = velocity 0N, 1 = velocity 0P, 2 = pressure 0N,
+// 3 = pressure 0P.  0N completes the five populations with c_x = +1 from their opposites:
+//   rho = (S_0 + 2 S_-) / (1 - u_x) with the real sums S (the t_q of the nine c_x = 0 and twice the five c_x = -1 ones add 1),
+//   f(1,0,0) = f(-1,0,0) + rho u_x / 3,  f(1,+-1,0) = f(-1,-+1,0) + rho (u_x +- u_y) / 6 -+ N_y,  likewise z,
+//   N_y = (sum f over c = (0,1,.) - sum over (0,-1,.)) / 2 - rho u_y / 3;
+// 0P mirrors it.  Pressure nodes take rho and u_x = 1 - (S_0 + 2 S_-) / rho (0N), (S_0 + 2 S_+) / rho - 1 (0P), u_y = u_z = 0.
+// tests/open_boundary_ref.py restates this operation for operation.
+__device__ __forceinline__ void zou_he_x(double f[HC_Q], int code, const double *__restrict__ val) {
+  const int kind = code & 3;
+  const long slot = code >> 2;
+  const double s0 = f[0] + f[2] + f[3] + f[8] + f[9] + f[11] + f[12] + f[17] + f[18];
+  const double sm = f[1] + f[4] + f[5] + f[6] + f[7];
+  const double sp = f[10] + f[13] + f[14] + f[15] + f[16];
+  const bool neg = (kind & 1) == 0;   // 0N
+  const double s_out = neg ? sm : sp;
+  const double known = s0 + 2.0 * s_out + 1.0;
+  double rho, ux, uy, uz;
+  if (kind < 2) {
+    ux = val[4 * slot]; uy = val[4 * slot + 1]; uz = val[4 * slot + 2];
+    rho = neg ? known / (1.0 - ux) : known / (1.0 + ux);
+  } else {
+    rho = val[4 * slot + 3];
+    ux = neg ? 1.0 - known / rho : known / rho - 1.0;
+    uy = 0.0; uz = 0.0;
+  }
+  const double ny = 0.5 * ((f[11] + f[17] + f[18]) - (f[2] + f[8] + f[9])) - rho * uy / 3.0;
+  const double nz = 0.5 * ((f[12] + f[9] + f[17]) - (f[3] + f[8] + f[18])) - rho * uz / 3.0;
+  if (neg) {
+    f[10] = f[1] + rho * ux / 3.0;
+    f[13] = f[4] + rho * (ux + uy) / 6.0 - ny;
+    f[14] = f[5] + rho * (ux - uy) / 6.0 + ny;
+    f[15] = f[6] + rho * (ux + uz) / 6.0 - nz;
+    f[16] = f[7] + rho * (ux - uz) / 6.0 + nz;
+  } else {
+    f[1] = f[10] - rho * ux / 3.0;
+    f[4] = f[13] - rho * (ux + uy) / 6.0 + ny;
+    f[5] = f[14] - rho * (ux - uy) / 6.0 - ny;
+    f[6] = f[15] - rho * (ux + uz) / 6.0 + nz;
+    f[7] = f[16] - rho * (ux - uz) / 6.0 - nz;
+  }
+}
+
+// OPEN: the instantiation for lattices with Zou-He nodes (launch_collide picks it while ob_n > 0); the other instantiations
+// compile to the same code as before it existed
+template <bool REGIONS, bool OPEN = false>
+__global__ __launch_bounds__(256) void collide_stream_kernel(std::conditional_t<OPEN, OpenArgs, LatArgs> a) {
   // thread -> (y,z) through the active-span map of this plane: consecutive threads walk the spans of
   // consecutive rows, so every lane of every wave (except the last of a plane) has a live node
   const int x = a.x_begin + (int)blockIdx.y + ((int)blockIdx.y >= a.x_split ? a.x_jump : 0);
@@ -224,6 +276,10 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(LatArgs a) {
     double Fx = bx, Fy = by, Fz = bz;
     if (fdirty) {   // x + 0.0 == x, so skipping untouched groups changes no bits
       Fx = bx + F0; Fy = by + F1; Fz = bz + F2;
+    }
+    if constexpr (OPEN) {
+      const int code = a.ob_code[node];
+      if (code >= 0) zou_he_x(f, code, a.ob_val);
     }
     collide_guo(f, Fx, Fy, Fz, a.omega);
   }
@@ -350,6 +406,36 @@ __global__ void pi_neq_kernel(LatArgs a, double *pi) {
   pi[o + 3] = yy - invRho * j1 * j1 - cs2 * rhoBar;
   pi[o + 4] = yz - invRho * j1 * j2;
   pi[o + 5] = zz - invRho * j2 * j2 - cs2 * rhoBar;
+}
+
+// Cell::computeVelocity on listed nodes of one plane with the body force alone (hcl_plane_velocity); out [n][3]
+__global__ void plane_velocity_kernel(LatArgs a, int x, const int *yz, int n, double *out) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int p = yz[k];
+  const int y = p / a.nz, z = p - y * a.nz;
+  const long node = (long)(x + HALO) * a.xs + p;
+  double u0 = 0.0, u1 = 0.0, u2 = 0.0;
+  if (a.mask[node] == 0) {
+    const Nbr nb = neighbours(a, x, y, z);
+    double f[HC_Q];
+    pull(a.fin, a.qs, node, nb, f);
+    double rhoBar, j0, j1, j2;
+    moments(f, rhoBar, j0, j1, j2);
+    const double invRho = 1.0 / (1.0 + rhoBar);
+    double bx, by, bz;
+    body_at(a, x, y, z, bx, by, bz);
+    u0 = j0 * invRho + bx / 2.0; u1 = j1 * invRho + by / 2.0; u2 = j2 * invRho + bz / 2.0;
+  }
+  out[3L * k] = u0; out[3L * k + 1] = u1; out[3L * k + 2] = u2;
+}
+
+// ob_val[first + i][c0 .. c0 + nc - 1] = src[i][0 .. nc - 1]
+__global__ void ob_set_kernel(double *val, int first, int n, const double *src, int c0, int nc) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n * nc) return;
+  const int i = k / nc, c = k - i * nc;
+  val[4L * (first + i) + c0 + c] = src[k];
 }
 
 __global__ void force_aos_kernel(LatArgs a, double *F) {
@@ -616,8 +702,15 @@ int launch_collide(hc_lattice *L, int x_begin, int nplanes, int x2 = 0, int n2 =
   a.x_begin = x_begin;
   if (n2 > 0) { a.x_split = nplanes; a.x_jump = x2 - (x_begin + nplanes); }
   const unsigned ny = (unsigned)(nplanes + n2);
-  if (L->regions.n) hipLaunchKernelGGL(collide_stream_kernel<true>, dim3((unsigned)((L->max_active + 255) / 256), ny, 1), dim3(256), 0, hc::stream(), a);
-  else hipLaunchKernelGGL(collide_stream_kernel<false>, dim3((unsigned)((L->max_active + 255) / 256), ny, 1), dim3(256), 0, hc::stream(), a);
+  const dim3 grid((unsigned)((L->max_active + 255) / 256), ny, 1);
+  if (L->ob_n > 0) {
+    OpenArgs o;
+    static_cast<LatArgs &>(o) = a;
+    o.ob_code = L->ob_code; o.ob_val = L->ob_val;
+    if (L->regions.n) hipLaunchKernelGGL((collide_stream_kernel<true, true>), grid, dim3(256), 0, hc::stream(), o);
+    else hipLaunchKernelGGL((collide_stream_kernel<false, true>), grid, dim3(256), 0, hc::stream(), o);
+  } else if (L->regions.n) hipLaunchKernelGGL(collide_stream_kernel<true>, grid, dim3(256), 0, hc::stream(), a);
+  else hipLaunchKernelGGL(collide_stream_kernel<false>, grid, dim3(256), 0, hc::stream(), a);
   HC_HIP(hipGetLastError());
   return HC_OK;
 }
@@ -729,6 +822,10 @@ int hcl_destroy(hc_lattice *L) {
   if (L->blk_row) hipFree(L->blk_row);
   if (L->wallbrick) hipFree(L->wallbrick);
   if (L->le_buf) hipFree(L->le_buf);
+  if (L->ob_code) hipFree(L->ob_code);
+  if (L->ob_val) hipFree(L->ob_val);
+  if (L->ob_list) hipFree(L->ob_list);
+  if (L->ob_out) hipFree(L->ob_out);
   delete L;
   return HC_OK;
 }
@@ -921,6 +1018,157 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]) {
   HC_REQUIRE(L && out, "hcl_lees_edwards_state: null pointer");
   if (!L->le_on) { hc::set_error("hcl_lees_edwards_state: no Lees-Edwards boundary (hcl_set_lees_edwards)"); return HC_ERR_STATE; }
   out[0] = L->le_D; out[1] = L->le_v_top; out[2] = L->le_v_bottom; out[3] = L->le_d;
+  return HC_OK;
+}
+
+// ---- Zou-He open boundaries (the completion is zou_he_x inside the collide)
+// room for `need` slots; the slots from ob_n on start at u = 0, rho = 1
+static int ob_grow(hc_lattice *L, int need) {
+  if (need <= L->ob_cap) {
+    if (need > L->ob_n) {
+      std::vector<double> init((size_t)(need - L->ob_n) * 4, 0.0);
+      for (size_t i = 0; i < init.size(); i += 4) init[i + 3] = 1.0;
+      HC_HIP(hipMemcpyAsync(L->ob_val + (size_t)L->ob_n * 4, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
+      HC_HIP(hipStreamSynchronize(hc::stream()));
+    }
+    return HC_OK;
+  }
+  int cap = std::max(need, 2 * L->ob_cap);
+  double *v = nullptr;
+  HC_HIP(hipMalloc((void **)&v, (size_t)cap * 4 * sizeof(double)));
+  std::vector<double> init((size_t)(cap - L->ob_n) * 4, 0.0);
+  for (size_t i = 0; i < init.size(); i += 4) init[i + 3] = 1.0;   // u = 0, rho = 1
+  if (L->ob_val && L->ob_n) HC_HIP(hipMemcpyAsync(v, L->ob_val, (size_t)L->ob_n * 4 * sizeof(double), hipMemcpyDeviceToDevice, hc::stream()));
+  HC_HIP(hipMemcpyAsync(v + (size_t)L->ob_n * 4, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  if (L->ob_val) HC_HIP(hipFree(L->ob_val));
+  L->ob_val = v; L->ob_cap = cap;
+  return HC_OK;
+}
+
+static int ob_stage(void **buf, int *cap, size_t elem, int n) {
+  if (n <= *cap) return HC_OK;
+  if (*buf) HC_HIP(hipFree(*buf));
+  *buf = nullptr; *cap = 0;
+  HC_HIP(hipMalloc(buf, (size_t)n * elem));
+  *cap = n;
+  return HC_OK;
+}
+
+static int ob_set(hc_lattice *L, const char *what, int first, int n, const double *src, int c0, int nc, int on_device) {
+  if (!L || (n > 0 && !src)) { hc::set_error(std::string(what) + ": null pointer"); return HC_ERR_ARG; }
+  if (first < 0 || n < 0 || first + n > L->ob_n) { hc::set_error(std::string(what) + ": slots out of range"); return HC_ERR_ARG; }
+  if (n == 0) return HC_OK;
+  const double *d = src;
+  if (!on_device) {
+    int rc = ensure_scratch(L, (size_t)n * nc); if (rc != HC_OK) return rc;
+    HC_HIP(hipMemcpyAsync(L->scratch, src, (size_t)n * nc * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
+    d = L->scratch;
+  }
+  hipLaunchKernelGGL(ob_set_kernel, dim3((unsigned)((n * nc + 255) / 256)), dim3(256), 0, hc::stream(), L->ob_val, first, n, d, c0, nc);
+  HC_HIP(hipGetLastError());
+  if (!on_device) HC_HIP(hipStreamSynchronize(hc::stream()));   // the host buffer may go away after the call
+  return HC_OK;
+}
+
+int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot) {
+  HC_REQUIRE(L && (n == 0 || nodes), "hcl_open_boundary_add: null pointer");
+  HC_REQUIRE(L->n_slabs == 1, "hcl_open_boundary_add: open boundaries need the whole domain on one GPU (n_slabs = 1)");
+  HC_REQUIRE(kind == HC_OB_VELOCITY || kind == HC_OB_PRESSURE, "hcl_open_boundary_add: kind must be HC_OB_VELOCITY or HC_OB_PRESSURE");
+  HC_REQUIRE(orientation == -1 || orientation == 1, "hcl_open_boundary_add: orientation must be -1 (0N) or +1 (0P)");
+  HC_REQUIRE(n >= 0 && (long)L->ob_n + n < (1L << 28), "hcl_open_boundary_add: too many nodes");
+  for (int i = 0; i < n; i++) {
+    const int *c = nodes + 3 * i;
+    HC_REQUIRE(c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz, "hcl_open_boundary_add: node outside the lattice");
+  }
+  if (first_slot) *first_slot = L->ob_n;
+  if (n == 0) return HC_OK;
+  int rc = ob_grow(L, L->ob_n + n); if (rc != HC_OK) return rc;
+  if (!L->ob_code) {
+    HC_HIP(hipMalloc((void **)&L->ob_code, L->npad * sizeof(int)));
+    L->ob_hcode.assign(L->npad, -1);
+  }
+  const int k = (kind == HC_OB_PRESSURE ? 2 : 0) + (orientation > 0 ? 1 : 0);
+  for (int i = 0; i < n; i++) {
+    const int *c = nodes + 3 * i;
+    L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]] = ((L->ob_n + i) << 2) | k;
+  }
+  L->ob_n += n;
+  HC_HIP(hipMemcpyAsync(L->ob_code, L->ob_hcode.data(), L->npad * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  return HC_OK;
+}
+
+int hcl_open_boundary_add_box(hc_lattice *L, int kind, int orientation, const int box[6], int *first_slot, int *n_nodes) {
+  HC_REQUIRE(L && box, "hcl_open_boundary_add_box: null pointer");
+  HC_REQUIRE(box[0] <= box[1] && box[2] <= box[3] && box[4] <= box[5], "hcl_open_boundary_add_box: empty box");
+  std::vector<int> nodes;
+  for (int x = box[0]; x <= box[1]; x++)
+    for (int y = box[2]; y <= box[3]; y++)
+      for (int z = box[4]; z <= box[5]; z++) { nodes.push_back(x); nodes.push_back(y); nodes.push_back(z); }
+  const int n = (int)(nodes.size() / 3);
+  const int rc = hcl_open_boundary_add(L, kind, orientation, nodes.data(), n, first_slot);
+  if (rc == HC_OK && n_nodes) *n_nodes = n;
+  return rc;
+}
+
+int hcl_open_boundary_clear(hc_lattice *L) {
+  HC_REQUIRE(L, "hcl_open_boundary_clear: null lattice");
+  if (L->ob_code) {
+    std::fill(L->ob_hcode.begin(), L->ob_hcode.end(), -1);
+    HC_HIP(hipMemcpyAsync(L->ob_code, L->ob_hcode.data(), L->npad * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
+    HC_HIP(hipStreamSynchronize(hc::stream()));
+  }
+  L->ob_n = 0;
+  return HC_OK;
+}
+
+int hcl_open_boundary_slots(const hc_lattice *L, const int *nodes, int n, int *slots) {
+  HC_REQUIRE(L && n >= 0 && (n == 0 || (nodes && slots)), "hcl_open_boundary_slots: bad arguments");
+  for (int i = 0; i < n; i++) {
+    const int *c = nodes + 3 * i;
+    int s = -1;
+    if (L->ob_code && c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz) {
+      const int code = L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]];
+      s = code < 0 ? -1 : code >> 2;
+    }
+    slots[i] = s;
+  }
+  return HC_OK;
+}
+
+int hcl_open_boundary_set_velocity(hc_lattice *L, int first_slot, int n, const double *u, int on_device) {
+  return ob_set(L, "hcl_open_boundary_set_velocity", first_slot, n, u, 0, 3, on_device);
+}
+
+int hcl_open_boundary_set_density(hc_lattice *L, int first_slot, int n, const double *rho, int on_device) {
+  return ob_set(L, "hcl_open_boundary_set_density", first_slot, n, rho, 3, 1, on_device);
+}
+
+int hcl_open_boundary_values(hc_lattice *L, int first_slot, int n, double *out) {
+  HC_REQUIRE(L && (n == 0 || out), "hcl_open_boundary_values: null pointer");
+  HC_REQUIRE(first_slot >= 0 && n >= 0 && first_slot + n <= L->ob_n, "hcl_open_boundary_values: slots out of range");
+  if (n == 0) return HC_OK;
+  HC_HIP(hipMemcpyAsync(out, L->ob_val + 4L * first_slot, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  return HC_OK;
+}
+
+int hcl_plane_velocity(hc_lattice *L, int x, const int *yz, int n, double *out, int on_device) {
+  HC_REQUIRE(L && n >= 0 && (n == 0 || (yz && out)), "hcl_plane_velocity: bad arguments");
+  HC_REQUIRE(x >= 0 && x < L->nx, "hcl_plane_velocity: plane outside the lattice");
+  HC_REQUIRE(L->n_slabs == 1, "hcl_plane_velocity: needs n_slabs = 1");
+  for (int i = 0; i < n; i++) HC_REQUIRE(yz[i] >= 0 && (size_t)yz[i] < L->plane, "hcl_plane_velocity: in-plane index out of range");
+  if (n == 0) return HC_OK;
+  int rc = ob_stage((void **)&L->ob_list, &L->ob_list_cap, sizeof(int), n); if (rc != HC_OK) return rc;
+  HC_HIP(hipMemcpyAsync(L->ob_list, yz, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
+  double *d = out;
+  if (!on_device) { rc = ob_stage((void **)&L->ob_out, &L->ob_out_cap, 3 * sizeof(double), n); if (rc != HC_OK) return rc; d = L->ob_out; }
+  LatArgs a = make_args(L);
+  hipLaunchKernelGGL(plane_velocity_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), a, x, (const int *)L->ob_list, n, d);
+  HC_HIP(hipGetLastError());
+  if (!on_device) HC_HIP(hipMemcpyAsync(out, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));   // the staged node list is reused by the next call
   return HC_OK;
 }
 

@@ -136,9 +136,97 @@ class Lattice:
         check(self.lib.hcl_set_body_force_regions(self.ptr, len(bb), bb.ctypes.data_as(C.POINTER(C.c_int)), dptr(ff)))
 
     def setBoundaryVelocity(self, wall_class, u):
-        """velocity of the nodes whose mask value is wall_class (3..6)"""
-        uu = np.array(u, dtype=np.float64)
-        check(self.lib.hcl_set_wall_velocity(self.ptr, int(wall_class), dptr(uu)))
+        """wall_class an int: velocity of the nodes whose mask value is wall_class (3..6).  Otherwise wall_class is an
+        inclusive box (x0, x1, y0, y1, z0, z1) or an [n][3] node list, and u one velocity or one per node ([n][3]) for its
+        Zou-He velocity nodes (setBoundaryVelocity on nodes of addVelocityBoundary*)"""
+        if isinstance(wall_class, (int, np.integer)):
+            uu = np.array(u, dtype=np.float64)
+            check(self.lib.hcl_set_wall_velocity(self.ptr, int(wall_class), dptr(uu)))
+            return
+        self._set_open(wall_class, u, 3, self.lib.hcl_open_boundary_set_velocity)
+
+    def setBoundaryDensity(self, where, rho):
+        """density of the Zou-He pressure nodes of a box or an [n][3] node list: one value or one per node"""
+        self._set_open(where, rho, 1, self.lib.hcl_open_boundary_set_density)
+
+    # Zou-He open boundaries with normal x (hcl_open_boundary_*).  Boxes are inclusive (x0, x1, y0, y1, z0, z1) in local
+    # node coordinates; each call returns (first_slot, n): the nodes hold the slots first_slot .. first_slot + n - 1 in
+    # box order (x outermost, z innermost)
+    def addVelocityBoundary0N(self, box):
+        return self._add_open_box(0, -1, box)
+
+    def addVelocityBoundary0P(self, box):
+        return self._add_open_box(0, 1, box)
+
+    def addPressureBoundary0N(self, box):
+        return self._add_open_box(1, -1, box)
+
+    def addPressureBoundary0P(self, box):
+        return self._add_open_box(1, 1, box)
+
+    def addOpenBoundaryNodes(self, kind, orientation, nodes):
+        """kind 0 = velocity, 1 = pressure; orientation -1 = 0N, +1 = 0P; nodes [n][3]: returns the first slot"""
+        nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
+        first = C.c_int()
+        check(self.lib.hcl_open_boundary_add(self.ptr, int(kind), int(orientation), nn.ctypes.data_as(C.POINTER(C.c_int)),
+                                             len(nn), C.byref(first)))
+        return first.value
+
+    def clearOpenBoundaries(self):
+        check(self.lib.hcl_open_boundary_clear(self.ptr))
+
+    def openBoundarySlots(self, nodes):
+        nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
+        out = np.empty(len(nn), np.int32)
+        check(self.lib.hcl_open_boundary_slots(self.ptr, nn.ctypes.data_as(C.POINTER(C.c_int)), len(nn),
+                                               out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
+    def setOpenBoundaryVelocitySlots(self, first_slot, u):
+        uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 3)
+        check(self.lib.hcl_open_boundary_set_velocity(self.ptr, int(first_slot), len(uu), uu.ctypes.data, 0))
+
+    def setOpenBoundaryDensitySlots(self, first_slot, rho):
+        rr = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+        check(self.lib.hcl_open_boundary_set_density(self.ptr, int(first_slot), len(rr), rr.ctypes.data, 0))
+
+    def openBoundaryValues(self, first_slot, n):
+        """[n][4] (u_x, u_y, u_z, rho) of the slots"""
+        out = np.empty((int(n), 4))
+        check(self.lib.hcl_open_boundary_values(self.ptr, int(first_slot), int(n), dptr(out)))
+        return out
+
+    def planeVelocity(self, x, yz):
+        """Cell::computeVelocity (u = j/rho + F/2, F the body force) on in-plane indices y * nz + z of plane x: [n][3]"""
+        ii = np.ascontiguousarray(yz, dtype=np.int32).reshape(-1)
+        out = np.empty((len(ii), 3))
+        check(self.lib.hcl_plane_velocity(self.ptr, int(x), ii.ctypes.data_as(C.POINTER(C.c_int)), len(ii), out.ctypes.data, 0))
+        return out
+
+    def _add_open_box(self, kind, orientation, box):
+        bb = (C.c_int * 6)(*[int(v) for v in box])
+        first, n = C.c_int(), C.c_int()
+        check(self.lib.hcl_open_boundary_add_box(self.ptr, int(kind), int(orientation), bb, C.byref(first), C.byref(n)))
+        return first.value, n.value
+
+    def _set_open(self, where, values, nc, fn):
+        w = np.asarray(where)
+        if w.shape == (6,):
+            x0, x1, y0, y1, z0, z1 = [int(v) for v in w]
+            g = np.mgrid[x0:x1 + 1, y0:y1 + 1, z0:z1 + 1].reshape(3, -1).T
+        else:
+            g = w.reshape(-1, 3)
+        slots = self.openBoundarySlots(g)
+        if (slots < 0).any():
+            raise HcError("node %s is not an open-boundary node" % (tuple(g[np.argmax(slots < 0)]),))
+        v = np.asarray(values, dtype=np.float64)
+        v = np.broadcast_to(v.reshape(-1, nc) if v.size != nc else v.reshape(1, nc), (len(g), nc))
+        order = np.argsort(slots, kind="stable")
+        s, vv = slots[order], np.ascontiguousarray(v[order])
+        cut = np.flatnonzero(np.diff(s) != 1) + 1   # one call per run of consecutive slots
+        for a, b in zip(np.r_[0, cut], np.r_[cut, len(s)]):
+            blk = np.ascontiguousarray(vv[a:b])
+            check(fn(self.ptr, int(s[a]), int(b - a), blk.ctypes.data, 0))
 
     def collideAndStream(self, steps=1):
         check(self.lib.hcl_collide_stream(self.ptr, int(steps)))
@@ -245,6 +333,59 @@ class LeesEdwardsBC:
     def updateLECurDisplacement(self, it):
         self.LEcurrentDisplacement = math.fmod(self.LEdisplacement * it, float(self.nx))
         self.lattice.setLeesEdwardsDisplacement(self.LEcurrentDisplacement, self.lattice.leesEdwardsState()[3])
+
+
+def preinlet_driving_force(Re, nu_lbm, fluid_area, direction="Xpos"):
+    """PreInlet::calculateDrivingForce (helper/preInlet.cpp): the pipe radius R = sqrt(A / pi) of the gathered number A of
+    fluid nodes of the pre-inlet's plane 2 in from its upstream end, u_max = Re nu / (2 R) and the driving force
+    8 nu (u_max / 2) / R / R in the reference's operation order, along -x for Xpos and +x for Xneg.  Returns (R, u_max, F_x)."""
+    if direction not in ("Xpos", "Xneg"):
+        raise HcError("PreInlet: only the directions Xpos and Xneg are supported")
+    radius = math.sqrt(fluid_area / math.pi)
+    u_max = Re * nu_lbm / (radius * 2)
+    force = 8 * nu_lbm * (u_max * 0.5) / radius / radius
+    return radius, u_max, (-force if direction == "Xpos" else force)
+
+
+class PreInlet:
+    """One-process stand-in for helper/preInlet.h's fluid coupling (x-normal): a pre-inlet lattice and a domain lattice step
+    in the reference's per-iteration order -- both iterate, then applyPreInlet: the pre-inlet evaluates u = j/rho + F/2 on its
+    plane pre_x at the coupled nodes, and the domain takes them as the velocities of its Zou-He velocity nodes at the same
+    global (y, z) on its plane domain_x (0N for Xneg, 0P for Xpos).  The domain thus lags the pre-inlet by one iteration, as
+    in the reference.  yz: [n][2] GLOBAL (y, z) of the coupled nodes; pre_origin / domain_origin: the global (y, z) of each
+    lattice's node (., 0, 0) -- the cross-sections may differ, as the reference's pre-inlet box (the slice's bounding box
+    enlarged by 1) differs from the domain's.  Cells do not cross yet: the coupling is the fluid's."""
+
+    def __init__(self, preinlet, domain, yz, pre_x, domain_x, direction="Xpos", pre_origin=(0, 0), domain_origin=(0, 0)):
+        if direction not in ("Xpos", "Xneg"):
+            raise HcError("PreInlet: only the directions Xpos and Xneg are supported")
+        self.pre, self.domain = preinlet, domain
+        g = np.asarray(yz, dtype=np.int64).reshape(-1, 2)
+        py, pz = g[:, 0] - int(pre_origin[0]), g[:, 1] - int(pre_origin[1])
+        dy, dz = g[:, 0] - int(domain_origin[0]), g[:, 1] - int(domain_origin[1])
+        if ((py < 0) | (py >= preinlet.ny) | (pz < 0) | (pz >= preinlet.nz)).any():
+            raise HcError("PreInlet: a coupled node lies outside the pre-inlet's cross-section")
+        if ((dy < 0) | (dy >= domain.ny) | (dz < 0) | (dz >= domain.nz)).any():
+            raise HcError("PreInlet: a coupled node lies outside the domain's cross-section")
+        self.pre_yz = np.ascontiguousarray(py * preinlet.nz + pz, dtype=np.int32)
+        self.pre_x, self.domain_x = int(pre_x), int(domain_x)
+        self.domain_nodes = np.stack([np.full(len(g), self.domain_x), dy, dz], axis=1)
+        # Xneg: the pre-inlet lies below the domain and drives along +x, so the domain's inlet is a 0N side; Xpos mirrors it
+        self.first = domain.addOpenBoundaryNodes(0, -1 if direction == "Xneg" else 1, self.domain_nodes)
+
+    def applyPreInlet(self):
+        u = self.pre.planeVelocity(self.pre_x, self.pre_yz)
+        self.domain.setOpenBoundaryVelocitySlots(self.first, u)
+        return u
+
+    def iterate(self, n=1):
+        """n iterations of (pre-inlet step, domain step, applyPreInlet); returns the last plane velocities sent"""
+        u = None
+        for _ in range(int(n)):
+            self.pre.collideAndStream(1)
+            self.domain.collideAndStream(1)
+            u = self.applyPreInlet()
+        return u
 
 
 class CellType:

@@ -160,6 +160,32 @@ int hcl_set_lees_edwards_displacement(hc_lattice *L, double D, double d_per_iter
 int hcl_lees_edwards_apply(hc_lattice *L);
 /* out = {D, v_top, v_bottom, d_per_iteration} */
 int hcl_lees_edwards_state(const hc_lattice *L, double out[4]);
+/* Zou-He open boundaries with normal x (Palabos' addVelocityBoundary0N/0P, addPressureBoundary0N/0P).  kind: HC_OB_VELOCITY
+ * (u given, rho from the known populations) or HC_OB_PRESSURE (rho given, u = (u_x, 0, 0) from them); orientation -1 = 0N
+ * (the populations with c_x = +1 are completed), +1 = 0P (c_x = -1).  The completion runs inside the collide, between the
+ * gather and the Guo-forced BGK, on the post-stream populations of the declared nodes; their mask stays fluid, and nodes
+ * that are bounce-back stay bounce-back.  nodes: [n][3] local node coordinates; the nodes get the consecutive slots
+ * first_slot .. first_slot + n - 1 (a node declared again takes its new slot), starting at u = 0 and rho = 1.  Lattices
+ * without open boundaries run the collide exactly as before.  Needs n_slabs = 1. */
+#define HC_OB_VELOCITY 0
+#define HC_OB_PRESSURE 1
+int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot);
+/* every node of the inclusive local box {x0, x1, y0, y1, z0, z1}, x outermost and z innermost */
+int hcl_open_boundary_add_box(hc_lattice *L, int kind, int orientation, const int box[6], int *first_slot, int *n_nodes);
+int hcl_open_boundary_clear(hc_lattice *L);
+/* slots[i] = the slot of local node nodes[i], or -1 */
+int hcl_open_boundary_slots(const hc_lattice *L, const int *nodes, int n, int *slots);
+/* setBoundaryVelocity / setBoundaryDensity on slots first_slot .. first_slot + n - 1: u [n][3], rho [n], read from the
+ * device (on_device != 0, ordered on the library's stream) or from the host */
+int hcl_open_boundary_set_velocity(hc_lattice *L, int first_slot, int n, const double *u, int on_device);
+int hcl_open_boundary_set_density(hc_lattice *L, int first_slot, int n, const double *rho, int on_device);
+/* out = [n][4] {u_x, u_y, u_z, rho} of the slots, host */
+int hcl_open_boundary_values(hc_lattice *L, int first_slot, int n, double *out);
+/* Cell::computeVelocity on nodes of the plane x of the post-stream state: u = j/rho + F/2 with F the body force (and the
+ * force regions) alone -- what HemoCell's force field holds after iterate() and setExternalVector.  yz: [n] in-plane
+ * indices y * nz + z (host); out: [n][3] on the device (on_device != 0, ordered on the library's stream) or the host.
+ * Bounce-back nodes give 0. */
+int hcl_plane_velocity(hc_lattice *L, int x, const int *yz, int n, double *out, int on_device);
 /* bring the x-halo planes of a slab up to date (width 1 or 2, see hcl_halo_doubles) through the data plane; the
  * download / statistics entry points do it by themselves */
 int hcl_slab_refresh_halos(hc_lattice *L, int width);
