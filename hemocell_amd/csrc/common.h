@@ -90,6 +90,50 @@ __device__ __forceinline__ void region_force(const BodyRegions &r, int xg, int y
     if (xg >= b[0] && xg <= b[1] && y >= b[2] && y <= b[3] && z >= b[4] && z <= b[5]) { bx = r.f[k][0]; by = r.f[k][1]; bz = r.f[k][2]; }
   }
 }
+
+// Zou-He completion with normal x on the gathered populations f (stored form f - t_q; the opposite populations of a pair share
+// t_q, so the completed ones are formed in that form directly).  code & 3: 0 = velocity 0N, 1 = velocity 0P, 2 = pressure 0N,
+// 3 = pressure 0P.  0N completes the five populations with c_x = +1 from their opposites:
+//   rho = (S_0 + 2 S_-) / (1 - u_x) with the real sums S (the t_q of the nine c_x = 0 and twice the five c_x = -1 ones add 1),
+//   f(1,0,0) = f(-1,0,0) + rho u_x / 3,  f(1,+-1,0) = f(-1,-+1,0) + rho (u_x +- u_y) / 6 -+ N_y,  likewise z,
+//   N_y = (sum f over c = (0,1,.) - sum over (0,-1,.)) / 2 - rho u_y / 3;
+// 0P mirrors it.  Pressure nodes take rho and u_x = 1 - (S_0 + 2 S_-) / rho (0N), (S_0 + 2 S_+) / rho - 1 (0P), u_y = u_z = 0.
+// tests/open_boundary_ref.py restates this operation for operation.  The collide calls it on fluid nodes before it relaxes, and
+// every observer of an open lattice (rho_u, pi_neq, plane velocity, statistics, the IBM node velocity) before it takes moments.
+__device__ __forceinline__ void zou_he_x(double f[HC_Q], int code, const double *__restrict__ val) {
+  const int kind = code & 3;
+  const long slot = code >> 2;
+  const double s0 = f[0] + f[2] + f[3] + f[8] + f[9] + f[11] + f[12] + f[17] + f[18];
+  const double sm = f[1] + f[4] + f[5] + f[6] + f[7];
+  const double sp = f[10] + f[13] + f[14] + f[15] + f[16];
+  const bool neg = (kind & 1) == 0;   // 0N
+  const double s_out = neg ? sm : sp;
+  const double known = s0 + 2.0 * s_out + 1.0;
+  double rho, ux, uy, uz;
+  if (kind < 2) {
+    ux = val[4 * slot]; uy = val[4 * slot + 1]; uz = val[4 * slot + 2];
+    rho = neg ? known / (1.0 - ux) : known / (1.0 + ux);
+  } else {
+    rho = val[4 * slot + 3];
+    ux = neg ? 1.0 - known / rho : known / rho - 1.0;
+    uy = 0.0; uz = 0.0;
+  }
+  const double ny = 0.5 * ((f[11] + f[17] + f[18]) - (f[2] + f[8] + f[9])) - rho * uy / 3.0;
+  const double nz = 0.5 * ((f[12] + f[9] + f[17]) - (f[3] + f[8] + f[18])) - rho * uz / 3.0;
+  if (neg) {
+    f[10] = f[1] + rho * ux / 3.0;
+    f[13] = f[4] + rho * (ux + uy) / 6.0 - ny;
+    f[14] = f[5] + rho * (ux - uy) / 6.0 + ny;
+    f[15] = f[6] + rho * (ux + uz) / 6.0 - nz;
+    f[16] = f[7] + rho * (ux - uz) / 6.0 + nz;
+  } else {
+    f[1] = f[10] - rho * ux / 3.0;
+    f[4] = f[13] - rho * (ux + uy) / 6.0 + ny;
+    f[5] = f[14] - rho * (ux - uy) / 6.0 - ny;
+    f[6] = f[15] - rho * (ux + uz) / 6.0 + nz;
+    f[7] = f[16] - rho * (ux - uz) / 6.0 - nz;
+  }
+}
 #endif
 }  // namespace hc
 

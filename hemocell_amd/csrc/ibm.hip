@@ -5,6 +5,7 @@
 //   core/hemoCellParticleField.cpp:841-863        spreadParticleForce
 //   core/hemoCellParticleField.cpp:819-839        interpolateFluidVelocity
 #include "cells.h"
+#include <type_traits>
 #include <hipcub/hipcub.hpp>
 #include <cstdlib>
 #include <cstring>
@@ -100,8 +101,14 @@ struct PopView {
   const double *f; const double *F; double bx, by, bz; long qs;   // qs: population stride
   hc::BodyRegions reg;
 };
+// lattices with Zou-He open boundaries (hc_lattice::ob_n > 0) run the OPEN instantiations of the interpolation kernels: the
+// gathered populations of a fluid open-boundary node are completed (zou_he_x, as the collide is about to) before the moments
+// are taken.  Every other lattice keeps PopView, its kernel-argument block and its code.
+struct OpenPopView : PopView { const int *ob_code; const double *ob_val; };
+template <bool OPEN> using Pops = std::conditional_t<OPEN, OpenPopView, PopView>;
 
-__device__ __forceinline__ void node_velocity(const LatView &v, const PopView &pv, int lx, int ly, int lz, long node, double u[3]) {
+template <bool OPEN = false>
+__device__ __forceinline__ void node_velocity(const LatView &v, const Pops<OPEN> &pv, int lx, int ly, int lz, long node, double u[3]) {
   // A node on the OUTER halo plane of a slab would pull from beyond the allocation.  Only particles whose nearest node lies
   // outside the slab have such a node in their stencil, and their interpolated velocity is never used (the owner's record
   // replaces it, "a local particle wins"), so the value does not matter -- the access must not happen.
@@ -121,6 +128,12 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const PopView &p
   if (lz == 0) { if (v.per_z) zm = v.nz - 1; else zmk = false; }
   if (lz == v.nz - 1) { if (v.per_z) zp = -(v.nz - 1); else zpk = false; }
   double r = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+  [[maybe_unused]] double f[OPEN ? HC_Q : 1];   // OPEN: the gathered populations are kept, completed, and summed afterwards in the same order
+#define NV_Q(M)                                                                              \
+  M(0, 0, 0, 0) M(1, -1, 0, 0) M(2, 0, -1, 0) M(3, 0, 0, -1) M(4, -1, -1, 0) M(5, -1, 1, 0)  \
+  M(6, -1, 0, -1) M(7, -1, 0, 1) M(8, 0, -1, -1) M(9, 0, -1, 1) M(10, 1, 0, 0) M(11, 0, 1, 0) \
+  M(12, 0, 0, 1) M(13, 1, 1, 0) M(14, 1, -1, 0) M(15, 1, 0, 1) M(16, 1, 0, -1) M(17, 0, 1, 1) \
+  M(18, 0, 1, -1)
 #define M(Q, CX, CY, CZ)                                                              \
   {                                                                                   \
     long off = 0; bool ok = true;                                                     \
@@ -128,16 +141,30 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const PopView &p
     if (CY == 1) { off += ym; ok = ok && ymk; } else if (CY == -1) { off += yp; ok = ok && ypk; } \
     if (CZ == 1) { off += zm; ok = ok && zmk; } else if (CZ == -1) { off += zp; ok = ok && zpk; } \
     const double fq = ok ? pv.f[(long)Q * pv.qs + node + off] : 0.0;                 \
-    r += fq;                                                                          \
-    if (CX == 1) jx += fq; else if (CX == -1) jx += -fq;                              \
-    if (CY == 1) jy += fq; else if (CY == -1) jy += -fq;                              \
-    if (CZ == 1) jz += fq; else if (CZ == -1) jz += -fq;                              \
+    if constexpr (OPEN) f[Q] = fq;                                                    \
+    else {                                                                            \
+      r += fq;                                                                        \
+      if (CX == 1) jx += fq; else if (CX == -1) jx += -fq;                            \
+      if (CY == 1) jy += fq; else if (CY == -1) jy += -fq;                            \
+      if (CZ == 1) jz += fq; else if (CZ == -1) jz += -fq;                            \
+    }                                                                                 \
   }
-  M(0, 0, 0, 0) M(1, -1, 0, 0) M(2, 0, -1, 0) M(3, 0, 0, -1) M(4, -1, -1, 0) M(5, -1, 1, 0)
-  M(6, -1, 0, -1) M(7, -1, 0, 1) M(8, 0, -1, -1) M(9, 0, -1, 1) M(10, 1, 0, 0) M(11, 0, 1, 0)
-  M(12, 0, 0, 1) M(13, 1, 1, 0) M(14, 1, -1, 0) M(15, 1, 0, 1) M(16, 1, 0, -1) M(17, 0, 1, 1)
-  M(18, 0, 1, -1)
+  NV_Q(M)
 #undef M
+  if constexpr (OPEN) {
+    if (v.mask[node] == 0) {
+      const int code = pv.ob_code[node];
+      if (code >= 0) hc::zou_he_x(f, code, pv.ob_val);
+    }
+#define M(Q, CX, CY, CZ)                                                              \
+    r += f[Q];                                                                        \
+    if (CX == 1) jx += f[Q]; else if (CX == -1) jx += -f[Q];                          \
+    if (CY == 1) jy += f[Q]; else if (CY == -1) jy += -f[Q];                          \
+    if (CZ == 1) jz += f[Q]; else if (CZ == -1) jz += -f[Q];
+    NV_Q(M)
+#undef M
+  }
+#undef NV_Q
   const double invRho = 1.0 / (1.0 + r);
   double bx = pv.bx, by = pv.by, bz = pv.bz;
   if (pv.reg.n) {   // a halo plane of a slab, or the wrapped image, is the global node next door
@@ -159,11 +186,12 @@ __global__ __launch_bounds__(256) void face_velocity_kernel(LatView v, PopView p
   const int ly = k / v.nz, lz = k - ly * v.nz;
   const long node = (long)(lx + HALO) * v.plane + (long)ly * v.nz + lz;
   double u[3] = {0.0, 0.0, 0.0};
-  if (v.mask[node] == 0) node_velocity(v, pv, lx, ly, lz, node, u);   // stencils admit fluid nodes only
+  if (v.mask[node] == 0) node_velocity<false>(v, pv, lx, ly, lz, node, u);   // stencils admit fluid nodes only; slabs have no open boundaries
   out[k] = u[0]; out[v.ny_nz + k] = u[1]; out[2L * v.ny_nz + k] = u[2];
 }
 
-__global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, PopView pv, long n, const double *px, const double *py,
+template <bool OPEN = false>
+__global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, Pops<OPEN> pv, long n, const double *px, const double *py,
                                                               const double *pz, double *vx, double *vy, double *vz, const int *vert_cell, const int *tag,
                                                               const unsigned char *dead) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -176,7 +204,7 @@ __global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, PopView
   for (int k = 0; k < 8; k++) {
     if (s.node[k] < 0) continue;
     double u[3];
-    node_velocity(v, pv, s.lx[k], s.ly[k], s.lz[k], s.node[k], u);
+    node_velocity<OPEN>(v, pv, s.lx[k], s.ly[k], s.lz[k], s.node[k], u);
     a0 += (u[0] * s.w[k]); a1 += (u[1] * s.w[k]); a2 += (u[2] * s.w[k]);
   }
   vx[i] = a0; vy[i] = a1; vz[i] = a2;
@@ -539,7 +567,8 @@ __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv,
   STAMP(7);
 }
 
-__global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, PopView pv, int nv, const double *px, const double *py,
+template <bool OPEN = false>
+__global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Pops<OPEN> pv, int nv, const double *px, const double *py,
                                                                    const double *pz, double *vx, double *vy, double *vz, const int *slots, int xcd_ranges,
                                                                    const int *tag, const unsigned char *vdead) {
   // 54 KB in all, so that three workgroups share a CU: 16-bit slots, and the node list reuses the mask tile
@@ -569,7 +598,7 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
       int lx, ly, lz;
       const long node = tile_node(v, t, list[k], lx, ly, lz);
       double u[3];
-      node_velocity(v, pv, lx, ly, lz, node, u);
+      node_velocity<OPEN>(v, pv, lx, ly, lz, node, u);
       ux[k] = u[0]; uy[k] = u[1]; uz[k] = u[2];
     }
     __syncthreads();
@@ -599,7 +628,7 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
     for (int k = 0; k < 8; k++) {
       if (s.node[k] < 0) continue;
       double u[3];
-      node_velocity(v, pv, s.lx[k], s.ly[k], s.lz[k], s.node[k], u);
+      node_velocity<OPEN>(v, pv, s.lx[k], s.ly[k], s.lz[k], s.node[k], u);
       a0 += (u[0] * s.w[k]); a1 += (u[1] * s.w[k]); a2 += (u[2] * s.w[k]);
     }
     vx[base + i] = a0; vy[base + i] = a1; vz[base + i] = a2;
@@ -607,6 +636,19 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
 }
 
 }  // namespace
+
+// launches K<true> with the open-boundary tables while the lattice L has Zou-He nodes, K<false> as ever otherwise
+static OpenPopView open_pops(const hc_lattice *L, const PopView &pv) {
+  OpenPopView o;
+  static_cast<PopView &>(o) = pv;
+  o.ob_code = L->ob_code; o.ob_val = L->ob_val;
+  return o;
+}
+#define HC_LAUNCH_POPS(K, grid, block, v, pv, ...)                                                                      \
+  do {                                                                                                                  \
+    if (L->ob_n > 0) hipLaunchKernelGGL(K<true>, grid, block, 0, hc::stream(), v, open_pops(L, pv), __VA_ARGS__);       \
+    else hipLaunchKernelGGL(K<false>, grid, block, 0, hc::stream(), v, pv, __VA_ARGS__);                                \
+  } while (0)
 
 static int g_ibm_per_vertex = 0;  // 1: one thread per vertex with direct global atomics (kept for A/B and as reference)
 extern "C" int hc_debug_ibm_per_vertex(int on) { g_ibm_per_vertex = on; return HC_OK; }
@@ -726,12 +768,12 @@ int hcp_interpolate(hc_cells *C) {
     if (n == 0) continue;
     const int nv = C->types[t]->host.nv;
     if (g_ibm_per_vertex)
-      hipLaunchKernelGGL(ibm_interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, pv, n,
+      HC_LAUNCH_POPS(ibm_interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), v, pv, n,
                          (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
                          C->vel[0] + f, C->vel[1] + f, C->vel[2] + f, (const int *)(C->d_vert_cell + f), (const int *)C->d_tag,
                          (const unsigned char *)(C->d_vdead + f));
     else {
-      hipLaunchKernelGGL(ibm_interpolate_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), 0, hc::stream(), v, pv, nv,
+      HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), v, pv, nv,
                          (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
                          C->vel[0] + f, C->vel[1] + f, C->vel[2] + f, (const int *)nullptr, 1, (const int *)(C->d_tag + C->cell0[t]),
                          (const unsigned char *)(C->d_vdead + f));
@@ -798,7 +840,7 @@ int hcc::interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n
   PopView pv{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
   const long f = C->first[type];
   const int nv = C->types[type]->host.nv;
-  hipLaunchKernelGGL(ibm_interpolate_cell_kernel, dim3((unsigned)n), dim3(nv > 128 ? 256 : 128), 0, hc::stream(), v, pv, nv,
+  HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)n), dim3(nv > 128 ? 256 : 128), v, pv, nv,
                      (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
                      C->vel[0] + f, C->vel[1] + f, C->vel[2] + f, (const int *)d_slots, 0, (const int *)(C->d_tag + C->cell0[type]),
                      (const unsigned char *)(C->d_vdead + f));

@@ -57,6 +57,7 @@ struct OpenArgs : LatArgs {
   const int *ob_code;    // Zou-He open boundaries: -1 or slot << 2 | kind
   const double *ob_val;  // [slot][4] {u_x, u_y, u_z, rho}
 };
+template <bool OPEN> using Args = std::conditional_t<OPEN, OpenArgs, LatArgs>;
 
 // uniform body force, or that of the last region holding the node
 __device__ __forceinline__ void body_at(const LatArgs &a, int x, int y, int z, double &bx, double &by, double &bz) {
@@ -124,6 +125,19 @@ __device__ __forceinline__ void pull(const double *__restrict__ fin, long npad, 
 #undef M
 }
 
+// What an observer sees on an open lattice: the gathered populations of a fluid Zou-He node completed as the collide is about
+// to complete them, so that a velocity node reports u_bc (+ F / 2) and a pressure node its prescribed density instead of
+// moments that count the unknown populations as the zeros that came from outside.  Nothing without OPEN.
+template <bool OPEN>
+__device__ __forceinline__ void complete_open(const Args<OPEN> &a, long node, double f[HC_Q]) {
+  if constexpr (OPEN) {
+    if (a.mask[node] == 0) {
+      const int code = a.ob_code[node];
+      if (code >= 0) zou_he_x(f, code, a.ob_val);
+    }
+  }
+}
+
 // moments in the oracle's order: ascending q, zero-velocity components skipped
 __device__ __forceinline__ void moments(const double f[HC_Q], double &rhoBar, double &jx, double &jy, double &jz) {
   double r = 0.0, x = 0.0, y = 0.0, z = 0.0;
@@ -182,53 +196,10 @@ __device__ __forceinline__ void collide_guo(double f[HC_Q], double Fx, double Fy
 #undef M
 }
 
-// Zou-He completion with normal x on the gathered populations f (stored form f - t_q; the opposite populations of a pair share
-// t_q, so the completed ones are formed in that form directly).  code & 3: 0 = velocity 0N, 1 = velocity 0P, 2 = pressure 0N,
-// 3 = pressure 0P.  0N completes the five populations with c_x = +1 from their opposites:
-//   rho = (S_0 + 2 S_-) / (1 - u_x) with the real sums S (the t_q of the nine c_x = 0 and twice the five c_x = -1 ones add 1),
-//   f(1,0,0) = f(-1,0,0) + rho u_x / 3,  f(1,+-1,0) = f(-1,-+1,0) + rho (u_x +- u_y) / 6 -+ N_y,  likewise z,
-//   N_y = (sum f over c = (0,1,.) - sum over (0,-1,.)) / 2 - rho u_y / 3;
-// 0P mirrors it.  Pressure nodes take rho and u_x = 1 - (S_0 + 2 S_-) / rho (0N), (S_0 + 2 S_+) / rho - 1 (0P), u_y = u_z = 0.
-// tests/open_boundary_ref.py restates this operation for operation.
-__device__ __forceinline__ void zou_he_x(double f[HC_Q], int code, const double *__restrict__ val) {
-  const int kind = code & 3;
-  const long slot = code >> 2;
-  const double s0 = f[0] + f[2] + f[3] + f[8] + f[9] + f[11] + f[12] + f[17] + f[18];
-  const double sm = f[1] + f[4] + f[5] + f[6] + f[7];
-  const double sp = f[10] + f[13] + f[14] + f[15] + f[16];
-  const bool neg = (kind & 1) == 0;   // 0N
-  const double s_out = neg ? sm : sp;
-  const double known = s0 + 2.0 * s_out + 1.0;
-  double rho, ux, uy, uz;
-  if (kind < 2) {
-    ux = val[4 * slot]; uy = val[4 * slot + 1]; uz = val[4 * slot + 2];
-    rho = neg ? known / (1.0 - ux) : known / (1.0 + ux);
-  } else {
-    rho = val[4 * slot + 3];
-    ux = neg ? 1.0 - known / rho : known / rho - 1.0;
-    uy = 0.0; uz = 0.0;
-  }
-  const double ny = 0.5 * ((f[11] + f[17] + f[18]) - (f[2] + f[8] + f[9])) - rho * uy / 3.0;
-  const double nz = 0.5 * ((f[12] + f[9] + f[17]) - (f[3] + f[8] + f[18])) - rho * uz / 3.0;
-  if (neg) {
-    f[10] = f[1] + rho * ux / 3.0;
-    f[13] = f[4] + rho * (ux + uy) / 6.0 - ny;
-    f[14] = f[5] + rho * (ux - uy) / 6.0 + ny;
-    f[15] = f[6] + rho * (ux + uz) / 6.0 - nz;
-    f[16] = f[7] + rho * (ux - uz) / 6.0 + nz;
-  } else {
-    f[1] = f[10] - rho * ux / 3.0;
-    f[4] = f[13] - rho * (ux + uy) / 6.0 + ny;
-    f[5] = f[14] - rho * (ux - uy) / 6.0 - ny;
-    f[6] = f[15] - rho * (ux + uz) / 6.0 + nz;
-    f[7] = f[16] - rho * (ux - uz) / 6.0 - nz;
-  }
-}
-
 // OPEN: the instantiation for lattices with Zou-He nodes (launch_collide picks it while ob_n > 0); the other instantiations
 // compile to the same code as before it existed
 template <bool REGIONS, bool OPEN = false>
-__global__ __launch_bounds__(256) void collide_stream_kernel(std::conditional_t<OPEN, OpenArgs, LatArgs> a) {
+__global__ __launch_bounds__(256) void collide_stream_kernel(Args<OPEN> a) {
   // thread -> (y,z) through the active-span map of this plane: consecutive threads walk the spans of
   // consecutive rows, so every lane of every wave (except the last of a plane) has a live node
   const int x = a.x_begin + (int)blockIdx.y + ((int)blockIdx.y >= a.x_split ? a.x_jump : 0);
@@ -352,7 +323,8 @@ __global__ void upload_kernel(LatArgs a, const double *aos, int lo_ok, int hi_ok
 #undef M
 }
 
-__global__ void rho_u_kernel(LatArgs a, double *rho, double *u) {
+template <bool OPEN = false>
+__global__ void rho_u_kernel(Args<OPEN> a, double *rho, double *u) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.plane) return;
   const int x = a.x_begin + blockIdx.y;
@@ -361,6 +333,7 @@ __global__ void rho_u_kernel(LatArgs a, double *rho, double *u) {
   const Nbr n = neighbours(a, x, y, z);
   double f[HC_Q];
   pull(a.fin, a.qs, node, n, f);
+  complete_open<OPEN>(a, node, f);
   double rhoBar, j0, j1, j2;
   moments(f, rhoBar, j0, j1, j2);
   const double invRho = 1.0 / (1.0 + rhoBar);
@@ -376,7 +349,8 @@ __global__ void rho_u_kernel(LatArgs a, double *rho, double *u) {
 // Off-equilibrium part of the momentum-flux tensor, as Palabos' momentTemplates::compute_rhoBar_j_PiNeq forms it from the
 // stored populations f_i - t_i: Pi_ab = sum_i c_ia c_ib fbar_i - j_a j_b / rho - cs2 rhoBar delta_ab, components in the
 // order xx, xy, xz, yy, yz, zz.  Output fields only (shear stress, strain rate); nothing on the step path reads it.
-__global__ void pi_neq_kernel(LatArgs a, double *pi) {
+template <bool OPEN = false>
+__global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.plane) return;
   const int x = a.x_begin + blockIdx.y;
@@ -385,6 +359,7 @@ __global__ void pi_neq_kernel(LatArgs a, double *pi) {
   const Nbr n = neighbours(a, x, y, z);
   double f[HC_Q];
   pull(a.fin, a.qs, node, n, f);
+  complete_open<OPEN>(a, node, f);
   double rhoBar, j0, j1, j2;
   moments(f, rhoBar, j0, j1, j2);
   const double invRho = 1.0 / (1.0 + rhoBar);
@@ -409,7 +384,8 @@ __global__ void pi_neq_kernel(LatArgs a, double *pi) {
 }
 
 // Cell::computeVelocity on listed nodes of one plane with the body force alone (hcl_plane_velocity); out [n][3]
-__global__ void plane_velocity_kernel(LatArgs a, int x, const int *yz, int n, double *out) {
+template <bool OPEN = false>
+__global__ void plane_velocity_kernel(Args<OPEN> a, int x, const int *yz, int n, double *out) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   const int p = yz[k];
@@ -420,6 +396,7 @@ __global__ void plane_velocity_kernel(LatArgs a, int x, const int *yz, int n, do
     const Nbr nb = neighbours(a, x, y, z);
     double f[HC_Q];
     pull(a.fin, a.qs, node, nb, f);
+    complete_open<OPEN>(a, node, f);
     double rhoBar, j0, j1, j2;
     moments(f, rhoBar, j0, j1, j2);
     const double invRho = 1.0 / (1.0 + rhoBar);
@@ -449,7 +426,8 @@ __global__ void force_aos_kernel(LatArgs a, double *F) {
 
 // FluidInfo statistics (helper/fluidInfo.cpp:33-96): magnitude of Cell::computeVelocity (what 0) or of the external
 // force (what 1) over the non-boundary bulk nodes; what 2: rhoBar = sum of the 19 stored populations, all bulk nodes
-__global__ __launch_bounds__(256) void fluid_stats_kernel(LatArgs a, int what, double *partial) {
+template <bool OPEN = false>
+__global__ __launch_bounds__(256) void fluid_stats_kernel(Args<OPEN> a, int what, double *partial) {
   StatAcc acc{1e300, -1e300, 0.0, 0};
   const long nbulk = (long)a.nx * a.plane;
   for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < nbulk; k += (long)STAT_BLOCKS * 256) {
@@ -473,6 +451,7 @@ __global__ __launch_bounds__(256) void fluid_stats_kernel(LatArgs a, int what, d
       const Nbr n = neighbours(a, x, y, z);
       double f[HC_Q];
       pull(a.fin, a.qs, node, n, f);
+      complete_open<OPEN>(a, node, f);
       double rhoBar, j0, j1, j2;
       moments(f, rhoBar, j0, j1, j2);
       const double invRho = 1.0 / (1.0 + rhoBar);
@@ -618,6 +597,14 @@ LatArgs make_args(const hc_lattice *L) {
   return a;
 }
 
+// the arguments of the open-boundary instantiations
+OpenArgs open_args(const hc_lattice *L, const LatArgs &a) {
+  OpenArgs o;
+  static_cast<LatArgs &>(o) = a;
+  o.ob_code = L->ob_code; o.ob_val = L->ob_val;
+  return o;
+}
+
 dim3 plane_grid(const hc_lattice *L, int nplanes) { return dim3((unsigned)((L->plane + 255) / 256), (unsigned)nplanes, 1); }
 
 int ensure_scratch(hc_lattice *L, size_t doubles) {
@@ -704,9 +691,7 @@ int launch_collide(hc_lattice *L, int x_begin, int nplanes, int x2 = 0, int n2 =
   const unsigned ny = (unsigned)(nplanes + n2);
   const dim3 grid((unsigned)((L->max_active + 255) / 256), ny, 1);
   if (L->ob_n > 0) {
-    OpenArgs o;
-    static_cast<LatArgs &>(o) = a;
-    o.ob_code = L->ob_code; o.ob_val = L->ob_val;
+    const OpenArgs o = open_args(L, a);
     if (L->regions.n) hipLaunchKernelGGL((collide_stream_kernel<true, true>), grid, dim3(256), 0, hc::stream(), o);
     else hipLaunchKernelGGL((collide_stream_kernel<false, true>), grid, dim3(256), 0, hc::stream(), o);
   } else if (L->regions.n) hipLaunchKernelGGL(collide_stream_kernel<true>, grid, dim3(256), 0, hc::stream(), a);
@@ -992,6 +977,7 @@ int hcl_set_lees_edwards(hc_lattice *L, double v_top, double v_bottom) {
   HC_REQUIRE(L->n_slabs == 1, "hcl_set_lees_edwards: the Lees-Edwards boundary needs the whole domain on one GPU (n_slabs = 1)");
   HC_REQUIRE(L->periodic[0] && L->periodic[1] && L->periodic[2], "hcl_set_lees_edwards: the lattice must be periodic on all three axes");
   HC_REQUIRE(L->nz >= 4, "hcl_set_lees_edwards: nz must be at least 4");
+  HC_REQUIRE(L->ob_n == 0, "hcl_set_lees_edwards: the lattice has open-boundary nodes; open boundaries and Lees-Edwards do not combine");
   if (!le_layers_fluid(L, L->hmask.data(), L->xs)) {
     hc::set_error("hcl_set_lees_edwards: the layers z = 0, 1, nz-2 and nz-1 must hold fluid nodes only");
     return HC_ERR_STATE;
@@ -1077,9 +1063,21 @@ int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *n
   HC_REQUIRE(kind == HC_OB_VELOCITY || kind == HC_OB_PRESSURE, "hcl_open_boundary_add: kind must be HC_OB_VELOCITY or HC_OB_PRESSURE");
   HC_REQUIRE(orientation == -1 || orientation == 1, "hcl_open_boundary_add: orientation must be -1 (0N) or +1 (0P)");
   HC_REQUIRE(n >= 0 && (long)L->ob_n + n < (1L << 28), "hcl_open_boundary_add: too many nodes");
-  for (int i = 0; i < n; i++) {
-    const int *c = nodes + 3 * i;
-    HC_REQUIRE(c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz, "hcl_open_boundary_add: node outside the lattice");
+  // The Lees-Edwards pass rewrites the post-stream populations of its z layers from plain moments of gathered populations; what
+  // it should read and leave on a node whose populations the collide completes is not defined, so the two do not share a lattice
+  HC_REQUIRE(!L->le_on, "hcl_open_boundary_add: the lattice has a Lees-Edwards boundary; open boundaries and Lees-Edwards do not combine");
+  // a node holds one slot: declaring it again (in this call or an earlier one) would orphan the first slot and let the second
+  // declaration win silently, so it is refused and nothing is changed
+  {
+    std::vector<size_t> seen((size_t)n);
+    for (int i = 0; i < n; i++) {
+      const int *c = nodes + 3 * i;
+      HC_REQUIRE(c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz, "hcl_open_boundary_add: node outside the lattice");
+      seen[(size_t)i] = (size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2];
+      HC_REQUIRE(!L->ob_code || L->ob_hcode[seen[(size_t)i]] < 0, "hcl_open_boundary_add: node declared twice (it is an open-boundary node already; hcl_open_boundary_clear removes all)");
+    }
+    std::sort(seen.begin(), seen.end());
+    HC_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "hcl_open_boundary_add: node declared twice (listed more than once)");
   }
   if (first_slot) *first_slot = L->ob_n;
   if (n == 0) return HC_OK;
@@ -1165,7 +1163,8 @@ int hcl_plane_velocity(hc_lattice *L, int x, const int *yz, int n, double *out, 
   double *d = out;
   if (!on_device) { rc = ob_stage((void **)&L->ob_out, &L->ob_out_cap, 3 * sizeof(double), n); if (rc != HC_OK) return rc; d = L->ob_out; }
   LatArgs a = make_args(L);
-  hipLaunchKernelGGL(plane_velocity_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), a, x, (const int *)L->ob_list, n, d);
+  if (L->ob_n > 0) hipLaunchKernelGGL(plane_velocity_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), open_args(L, a), x, (const int *)L->ob_list, n, d);
+  else hipLaunchKernelGGL(plane_velocity_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), a, x, (const int *)L->ob_list, n, d);
   HC_HIP(hipGetLastError());
   if (!on_device) HC_HIP(hipMemcpyAsync(out, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));   // the staged node list is reused by the next call
@@ -1218,7 +1217,8 @@ int hcl_download_rho_u(hc_lattice *L, double *rho, double *u) {
   const size_t n = (size_t)L->nx * L->plane;
   int rc = ensure_scratch(L, n * 4); if (rc != HC_OK) return rc;
   LatArgs a = make_args(L);
-  hipLaunchKernelGGL(rho_u_kernel, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch, L->scratch + n);
+  if (L->ob_n > 0) hipLaunchKernelGGL(rho_u_kernel<true>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), open_args(L, a), L->scratch, L->scratch + n);
+  else hipLaunchKernelGGL(rho_u_kernel<false>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch, L->scratch + n);
   HC_HIP(hipGetLastError());
   HC_HIP(hipMemcpyAsync(rho, L->scratch, n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipMemcpyAsync(u, L->scratch + n, 3 * n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
@@ -1232,7 +1232,8 @@ int hcl_download_pi_neq(hc_lattice *L, double *pi) {
   const size_t n = (size_t)L->nx * L->plane;
   int rc = ensure_scratch(L, n * 6); if (rc != HC_OK) return rc;
   LatArgs a = make_args(L);
-  hipLaunchKernelGGL(pi_neq_kernel, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch);
+  if (L->ob_n > 0) hipLaunchKernelGGL(pi_neq_kernel<true>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), open_args(L, a), L->scratch);
+  else hipLaunchKernelGGL(pi_neq_kernel<false>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch);
   HC_HIP(hipGetLastError());
   HC_HIP(hipMemcpyAsync(pi, L->scratch, 6 * n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
@@ -1262,7 +1263,8 @@ int hcl_fluid_stats(hc_lattice *L, int what, double out[3], long *n_nodes) {
   if (L->n_slabs > 1 && what == 0) { const int rc0 = hcl_slab_refresh_halos(L, 1); if (rc0 != HC_OK) return rc0; }   // velocities on the face planes pull from the halos
   int rc = ensure_scratch(L, (size_t)STAT_BLOCKS * 4); if (rc != HC_OK) return rc;
   LatArgs a = make_args(L);
-  hipLaunchKernelGGL(fluid_stats_kernel, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), a, what, L->scratch);
+  if (L->ob_n > 0) hipLaunchKernelGGL(fluid_stats_kernel<true>, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), open_args(L, a), what, L->scratch);
+  else hipLaunchKernelGGL(fluid_stats_kernel<false>, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), a, what, L->scratch);
   HC_HIP(hipGetLastError());
   return hc::stat_finish(L->scratch, out, n_nodes);
 }

@@ -165,8 +165,14 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]);
  * (the populations with c_x = +1 are completed), +1 = 0P (c_x = -1).  The completion runs inside the collide, between the
  * gather and the Guo-forced BGK, on the post-stream populations of the declared nodes; their mask stays fluid, and nodes
  * that are bounce-back stay bounce-back.  nodes: [n][3] local node coordinates; the nodes get the consecutive slots
- * first_slot .. first_slot + n - 1 (a node declared again takes its new slot), starting at u = 0 and rho = 1.  Lattices
- * without open boundaries run the collide exactly as before.  Needs n_slabs = 1. */
+ * first_slot .. first_slot + n - 1, starting at u = 0 and rho = 1.  A node holds one slot: a call that names a node that
+ * is an open-boundary node already, or names a node twice, is refused and changes nothing (hcl_open_boundary_clear removes
+ * all).  While a lattice has such nodes, every observer (hcl_download_rho_u, hcl_download_pi_neq, hcl_plane_velocity,
+ * the velocity statistic of hcl_fluid_stats (what 0), the IBM interpolation) takes its moments of the COMPLETED populations
+ * of a fluid open-boundary node: a velocity node reports u_bc + F / 2, a pressure node its prescribed density.  The force
+ * and mass statistics (what 1, 2) are untouched: mass is the sum of the STORED populations, which is what is conserved.  Lattices without open boundaries run the
+ * collide and the observers exactly as before.  Needs n_slabs = 1 and a lattice without a Lees-Edwards boundary (and
+ * hcl_set_lees_edwards refuses a lattice with open-boundary nodes): the two do not combine. */
 #define HC_OB_VELOCITY 0
 #define HC_OB_PRESSURE 1
 int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot);

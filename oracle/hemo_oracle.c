@@ -44,7 +44,7 @@ orc_lattice *orc_lattice_create(int nx, int ny, int nz, const int periodic[3], d
 }
 void orc_lattice_destroy(orc_lattice *L) {
   if (!L) return;
-  free(L->f); free(L->ftmp); free(L->force); free(L->mask); free(L);
+  free(L->f); free(L->ftmp); free(L->force); free(L->mask); free(L->ob_code); free(L->ob_val); free(L);
 }
 void orc_lattice_set_threads(orc_lattice *L, int n) { L->nthreads = n < 1 ? 1 : n; }
 void orc_lattice_set_wall_velocity(orc_lattice *L, int cls, const double u[3]) { for (int d = 0; d < 3; d++) L->wall_u[cls][d] = u[d]; }
@@ -101,11 +101,70 @@ static inline void moments(const double *f, double *rhoBar, double j[3]) {
   *rhoBar = r; j[0] = jx; j[1] = jy; j[2] = jz;
 }
 
+void orc_lattice_set_open_boundary(orc_lattice *L, const int *code, const double *val) {
+  const long n = (long)L->nx * L->ny * L->nz;
+  free(L->ob_code); free(L->ob_val); L->ob_code = NULL; L->ob_val = NULL;
+  if (!code) return;
+  long slots = 0;
+  for (long k = 0; k < n; k++) if (code[k] >= 0 && (code[k] >> 2) + 1 > slots) slots = (code[k] >> 2) + 1;
+  L->ob_code = (int *)malloc((size_t)n * sizeof(int));
+  memcpy(L->ob_code, code, (size_t)n * sizeof(int));
+  L->ob_val = (double *)malloc((size_t)(slots ? slots : 1) * 4 * sizeof(double));
+  if (slots) memcpy(L->ob_val, val, (size_t)slots * 4 * sizeof(double));
+}
+
+/* Zou-He completion with normal x on stored-form populations (f_i - t_i; the opposite populations of a pair share t_i, and
+ * the t_i of the nine c_x = 0 and twice the five outgoing populations add up to 1).  0N (kind even): the five populations
+ * with c_x = +1 are unknown,
+ *   rho = (S_0 + 2 S_-) / (1 - u_x)   [pressure nodes: rho given, u_x = 1 - (S_0 + 2 S_-) / rho, u_y = u_z = 0]
+ *   f(1,0,0) = f(-1,0,0) + rho u_x / 3,  f(1,+-1,0) = f(-1,-+1,0) + rho (u_x +- u_y) / 6 -+ N_y,  likewise z,
+ *   N_y = (sum over c = (0,1,.) - sum over c = (0,-1,.)) / 2 - rho u_y / 3;
+ * 0P mirrors it with rho = (S_0 + 2 S_+) / (1 + u_x).  Palabos is not in the tree: the operation order is this project's. */
+static void zou_he_x(double *f, int code, const double *val) {
+  const int kind = code & 3, neg = (kind & 1) == 0;
+  const double *v = val + 4 * (long)(code >> 2);
+  const double s0 = f[0] + f[2] + f[3] + f[8] + f[9] + f[11] + f[12] + f[17] + f[18];
+  const double sm = f[1] + f[4] + f[5] + f[6] + f[7];
+  const double sp = f[10] + f[13] + f[14] + f[15] + f[16];
+  const double known = s0 + 2.0 * (neg ? sm : sp) + 1.0;
+  double rho, ux, uy, uz;
+  if (kind < 2) {
+    ux = v[0]; uy = v[1]; uz = v[2];
+    rho = neg ? known / (1.0 - ux) : known / (1.0 + ux);
+  } else {
+    rho = v[3];
+    ux = neg ? 1.0 - known / rho : known / rho - 1.0;
+    uy = 0.0; uz = 0.0;
+  }
+  const double ny = 0.5 * ((f[11] + f[17] + f[18]) - (f[2] + f[8] + f[9])) - rho * uy / 3.0;
+  const double nz = 0.5 * ((f[12] + f[9] + f[17]) - (f[3] + f[8] + f[18])) - rho * uz / 3.0;
+  if (neg) {
+    f[10] = f[1] + rho * ux / 3.0;
+    f[13] = f[4] + rho * (ux + uy) / 6.0 - ny;
+    f[14] = f[5] + rho * (ux - uy) / 6.0 + ny;
+    f[15] = f[6] + rho * (ux + uz) / 6.0 - nz;
+    f[16] = f[7] + rho * (ux - uz) / 6.0 + nz;
+  } else {
+    f[1] = f[10] - rho * ux / 3.0;
+    f[4] = f[13] - rho * (ux + uy) / 6.0 + ny;
+    f[5] = f[14] - rho * (ux - uy) / 6.0 - ny;
+    f[6] = f[15] - rho * (ux + uz) / 6.0 + nz;
+    f[7] = f[16] - rho * (ux - uz) / 6.0 - nz;
+  }
+}
+static inline int open_code(const orc_lattice *L, long k) { return (L->ob_code && !L->mask[k]) ? L->ob_code[k] : -1; }
+
 /* Cell::computeVelocity for ExternalForceDynamics: u = j*invRho + F/2 (SURVEY A6;
  * used by core/hemoCellParticleField.cpp:833) */
 void orc_node_rho_u(const orc_lattice *L, long node, double *rho, double u[3]) {
   double rhoBar, j[3];
-  moments(L->f + node * ORC_Q, &rhoBar, j);
+  const int code = open_code(L, node);
+  if (code >= 0) {   /* an open-boundary node reports the moments of the completed populations: what its collide relaxes */
+    double g[ORC_Q];
+    for (int i = 0; i < ORC_Q; i++) g[i] = L->f[node * ORC_Q + i];
+    zou_he_x(g, code, L->ob_val);
+    moments(g, &rhoBar, j);
+  } else moments(L->f + node * ORC_Q, &rhoBar, j);
   double invRho = 1.0 / (1.0 + rhoBar);
   *rho = 1.0 + rhoBar;
   for (int d = 0; d < 3; d++) u[d] = j[d] * invRho + L->force[3 * node + d] / 2.0;
@@ -172,7 +231,11 @@ void orc_collide_stream(orc_lattice *L) {
   for (long k = 0; k < n; k++) {
     if (L->mask[k] >= 3) collide_moving_wall(L->ftmp + k * ORC_Q, L->wall_u[L->mask[k] - 3]);
     else if (L->mask[k]) collide_bounce_back(L->ftmp + k * ORC_Q);
-    else collide_guo_bgk(L->ftmp + k * ORC_Q, L->force + 3 * k, L->omega);
+    else {
+      const int code = open_code(L, k);
+      if (code >= 0) zou_he_x(L->ftmp + k * ORC_Q, code, L->ob_val);
+      collide_guo_bgk(L->ftmp + k * ORC_Q, L->force + 3 * k, L->omega);
+    }
   }
 #ifdef _OPENMP
 #pragma omp parallel for num_threads(L->nthreads) schedule(static)
@@ -233,7 +296,11 @@ void orc_collide_stream_fused(orc_lattice *L) {
         for (int i = 0; i < ORC_Q; i++) f[i] = src[k * ORC_Q + i];
         if (L->mask[k] >= 3) collide_moving_wall(f, L->wall_u[L->mask[k] - 3]);
         else if (L->mask[k]) collide_bounce_back(f);
-        else collide_guo_bgk(f, L->force + 3 * k, L->omega);
+        else {
+          const int code = open_code(L, k);
+          if (code >= 0) zou_he_x(f, code, L->ob_val);
+          collide_guo_bgk(f, L->force + 3 * k, L->omega);
+        }
         for (int i = 0; i < ORC_Q; i++) {
           int tx = x + orc_c[i][0], ty = y + orc_c[i][1], tz = z + orc_c[i][2];
           if (tx < 0 || tx >= nx) { if (L->periodic[0]) tx = (tx + nx) % nx; else continue; }

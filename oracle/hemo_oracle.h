@@ -36,6 +36,9 @@ typedef struct orc_lattice {
   int nthreads;            /* OpenMP threads used by orc_collide_stream (cpu_baseline)     */
   double wall_u[4][3];     /* velocity of the moving-wall classes 3..6                     */
   int fused;               /* cpu_baseline only: orc_collide_stream runs as ONE pass (orc_collide_stream_fused) */
+  /* Zou-He open boundaries with normal x (orc_lattice_set_open_boundary); null = none.  Kept at the end of the struct */
+  int *ob_code;            /* [n]: -1, or slot << 2 | kind (0 velocity 0N, 1 velocity 0P, 2 pressure 0N, 3 pressure 0P) */
+  double *ob_val;          /* [slots][4] {u_x, u_y, u_z, rho}                                                            */
 } orc_lattice;
 
 orc_lattice *orc_lattice_create(int nx, int ny, int nz, const int periodic[3], double omega);
@@ -44,6 +47,11 @@ void orc_lattice_set_mask(orc_lattice *L, const unsigned char *mask);
 void orc_lattice_init_equilibrium(orc_lattice *L, double rho, const double u[3]);
 void orc_lattice_set_force_uniform(orc_lattice *L, const double F[3]);
 void orc_lattice_set_force_box(orc_lattice *L, const int box[6], const double F[3]);
+/* Zou-He open boundaries, normal x: code [n] (-1 or slot << 2 | kind), val [slots][4] {u_x, u_y, u_z, rho}; both are copied
+ * (slots = the largest slot in code + 1); code = NULL removes them.  On fluid nodes with a code the unknown populations are
+ * completed between the bounce-back test and collide_guo_bgk in both collide forms, and in orc_node_rho_u (so the
+ * interpolation of orc_sim sees the completed moments).  Without a table every function gives its former bits. */
+void orc_lattice_set_open_boundary(orc_lattice *L, const int *code, const double *val);
 void orc_collide_stream(orc_lattice *L);
 /* the same step as one pass over the lattice (collide in registers, push to the neighbours in the second buffer):
  * same arithmetic, same bits, a third of the memory traffic -- the faster of the two CPU baselines of bench.py */

@@ -21,7 +21,7 @@ class Lattice(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("periodic", C.c_int * 3),
                 ("omega", C.c_double), ("f", c_double_p), ("ftmp", c_double_p), ("force", c_double_p),
                 ("mask", C.POINTER(C.c_ubyte)), ("nthreads", C.c_int), ("wall_u", (C.c_double * 3) * 4),
-                ("fused", C.c_int)]
+                ("fused", C.c_int), ("ob_code", c_int_p), ("ob_val", c_double_p)]
 
 
 class Params(C.Structure):
@@ -85,6 +85,7 @@ def load():
         "orc_lattice_init_equilibrium": (None, [LP, C.c_double, c_double_p]),
         "orc_lattice_set_force_uniform": (None, [LP, c_double_p]),
         "orc_lattice_set_force_box": (None, [LP, C.POINTER(C.c_int), c_double_p]),
+        "orc_lattice_set_open_boundary": (None, [LP, c_int_p, c_double_p]),
         "orc_collide_stream": (None, [LP]),
         "orc_collide_stream_fused": (None, [LP]),
         "orc_lattice_set_threads": (None, [LP, C.c_int]),
@@ -157,6 +158,16 @@ class OracleLattice:
         """setExternalVector on a sub-domain; box = inclusive (x0, x1, y0, y1, z0, z1)"""
         bb = (C.c_int * 6)(*[int(b) for b in box]); ff = np.array(F, dtype=np.float64)
         self.lib.orc_lattice_set_force_box(self.ptr, bb, dptr(ff))
+
+    def set_open_boundary(self, code, val):
+        """Zou-He open boundaries: code [n] or [nx][ny][nz] (-1 or slot << 2 | kind), val [slots][4]; None removes them"""
+        if code is None:
+            self.lib.orc_lattice_set_open_boundary(self.ptr, None, None)
+            return
+        cc = np.ascontiguousarray(code, dtype=np.int32).reshape(-1)
+        vv = np.ascontiguousarray(val, dtype=np.float64).reshape(-1, 4)
+        assert cc.size == self.n and (cc.max() >> 2) < len(vv)
+        self.lib.orc_lattice_set_open_boundary(self.ptr, cc.ctypes.data_as(c_int_p), dptr(vv))
 
     def set_threads(self, n):
         self.lib.orc_lattice_set_threads(self.ptr, n)

@@ -4,9 +4,10 @@ infrastructure only.
 State: the post-stream populations f[nx][ny][nz][19] in the stored form f_i - t_i (Palabos D3Q19 order), as
 Lattice.populations() returns them reshaped.  One step, in the order the collide kernel runs it on every node:
 
-1. bounce-back nodes (mask != 0) swap opposite populations;
+1. bounce-back nodes (mask != 0) swap opposite populations; moving-wall classes (mask 3..6) then add Ladd's momentum term;
 2. open-boundary nodes complete their unknown populations (complete() below);
-3. fluid nodes relax with the Guo-forced BGK (the oracle's collide_guo_bgk);
+3. fluid nodes relax with the Guo-forced BGK (the oracle's collide_guo_bgk) under the body force -- uniform, or that of the
+   last box holding the node -- plus the node's own force (the spread IBM force);
 4. stream: S'(x, i) = P(x - c_i, i), 0 where x - c_i lies outside a non-periodic axis.
 
 Every operation is an IEEE double operation in the kernel's order, so the GPU (built with -ffp-contract=off) agrees bit for
@@ -118,23 +119,57 @@ def collide_guo(f, F, omega):
     return f
 
 
-def step(S, mask, periodic, omega, body, ob_code=None, ob_val=None):
-    """one collide-stream.  S: [nx][ny][nz][19] post-stream; mask [nx][ny][nz] (0 fluid); body (3,);
-    ob_code [nx][ny][nz]: -1 or slot << 2 | kind; ob_val [slots][4].  Returns the next post-stream state."""
+def body_field(shape, body, boxes=None, box_forces=None):
+    """the body force of every node [nx][ny][nz][3]: `body`, or the force of the last box (inclusive x0, x1, y0, y1, z0, z1)
+    that holds the node -- region_force"""
+    b = np.empty(tuple(shape) + (3,))
+    b[...] = np.asarray(body, dtype=np.float64)
+    if boxes is not None:
+        for box, f in zip(boxes, box_forces):
+            x0, x1, y0, y1, z0, z1 = (int(v) for v in box)
+            b[max(x0, 0):x1 + 1, max(y0, 0):y1 + 1, max(z0, 0):z1 + 1] = np.asarray(f, dtype=np.float64)
+    return b
+
+
+def _complete_open(P, fluid, ob_code, ob_val):
+    """complete() on the fluid nodes of P [n][19] that carry a code (in place)"""
+    if ob_code is None:
+        return
+    code = np.asarray(ob_code).reshape(-1)
+    for kind in range(4):
+        sel = fluid & (code >= 0) & ((code & 3) == kind)
+        if sel.any():
+            P[sel] = complete(P[sel], kind, ob_val[code[sel] >> 2])
+
+
+def step(S, mask, periodic, omega, body, ob_code=None, ob_val=None, F=None, boxes=None, box_forces=None, wall_u=None):
+    """one collide-stream.  S: [nx][ny][nz][19] post-stream; mask [nx][ny][nz] (0 fluid, 3..6 moving-wall classes, any other
+    value bounce-back); body (3,); ob_code [nx][ny][nz]: -1 or slot << 2 | kind; ob_val [slots][4]; F [nx][ny][nz][3]: a
+    per-node force added to the body force (the kernel's bx + F0, in that order); boxes / box_forces: body-force boxes, the
+    last one holding a node wins; wall_u {class: (3,)}: velocities of the moving-wall classes, applied after the swap as
+    f[opp(i)] -= 6 t_i (c_i . u_w) for i = 1..18 in ascending order (the oracle's collide_moving_wall).
+    Returns the next post-stream state."""
     nx, ny, nz, _ = S.shape
     P = S.reshape(-1, 19).copy()
     m = mask.reshape(-1)
     wall = m != 0
     P[wall] = P[wall][:, OPP]
+    if wall_u is not None:
+        for cls, w in wall_u.items():
+            sel = m == cls
+            if not sel.any():
+                continue
+            w0, w1, w2 = (float(v) for v in w)
+            for q in range(1, 19):
+                cx, cy, cz = (float(v) for v in C[q])
+                c_u = cx * w0 + cy * w1 + cz * w2
+                P[sel, OPP[q]] = P[sel, OPP[q]] - 6.0 * T[q] * c_u
     fluid = ~wall
-    if ob_code is not None:
-        code = ob_code.reshape(-1)
-        for kind in range(4):
-            sel = fluid & (code >= 0) & ((code & 3) == kind)
-            if sel.any():
-                P[sel] = complete(P[sel], kind, ob_val[code[sel] >> 2])
-    F = np.broadcast_to(np.asarray(body, dtype=np.float64), (int(fluid.sum()), 3))
-    P[fluid] = collide_guo(P[fluid], F, omega)
+    _complete_open(P, fluid, ob_code, ob_val)
+    Ft = body_field((nx, ny, nz), body, boxes, box_forces).reshape(-1, 3)
+    if F is not None:
+        Ft = Ft + np.asarray(F, dtype=np.float64).reshape(-1, 3)
+    P[fluid] = collide_guo(P[fluid], Ft[fluid], omega)
     P = P.reshape(nx, ny, nz, 19)
     out = np.zeros_like(P)
     for q in range(19):
@@ -149,6 +184,43 @@ def step(S, mask, periodic, omega, body, ob_code=None, ob_val=None):
                 src[tuple(idx)] = 0.0
         out[:, :, :, q] = src
     return out
+
+
+def observe(S, mask, periodic, body, F=None, ob_code=None, ob_val=None, boxes=None, box_forces=None):
+    """what the observers report on the post-stream state S: per node rho [nx][ny][nz], u = j / rho + (body + F) / 2
+    [..][3] and the off-equilibrium momentum flux Pi_neq [..][6] (xx, xy, xz, yy, yz, zz), taken AFTER the completion on
+    fluid open-boundary nodes -- the populations the next collide relaxes.  So a velocity node shows u_bc + F / 2 and a
+    pressure node its prescribed density.  Plain moments everywhere else, bounce-back nodes included.  IEEE double in the
+    order of the kernels' moments(): ascending q, zero components skipped.  `periodic` is unused (S is the gathered state)
+    and kept so that the call reads like step()."""
+    nx, ny, nz, _ = S.shape
+    f = S.reshape(-1, 19).copy()
+    _complete_open(f, mask.reshape(-1) == 0, ob_code, ob_val)
+    n = f.shape[0]
+    r = np.zeros(n); j = [np.zeros(n) for _ in range(3)]
+    pi = {k: np.zeros(n) for k in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))}
+    for q in range(19):
+        r = r + f[:, q]
+        for d in range(3):
+            if C[q][d] == 1: j[d] = j[d] + f[:, q]
+            elif C[q][d] == -1: j[d] = j[d] + (-f[:, q])
+        for (a, b) in pi:
+            cc = C[q][a] * C[q][b]
+            if cc == 1: pi[(a, b)] = pi[(a, b)] + f[:, q]
+            elif cc == -1: pi[(a, b)] = pi[(a, b)] + (-f[:, q])
+    invRho = 1.0 / (1.0 + r)
+    Ft = body_field((nx, ny, nz), body, boxes, box_forces).reshape(-1, 3)
+    if F is not None:
+        Ft = Ft + np.asarray(F, dtype=np.float64).reshape(-1, 3)
+    u = np.stack([j[d] * invRho + Ft[:, d] / 2.0 for d in range(3)], axis=1)
+    cs2 = 1.0 / 3.0
+    out = np.empty((n, 6))
+    for k, (a, b) in enumerate(pi):
+        v = pi[(a, b)] - invRho * j[a] * j[b]
+        if a == b:
+            v = v - cs2 * r
+        out[:, k] = v
+    return (1.0 + r).reshape(nx, ny, nz), u.reshape(nx, ny, nz, 3), out.reshape(nx, ny, nz, 6)
 
 
 def pipe_radius(fluid_area):
