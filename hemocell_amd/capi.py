@@ -97,6 +97,9 @@ SIGNATURES = {
     "hcl_lees_edwards_state": (C.c_int, [VP, c_double_p]),
     "hcl_open_boundary_add": (C.c_int, [VP, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p]),
     "hcl_open_boundary_add_box": (C.c_int, [VP, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p]),
+    "hcl_open_boundary_add_axis": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p]),
+    "hcl_open_boundary_add_box_axis": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p]),
+    "hcl_open_boundary_axes": (C.c_int, [VP, c_int_p, C.c_int, c_int_p]),
     "hcl_open_boundary_clear": (C.c_int, [VP]),
     "hcl_open_boundary_slots": (C.c_int, [VP, c_int_p, C.c_int, c_int_p]),
     "hcl_open_boundary_set_velocity": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int]),

@@ -91,47 +91,80 @@ __device__ __forceinline__ void region_force(const BodyRegions &r, int xg, int y
   }
 }
 
-// Zou-He completion with normal x on the gathered populations f (stored form f - t_q; the opposite populations of a pair share
-// t_q, so the completed ones are formed in that form directly).  code & 3: 0 = velocity 0N, 1 = velocity 0P, 2 = pressure 0N,
-// 3 = pressure 0P.  0N completes the five populations with c_x = +1 from their opposites:
+// Zou-He completion on the gathered populations f (stored form f - t_q; the opposite populations of a pair share t_q, so the
+// completed ones are formed in that form directly).  With normal x (AXIS 0), code & 3: 0 = velocity 0N, 1 = velocity 0P,
+// 2 = pressure 0N, 3 = pressure 0P.  0N completes the five populations with c_x = +1 from their opposites:
 //   rho = (S_0 + 2 S_-) / (1 - u_x) with the real sums S (the t_q of the nine c_x = 0 and twice the five c_x = -1 ones add 1),
 //   f(1,0,0) = f(-1,0,0) + rho u_x / 3,  f(1,+-1,0) = f(-1,-+1,0) + rho (u_x +- u_y) / 6 -+ N_y,  likewise z,
 //   N_y = (sum f over c = (0,1,.) - sum over (0,-1,.)) / 2 - rho u_y / 3;
 // 0P mirrors it.  Pressure nodes take rho and u_x = 1 - (S_0 + 2 S_-) / rho (0N), (S_0 + 2 S_+) / rho - 1 (0P), u_y = u_z = 0.
-// tests/open_boundary_ref.py restates this operation for operation.  The collide calls it on fluid nodes before it relaxes, and
-// every observer of an open lattice (rho_u, pi_neq, plane velocity, statistics, the IBM node velocity) before it takes moments.
-__device__ __forceinline__ void zou_he_x(double f[HC_Q], int code, const double *__restrict__ val) {
+// Normal y (AXIS 1) and z (AXIS 2) are the x completion on swapped populations: axis a exchanges the roles of x and a, so
+// population i stands where zh_perm(a, i) -- the direction c_i with those two components exchanged, an involution -- stands
+// for x, the normal velocity is u[a] and the tangential pair is (u_x, u_z) for y and (u_y, u_x) for z.  Every sum keeps the
+// operand order of the x completion; the indices are template constants, so f stays in registers.
+// tests/open_boundary_ref.py restates the x completion operation for operation and tests/open_boundary_axis_ref.py the
+// permutation around it.  The collide calls it on fluid nodes before it relaxes, and every observer of an open lattice
+// (rho_u, pi_neq, plane velocity, statistics, the IBM node velocity) before it takes moments.
+//
+// ob_code[node] = -1, or axis << 29 | slot << 2 | kind: the axis sits above the slot, so a node with normal x carries the code
+// it always carried and slots stay below 1 << 27 (HC_OB_MAX_SLOTS).
+constexpr int HC_OB_AXIS_SHIFT = 29;
+constexpr int HC_OB_MAX_SLOTS = 1 << 27;
+__host__ __device__ constexpr int zh_perm(int axis, int i) {
+  constexpr int cx[HC_Q] = HC_CX, cy[HC_Q] = HC_CY, cz[HC_Q] = HC_CZ;
+  const int x = axis == 1 ? cy[i] : axis == 2 ? cz[i] : cx[i];
+  const int y = axis == 1 ? cx[i] : cy[i];
+  const int z = axis == 2 ? cx[i] : cz[i];
+  for (int j = 0; j < HC_Q; j++) if (cx[j] == x && cy[j] == y && cz[j] == z) return j;
+  return -1;
+}
+template <int AXIS, int I> inline constexpr int ZH = zh_perm(AXIS, I);
+static_assert(ZH<0, 7> == 7 && ZH<1, 1> == 2 && ZH<1, 5> == 14 && ZH<1, 15> == 17 && ZH<2, 1> == 3 && ZH<2, 7> == 16 && ZH<2, 13> == 17, "zh_perm");
+
+template <int AXIS>
+__device__ __forceinline__ void zou_he(double f[HC_Q], int code, const double *__restrict__ val) {
+#define G(I) f[ZH<AXIS, I>]
   const int kind = code & 3;
   const long slot = code >> 2;
-  const double s0 = f[0] + f[2] + f[3] + f[8] + f[9] + f[11] + f[12] + f[17] + f[18];
-  const double sm = f[1] + f[4] + f[5] + f[6] + f[7];
-  const double sp = f[10] + f[13] + f[14] + f[15] + f[16];
-  const bool neg = (kind & 1) == 0;   // 0N
+  const double s0 = G(0) + G(2) + G(3) + G(8) + G(9) + G(11) + G(12) + G(17) + G(18);
+  const double sm = G(1) + G(4) + G(5) + G(6) + G(7);
+  const double sp = G(10) + G(13) + G(14) + G(15) + G(16);
+  const bool neg = (kind & 1) == 0;   // N
   const double s_out = neg ? sm : sp;
   const double known = s0 + 2.0 * s_out + 1.0;
   double rho, ux, uy, uz;
   if (kind < 2) {
-    ux = val[4 * slot]; uy = val[4 * slot + 1]; uz = val[4 * slot + 2];
+    ux = val[4 * slot + AXIS]; uy = val[4 * slot + (AXIS == 1 ? 0 : 1)]; uz = val[4 * slot + (AXIS == 2 ? 0 : 2)];
     rho = neg ? known / (1.0 - ux) : known / (1.0 + ux);
   } else {
     rho = val[4 * slot + 3];
     ux = neg ? 1.0 - known / rho : known / rho - 1.0;
     uy = 0.0; uz = 0.0;
   }
-  const double ny = 0.5 * ((f[11] + f[17] + f[18]) - (f[2] + f[8] + f[9])) - rho * uy / 3.0;
-  const double nz = 0.5 * ((f[12] + f[9] + f[17]) - (f[3] + f[8] + f[18])) - rho * uz / 3.0;
+  const double ny = 0.5 * ((G(11) + G(17) + G(18)) - (G(2) + G(8) + G(9))) - rho * uy / 3.0;
+  const double nz = 0.5 * ((G(12) + G(9) + G(17)) - (G(3) + G(8) + G(18))) - rho * uz / 3.0;
   if (neg) {
-    f[10] = f[1] + rho * ux / 3.0;
-    f[13] = f[4] + rho * (ux + uy) / 6.0 - ny;
-    f[14] = f[5] + rho * (ux - uy) / 6.0 + ny;
-    f[15] = f[6] + rho * (ux + uz) / 6.0 - nz;
-    f[16] = f[7] + rho * (ux - uz) / 6.0 + nz;
+    G(10) = G(1) + rho * ux / 3.0;
+    G(13) = G(4) + rho * (ux + uy) / 6.0 - ny;
+    G(14) = G(5) + rho * (ux - uy) / 6.0 + ny;
+    G(15) = G(6) + rho * (ux + uz) / 6.0 - nz;
+    G(16) = G(7) + rho * (ux - uz) / 6.0 + nz;
   } else {
-    f[1] = f[10] - rho * ux / 3.0;
-    f[4] = f[13] - rho * (ux + uy) / 6.0 + ny;
-    f[5] = f[14] - rho * (ux - uy) / 6.0 - ny;
-    f[6] = f[15] - rho * (ux + uz) / 6.0 + nz;
-    f[7] = f[16] - rho * (ux - uz) / 6.0 - nz;
+    G(1) = G(10) - rho * ux / 3.0;
+    G(4) = G(13) - rho * (ux + uy) / 6.0 + ny;
+    G(5) = G(14) - rho * (ux - uy) / 6.0 - ny;
+    G(6) = G(15) - rho * (ux + uz) / 6.0 + nz;
+    G(7) = G(16) - rho * (ux - uz) / 6.0 - nz;
+  }
+#undef G
+}
+
+// the completion of an open-boundary node (code >= 0) along the axis its code names; uniform per node
+__device__ __forceinline__ void zou_he_node(double f[HC_Q], int code, const double *__restrict__ val) {
+  switch (code >> HC_OB_AXIS_SHIFT) {
+    case 0: zou_he<0>(f, code, val); break;
+    case 1: zou_he<1>(f, code & ((1 << HC_OB_AXIS_SHIFT) - 1), val); break;
+    default: zou_he<2>(f, code & ((1 << HC_OB_AXIS_SHIFT) - 1), val); break;
   }
 }
 #endif
@@ -183,8 +216,9 @@ struct hc_lattice {
   bool le_on = false;
   double le_D = 0.0, le_d = 0.0, le_v_top = 0.0, le_v_bottom = 0.0;
   double *le_buf = nullptr;   // [2][19][nx ny] post-pass values of the top and bottom layers
-  // Zou-He open boundaries, normal x (hcl_open_boundary_add): ob_code[node] = -1 for every other node, else slot << 2 | kind
-  // (HC_OB_*); ob_val[slot] = {u_x, u_y, u_z, rho}.  The collide runs its open-boundary instantiation while ob_n > 0.
+  // Zou-He open boundaries (hcl_open_boundary_add_axis): ob_code[node] = -1 for every other node, else
+  // axis << 29 | slot << 2 | kind (zou_he_node above); ob_val[slot] = {u_x, u_y, u_z, rho} in lattice axes.  The collide runs
+  // its open-boundary instantiation while ob_n > 0.
   int *ob_code = nullptr;           // [npad], device
   std::vector<int> ob_hcode;        // host copy
   double *ob_val = nullptr;         // [ob_cap][4], device

@@ -102,7 +102,7 @@ struct PopView {
   hc::BodyRegions reg;
 };
 // lattices with Zou-He open boundaries (hc_lattice::ob_n > 0) run the OPEN instantiations of the interpolation kernels: the
-// gathered populations of a fluid open-boundary node are completed (zou_he_x, as the collide is about to) before the moments
+// gathered populations of a fluid open-boundary node are completed (zou_he_node, as the collide is about to) before the moments
 // are taken.  Every other lattice keeps PopView, its kernel-argument block and its code.
 struct OpenPopView : PopView { const int *ob_code; const double *ob_val; };
 template <bool OPEN> using Pops = std::conditional_t<OPEN, OpenPopView, PopView>;
@@ -154,7 +154,7 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const Pops<OPEN>
   if constexpr (OPEN) {
     if (v.mask[node] == 0) {
       const int code = pv.ob_code[node];
-      if (code >= 0) hc::zou_he_x(f, code, pv.ob_val);
+      if (code >= 0) hc::zou_he_node(f, code, pv.ob_val);
     }
 #define M(Q, CX, CY, CZ)                                                              \
     r += f[Q];                                                                        \

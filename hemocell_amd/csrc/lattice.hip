@@ -54,7 +54,7 @@ struct LatArgs {
 
 // the arguments of the open-boundary instantiation: the other instantiations keep LatArgs, and with it their kernel-argument block
 struct OpenArgs : LatArgs {
-  const int *ob_code;    // Zou-He open boundaries: -1 or slot << 2 | kind
+  const int *ob_code;    // Zou-He open boundaries: -1 or axis << 29 | slot << 2 | kind
   const double *ob_val;  // [slot][4] {u_x, u_y, u_z, rho}
 };
 template <bool OPEN> using Args = std::conditional_t<OPEN, OpenArgs, LatArgs>;
@@ -133,7 +133,7 @@ __device__ __forceinline__ void complete_open(const Args<OPEN> &a, long node, do
   if constexpr (OPEN) {
     if (a.mask[node] == 0) {
       const int code = a.ob_code[node];
-      if (code >= 0) zou_he_x(f, code, a.ob_val);
+      if (code >= 0) zou_he_node(f, code, a.ob_val);
     }
   }
 }
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(Args<OPEN> a) {
     }
     if constexpr (OPEN) {
       const int code = a.ob_code[node];
-      if (code >= 0) zou_he_x(f, code, a.ob_val);
+      if (code >= 0) zou_he_node(f, code, a.ob_val);
     }
     collide_guo(f, Fx, Fy, Fz, a.omega);
   }
@@ -1007,7 +1007,7 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]) {
   return HC_OK;
 }
 
-// ---- Zou-He open boundaries (the completion is zou_he_x inside the collide)
+// ---- Zou-He open boundaries (the completion is zou_he_node inside the collide)
 // room for `need` slots; the slots from ob_n on start at u = 0, rho = 1
 static int ob_grow(hc_lattice *L, int need) {
   if (need <= L->ob_cap) {
@@ -1057,27 +1057,29 @@ static int ob_set(hc_lattice *L, const char *what, int first, int n, const doubl
   return HC_OK;
 }
 
-int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot) {
-  HC_REQUIRE(L && (n == 0 || nodes), "hcl_open_boundary_add: null pointer");
-  HC_REQUIRE(L->n_slabs == 1, "hcl_open_boundary_add: open boundaries need the whole domain on one GPU (n_slabs = 1)");
-  HC_REQUIRE(kind == HC_OB_VELOCITY || kind == HC_OB_PRESSURE, "hcl_open_boundary_add: kind must be HC_OB_VELOCITY or HC_OB_PRESSURE");
-  HC_REQUIRE(orientation == -1 || orientation == 1, "hcl_open_boundary_add: orientation must be -1 (0N) or +1 (0P)");
-  HC_REQUIRE(n >= 0 && (long)L->ob_n + n < (1L << 28), "hcl_open_boundary_add: too many nodes");
+// who: the entry point the caller used, for the messages
+static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int orientation, const int *nodes, int n, int *first_slot) {
+  HC_REQUIRE(L && (n == 0 || nodes), who + ": null pointer");
+  HC_REQUIRE(L->n_slabs == 1, who + ": open boundaries need the whole domain on one GPU (n_slabs = 1)");
+  HC_REQUIRE(kind == HC_OB_VELOCITY || kind == HC_OB_PRESSURE, who + ": kind must be HC_OB_VELOCITY or HC_OB_PRESSURE");
+  HC_REQUIRE(orientation == -1 || orientation == 1, who + ": orientation must be -1 (N) or +1 (P)");
+  HC_REQUIRE(axis >= 0 && axis <= 2, who + ": axis must be 0, 1 or 2");
+  HC_REQUIRE(n >= 0 && (long)L->ob_n + n < (long)HC_OB_MAX_SLOTS, who + ": too many nodes");
   // The Lees-Edwards pass rewrites the post-stream populations of its z layers from plain moments of gathered populations; what
   // it should read and leave on a node whose populations the collide completes is not defined, so the two do not share a lattice
-  HC_REQUIRE(!L->le_on, "hcl_open_boundary_add: the lattice has a Lees-Edwards boundary; open boundaries and Lees-Edwards do not combine");
+  HC_REQUIRE(!L->le_on, who + ": the lattice has a Lees-Edwards boundary; open boundaries and Lees-Edwards do not combine");
   // a node holds one slot: declaring it again (in this call or an earlier one) would orphan the first slot and let the second
   // declaration win silently, so it is refused and nothing is changed
   {
     std::vector<size_t> seen((size_t)n);
     for (int i = 0; i < n; i++) {
       const int *c = nodes + 3 * i;
-      HC_REQUIRE(c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz, "hcl_open_boundary_add: node outside the lattice");
+      HC_REQUIRE(c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz, who + ": node outside the lattice");
       seen[(size_t)i] = (size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2];
-      HC_REQUIRE(!L->ob_code || L->ob_hcode[seen[(size_t)i]] < 0, "hcl_open_boundary_add: node declared twice (it is an open-boundary node already; hcl_open_boundary_clear removes all)");
+      HC_REQUIRE(!L->ob_code || L->ob_hcode[seen[(size_t)i]] < 0, who + ": node declared twice (it is an open-boundary node already; hcl_open_boundary_clear removes all)");
     }
     std::sort(seen.begin(), seen.end());
-    HC_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "hcl_open_boundary_add: node declared twice (listed more than once)");
+    HC_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), who + ": node declared twice (listed more than once)");
   }
   if (first_slot) *first_slot = L->ob_n;
   if (n == 0) return HC_OK;
@@ -1089,7 +1091,7 @@ int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *n
   const int k = (kind == HC_OB_PRESSURE ? 2 : 0) + (orientation > 0 ? 1 : 0);
   for (int i = 0; i < n; i++) {
     const int *c = nodes + 3 * i;
-    L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]] = ((L->ob_n + i) << 2) | k;
+    L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]] = (axis << HC_OB_AXIS_SHIFT) | ((L->ob_n + i) << 2) | k;
   }
   L->ob_n += n;
   HC_HIP(hipMemcpyAsync(L->ob_code, L->ob_hcode.data(), L->npad * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
@@ -1097,17 +1099,33 @@ int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *n
   return HC_OK;
 }
 
-int hcl_open_boundary_add_box(hc_lattice *L, int kind, int orientation, const int box[6], int *first_slot, int *n_nodes) {
-  HC_REQUIRE(L && box, "hcl_open_boundary_add_box: null pointer");
-  HC_REQUIRE(box[0] <= box[1] && box[2] <= box[3] && box[4] <= box[5], "hcl_open_boundary_add_box: empty box");
+int hcl_open_boundary_add_axis(hc_lattice *L, int kind, int axis, int orientation, const int *nodes, int n, int *first_slot) {
+  return ob_add("hcl_open_boundary_add_axis", L, kind, axis, orientation, nodes, n, first_slot);
+}
+
+int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot) {
+  return ob_add("hcl_open_boundary_add", L, kind, 0, orientation, nodes, n, first_slot);
+}
+
+static int ob_add_box(const std::string &who, hc_lattice *L, int kind, int axis, int orientation, const int box[6], int *first_slot, int *n_nodes) {
+  HC_REQUIRE(L && box, who + ": null pointer");
+  HC_REQUIRE(box[0] <= box[1] && box[2] <= box[3] && box[4] <= box[5], who + ": empty box");
   std::vector<int> nodes;
   for (int x = box[0]; x <= box[1]; x++)
     for (int y = box[2]; y <= box[3]; y++)
       for (int z = box[4]; z <= box[5]; z++) { nodes.push_back(x); nodes.push_back(y); nodes.push_back(z); }
   const int n = (int)(nodes.size() / 3);
-  const int rc = hcl_open_boundary_add(L, kind, orientation, nodes.data(), n, first_slot);
+  const int rc = ob_add(who, L, kind, axis, orientation, nodes.data(), n, first_slot);
   if (rc == HC_OK && n_nodes) *n_nodes = n;
   return rc;
+}
+
+int hcl_open_boundary_add_box_axis(hc_lattice *L, int kind, int axis, int orientation, const int box[6], int *first_slot, int *n_nodes) {
+  return ob_add_box("hcl_open_boundary_add_box_axis", L, kind, axis, orientation, box, first_slot, n_nodes);
+}
+
+int hcl_open_boundary_add_box(hc_lattice *L, int kind, int orientation, const int box[6], int *first_slot, int *n_nodes) {
+  return ob_add_box("hcl_open_boundary_add_box", L, kind, 0, orientation, box, first_slot, n_nodes);
 }
 
 int hcl_open_boundary_clear(hc_lattice *L) {
@@ -1128,9 +1146,23 @@ int hcl_open_boundary_slots(const hc_lattice *L, const int *nodes, int n, int *s
     int s = -1;
     if (L->ob_code && c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz) {
       const int code = L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]];
-      s = code < 0 ? -1 : code >> 2;
+      s = code < 0 ? -1 : (code & ((1 << HC_OB_AXIS_SHIFT) - 1)) >> 2;
     }
     slots[i] = s;
+  }
+  return HC_OK;
+}
+
+int hcl_open_boundary_axes(const hc_lattice *L, const int *nodes, int n, int *axes) {
+  HC_REQUIRE(L && n >= 0 && (n == 0 || (nodes && axes)), "hcl_open_boundary_axes: bad arguments");
+  for (int i = 0; i < n; i++) {
+    const int *c = nodes + 3 * i;
+    int a = -1;
+    if (L->ob_code && c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz) {
+      const int code = L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]];
+      a = code < 0 ? -1 : code >> HC_OB_AXIS_SHIFT;
+    }
+    axes[i] = a;
   }
   return HC_OK;
 }

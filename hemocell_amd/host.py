@@ -149,7 +149,7 @@ class Lattice:
         """density of the Zou-He pressure nodes of a box or an [n][3] node list: one value or one per node"""
         self._set_open(where, rho, 1, self.lib.hcl_open_boundary_set_density)
 
-    # Zou-He open boundaries with normal x (hcl_open_boundary_*).  Boxes are inclusive (x0, x1, y0, y1, z0, z1) in local
+    # Zou-He open boundaries (hcl_open_boundary_*), first with normal x.  Boxes are inclusive (x0, x1, y0, y1, z0, z1) in local
     # node coordinates; each call returns (first_slot, n): the nodes hold the slots first_slot .. first_slot + n - 1 in
     # box order (x outermost, z innermost)
     def addVelocityBoundary0N(self, box):
@@ -164,13 +164,46 @@ class Lattice:
     def addPressureBoundary0P(self, box):
         return self._add_open_box(1, 1, box)
 
-    def addOpenBoundaryNodes(self, kind, orientation, nodes):
-        """kind 0 = velocity, 1 = pressure; orientation -1 = 0N, +1 = 0P; nodes [n][3]: returns the first slot"""
+    # ... and with normal y (1N / 1P) and z (2N / 2P): the same completion with the roles of x and the axis exchanged
+    def addVelocityBoundary1N(self, box):
+        return self._add_open_box(0, -1, box, 1)
+
+    def addVelocityBoundary1P(self, box):
+        return self._add_open_box(0, 1, box, 1)
+
+    def addPressureBoundary1N(self, box):
+        return self._add_open_box(1, -1, box, 1)
+
+    def addPressureBoundary1P(self, box):
+        return self._add_open_box(1, 1, box, 1)
+
+    def addVelocityBoundary2N(self, box):
+        return self._add_open_box(0, -1, box, 2)
+
+    def addVelocityBoundary2P(self, box):
+        return self._add_open_box(0, 1, box, 2)
+
+    def addPressureBoundary2N(self, box):
+        return self._add_open_box(1, -1, box, 2)
+
+    def addPressureBoundary2P(self, box):
+        return self._add_open_box(1, 1, box, 2)
+
+    def addOpenBoundaryNodes(self, kind, orientation, nodes, axis=0):
+        """kind 0 = velocity, 1 = pressure; orientation -1 = N, +1 = P; nodes [n][3]; axis 0, 1, 2: returns the first slot"""
         nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
         first = C.c_int()
-        check(self.lib.hcl_open_boundary_add(self.ptr, int(kind), int(orientation), nn.ctypes.data_as(C.POINTER(C.c_int)),
-                                             len(nn), C.byref(first)))
+        check(self.lib.hcl_open_boundary_add_axis(self.ptr, int(kind), int(axis), int(orientation),
+                                                  nn.ctypes.data_as(C.POINTER(C.c_int)), len(nn), C.byref(first)))
         return first.value
+
+    def openBoundaryAxes(self, nodes):
+        """the axis (0, 1, 2) on which each node of [n][3] was declared, or -1"""
+        nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
+        out = np.empty(len(nn), np.int32)
+        check(self.lib.hcl_open_boundary_axes(self.ptr, nn.ctypes.data_as(C.POINTER(C.c_int)), len(nn),
+                                              out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out
 
     def clearOpenBoundaries(self):
         check(self.lib.hcl_open_boundary_clear(self.ptr))
@@ -203,10 +236,10 @@ class Lattice:
         check(self.lib.hcl_plane_velocity(self.ptr, int(x), ii.ctypes.data_as(C.POINTER(C.c_int)), len(ii), out.ctypes.data, 0))
         return out
 
-    def _add_open_box(self, kind, orientation, box):
+    def _add_open_box(self, kind, orientation, box, axis=0):
         bb = (C.c_int * 6)(*[int(v) for v in box])
         first, n = C.c_int(), C.c_int()
-        check(self.lib.hcl_open_boundary_add_box(self.ptr, int(kind), int(orientation), bb, C.byref(first), C.byref(n)))
+        check(self.lib.hcl_open_boundary_add_box_axis(self.ptr, int(kind), int(axis), int(orientation), bb, C.byref(first), C.byref(n)))
         return first.value, n.value
 
     def _set_open(self, where, values, nc, fn):

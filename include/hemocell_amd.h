@@ -160,7 +160,7 @@ int hcl_set_lees_edwards_displacement(hc_lattice *L, double D, double d_per_iter
 int hcl_lees_edwards_apply(hc_lattice *L);
 /* out = {D, v_top, v_bottom, d_per_iteration} */
 int hcl_lees_edwards_state(const hc_lattice *L, double out[4]);
-/* Zou-He open boundaries with normal x (Palabos' addVelocityBoundary0N/0P, addPressureBoundary0N/0P).  kind: HC_OB_VELOCITY
+/* Zou-He open boundaries, here with normal x (Palabos' addVelocityBoundary0N/0P, addPressureBoundary0N/0P).  kind: HC_OB_VELOCITY
  * (u given, rho from the known populations) or HC_OB_PRESSURE (rho given, u = (u_x, 0, 0) from them); orientation -1 = 0N
  * (the populations with c_x = +1 are completed), +1 = 0P (c_x = -1).  The completion runs inside the collide, between the
  * gather and the Guo-forced BGK, on the post-stream populations of the declared nodes; their mask stays fluid, and nodes
@@ -178,9 +178,21 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]);
 int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot);
 /* every node of the inclusive local box {x0, x1, y0, y1, z0, z1}, x outermost and z innermost */
 int hcl_open_boundary_add_box(hc_lattice *L, int kind, int orientation, const int box[6], int *first_slot, int *n_nodes);
+/* The same with the normal along any axis: axis 0, 1 or 2 (x, y, z; anything else is HC_ERR_ARG) -- Palabos'
+ * addVelocityBoundary1N ... addPressureBoundary2P.  orientation -1 completes the populations with c_axis = +1, +1 those with
+ * c_axis = -1.  The completion on axis a is the x completion with the roles of x and a exchanged: the normal velocity is
+ * u[a], a pressure node takes the prescribed rho, the normal velocity from the known populations and tangential velocity 0.
+ * The values of a slot stay {u_x, u_y, u_z, rho} in lattice axes whatever the axis.  Every rule above holds unchanged (one
+ * slot per node, on whatever axis it was declared; n_slabs = 1; no Lees-Edwards; bounce-back nodes stay bounce-back), and
+ * so do the observers.  Nodes where two open faces meet get no dynamics of their own: they are the caller's to make walls.
+ * hcl_open_boundary_add and _add_box are these with axis 0.  A lattice holds fewer than 2^27 open-boundary nodes. */
+int hcl_open_boundary_add_axis(hc_lattice *L, int kind, int axis, int orientation, const int *nodes, int n, int *first_slot);
+int hcl_open_boundary_add_box_axis(hc_lattice *L, int kind, int axis, int orientation, const int box[6], int *first_slot, int *n_nodes);
 int hcl_open_boundary_clear(hc_lattice *L);
 /* slots[i] = the slot of local node nodes[i], or -1 */
 int hcl_open_boundary_slots(const hc_lattice *L, const int *nodes, int n, int *slots);
+/* axes[i] = the axis (0, 1, 2) on which local node nodes[i] was declared, or -1 */
+int hcl_open_boundary_axes(const hc_lattice *L, const int *nodes, int n, int *axes);
 /* setBoundaryVelocity / setBoundaryDensity on slots first_slot .. first_slot + n - 1: u [n][3], rho [n], read from the
  * device (on_device != 0, ordered on the library's stream) or from the host */
 int hcl_open_boundary_set_velocity(hc_lattice *L, int first_slot, int n, const double *u, int on_device);
