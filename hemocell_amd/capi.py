@@ -106,6 +106,11 @@ SIGNATURES = {
     "hcl_open_boundary_set_density": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int]),
     "hcl_open_boundary_values": (C.c_int, [VP, C.c_int, C.c_int, c_double_p]),
     "hcl_plane_velocity": (C.c_int, [VP, C.c_int, c_int_p, C.c_int, VP, C.c_int]),
+    "hcl_plane_velocity_axis": (C.c_int, [VP, C.c_int, C.c_int, c_int_p, C.c_int, VP, C.c_int]),
+    "hcl_preinlet_create": (C.c_int, [C.POINTER(VP), VP, VP, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int]),
+    "hcl_preinlet_apply": (C.c_int, [VP]),
+    "hcl_preinlet_iterate": (C.c_int, [VP, C.c_int]),
+    "hcl_preinlet_destroy": (C.c_int, [VP]),
     "hcl_collide_stream_part": (C.c_int, [VP, C.c_int]),
     "hcl_step_end": (C.c_int, [VP]),
     "hcl_download_populations": (C.c_int, [VP, c_double_p]),

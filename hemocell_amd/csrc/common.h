@@ -223,6 +223,7 @@ struct hc_lattice {
   std::vector<int> ob_hcode;        // host copy
   double *ob_val = nullptr;         // [ob_cap][4], device
   int ob_n = 0, ob_cap = 0;
+  long ob_epoch = 0;                // counts hcl_open_boundary_clear: a pre-inlet coupling (hc_preinlet) made before one is stale
   int *ob_list = nullptr; int ob_list_cap = 0;   // staging of hcl_plane_velocity's node list
   double *ob_out = nullptr; int ob_out_cap = 0;  // ... and of its output when the caller's buffer is on the host
 };

@@ -383,29 +383,63 @@ __global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
   pi[o + 5] = zz - invRho * j2 * j2 - cs2 * rhoBar;
 }
 
-// Cell::computeVelocity on listed nodes of one plane with the body force alone (hcl_plane_velocity); out [n][3]
+// Cell::computeVelocity with the body force alone on node P of the plane coordinate[AXIS] == PLANE of the lattice `a`, into the
+// new variables u0, u1, u2.  P is the node's offset with the axis removed: y * nz + z, x * nz + z, x * ny + y for AXIS 0, 1, 2
+// (x local).  Bounce-back nodes give 0.  This is the one statement of the arithmetic: the plane-velocity kernels and the
+// pre-inlet coupling kernel below all expand it, so they cannot drift apart.  It is a macro and not a __device__ function
+// because the compiler inlines the helpers in another order through an intermediate function, and plane_velocity_kernel<false>
+// and <true> then come out with other scalar registers than before; expanded in place they are the code
+// they were, line for line.
+#define PLANE_NODE_VELOCITY(AXIS, PLANE, P)                                                       \
+  const int p = (P);                                                                              \
+  const int x = AXIS == 0 ? (PLANE) : AXIS == 1 ? p / a.nz : p / a.ny;                            \
+  const int y = AXIS == 0 ? p / a.nz : AXIS == 1 ? (PLANE) : p - x * a.ny;                        \
+  const int z = AXIS == 0 ? p - y * a.nz : AXIS == 1 ? p - x * a.nz : (PLANE);                    \
+  const long node = (long)(x + HALO) * a.xs + (AXIS == 0 ? p : y * a.nz + z);                     \
+  double u0 = 0.0, u1 = 0.0, u2 = 0.0;                                                            \
+  if (a.mask[node] == 0) {                                                                        \
+    const Nbr nb = neighbours(a, x, y, z);                                                        \
+    double f[HC_Q];                                                                               \
+    pull(a.fin, a.qs, node, nb, f);                                                               \
+    complete_open<OPEN>(a, node, f);                                                              \
+    double rhoBar, j0, j1, j2;                                                                    \
+    moments(f, rhoBar, j0, j1, j2);                                                               \
+    const double invRho = 1.0 / (1.0 + rhoBar);                                                   \
+    double bx, by, bz;                                                                            \
+    body_at(a, x, y, z, bx, by, bz);                                                              \
+    u0 = j0 * invRho + bx / 2.0; u1 = j1 * invRho + by / 2.0; u2 = j2 * invRho + bz / 2.0;        \
+  }
+
+// hcl_plane_velocity: listed nodes of one x plane; out [n][3]
 template <bool OPEN = false>
-__global__ void plane_velocity_kernel(Args<OPEN> a, int x, const int *yz, int n, double *out) {
+__global__ void plane_velocity_kernel(Args<OPEN> a, int plane, const int *yz, int n, double *out) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
-  const int p = yz[k];
-  const int y = p / a.nz, z = p - y * a.nz;
-  const long node = (long)(x + HALO) * a.xs + p;
-  double u0 = 0.0, u1 = 0.0, u2 = 0.0;
-  if (a.mask[node] == 0) {
-    const Nbr nb = neighbours(a, x, y, z);
-    double f[HC_Q];
-    pull(a.fin, a.qs, node, nb, f);
-    complete_open<OPEN>(a, node, f);
-    double rhoBar, j0, j1, j2;
-    moments(f, rhoBar, j0, j1, j2);
-    const double invRho = 1.0 / (1.0 + rhoBar);
-    double bx, by, bz;
-    body_at(a, x, y, z, bx, by, bz);
-    u0 = j0 * invRho + bx / 2.0; u1 = j1 * invRho + by / 2.0; u2 = j2 * invRho + bz / 2.0;
-  }
+  PLANE_NODE_VELOCITY(0, plane, yz[k])
   out[3L * k] = u0; out[3L * k + 1] = u1; out[3L * k + 2] = u2;
 }
+
+// hcl_plane_velocity_axis on a y plane (AXIS 1) or a z plane (AXIS 2).  On a z plane consecutive nodes lie nz doubles apart,
+// as in the Lees-Edwards layers; a plane is small
+template <bool OPEN, int AXIS>
+__global__ void plane_velocity_axis_kernel(Args<OPEN> a, int plane, const int *idx, int n, double *out) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  PLANE_NODE_VELOCITY(AXIS, plane, idx[k])
+  out[3L * k] = u0; out[3L * k + 1] = u1; out[3L * k + 2] = u2;
+}
+
+// applyPreInlet on the device (hcl_preinlet_apply): the plane velocities of the pre-inlet lattice `a` at idx[0 .. n-1] go
+// straight into the velocity components of the domain's slots first .. first + n - 1; rho (component 3) is not touched
+template <bool OPEN, int AXIS>
+__global__ void preinlet_couple_kernel(Args<OPEN> a, int plane, const int *idx, int n, double *val, int first) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  PLANE_NODE_VELOCITY(AXIS, plane, idx[k])
+  double *v = val + 4L * (first + k);
+  v[0] = u0; v[1] = u1; v[2] = u2;
+}
+#undef PLANE_NODE_VELOCITY
 
 // ob_val[first + i][c0 .. c0 + nc - 1] = src[i][0 .. nc - 1]
 __global__ void ob_set_kernel(double *val, int first, int n, const double *src, int c0, int nc) {
@@ -1135,7 +1169,7 @@ int hcl_open_boundary_clear(hc_lattice *L) {
     HC_HIP(hipMemcpyAsync(L->ob_code, L->ob_hcode.data(), L->npad * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
     HC_HIP(hipStreamSynchronize(hc::stream()));
   }
-  L->ob_n = 0;
+  L->ob_n = 0; L->ob_epoch++;
   return HC_OK;
 }
 
@@ -1184,22 +1218,137 @@ int hcl_open_boundary_values(hc_lattice *L, int first_slot, int n, double *out) 
   return HC_OK;
 }
 
-int hcl_plane_velocity(hc_lattice *L, int x, const int *yz, int n, double *out, int on_device) {
-  HC_REQUIRE(L && n >= 0 && (n == 0 || (yz && out)), "hcl_plane_velocity: bad arguments");
-  HC_REQUIRE(x >= 0 && x < L->nx, "hcl_plane_velocity: plane outside the lattice");
-  HC_REQUIRE(L->n_slabs == 1, "hcl_plane_velocity: needs n_slabs = 1");
-  for (int i = 0; i < n; i++) HC_REQUIRE(yz[i] >= 0 && (size_t)yz[i] < L->plane, "hcl_plane_velocity: in-plane index out of range");
+// nodes of the plane coordinate[axis] == const, and the lattice's extent along the axis
+static size_t plane_nodes(const hc_lattice *L, int axis) { return axis == 0 ? L->plane : (size_t)L->nx * (axis == 1 ? L->nz : L->ny); }
+static int axis_extent(const hc_lattice *L, int axis) { return axis == 0 ? L->nx : axis == 1 ? L->ny : L->nz; }
+
+// who: the entry point the caller used, for the messages.  Axis 0 launches plane_velocity_kernel, as it always did
+static int plane_velocity(const std::string &who, hc_lattice *L, int axis, int plane, const int *idx, int n, double *out, int on_device) {
+  HC_REQUIRE(L && n >= 0 && (n == 0 || (idx && out)), who + ": bad arguments");
+  HC_REQUIRE(axis >= 0 && axis <= 2, who + ": axis must be 0, 1 or 2");
+  HC_REQUIRE(plane >= 0 && plane < axis_extent(L, axis), who + ": plane outside the lattice");
+  HC_REQUIRE(L->n_slabs == 1, who + ": needs n_slabs = 1");
+  for (int i = 0; i < n; i++) HC_REQUIRE(idx[i] >= 0 && (size_t)idx[i] < plane_nodes(L, axis), who + ": in-plane index out of range");
   if (n == 0) return HC_OK;
   int rc = ob_stage((void **)&L->ob_list, &L->ob_list_cap, sizeof(int), n); if (rc != HC_OK) return rc;
-  HC_HIP(hipMemcpyAsync(L->ob_list, yz, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
+  HC_HIP(hipMemcpyAsync(L->ob_list, idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
   double *d = out;
   if (!on_device) { rc = ob_stage((void **)&L->ob_out, &L->ob_out_cap, 3 * sizeof(double), n); if (rc != HC_OK) return rc; d = L->ob_out; }
   LatArgs a = make_args(L);
-  if (L->ob_n > 0) hipLaunchKernelGGL(plane_velocity_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), open_args(L, a), x, (const int *)L->ob_list, n, d);
-  else hipLaunchKernelGGL(plane_velocity_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), a, x, (const int *)L->ob_list, n, d);
+  const dim3 grid((unsigned)((n + 255) / 256));
+  const int *list = L->ob_list;
+  if (L->ob_n > 0) {
+    const OpenArgs o = open_args(L, a);
+    if (axis == 0) hipLaunchKernelGGL(plane_velocity_kernel<true>, grid, dim3(256), 0, hc::stream(), o, plane, list, n, d);
+    else if (axis == 1) hipLaunchKernelGGL((plane_velocity_axis_kernel<true, 1>), grid, dim3(256), 0, hc::stream(), o, plane, list, n, d);
+    else hipLaunchKernelGGL((plane_velocity_axis_kernel<true, 2>), grid, dim3(256), 0, hc::stream(), o, plane, list, n, d);
+  } else if (axis == 0) hipLaunchKernelGGL(plane_velocity_kernel<false>, grid, dim3(256), 0, hc::stream(), a, plane, list, n, d);
+  else if (axis == 1) hipLaunchKernelGGL((plane_velocity_axis_kernel<false, 1>), grid, dim3(256), 0, hc::stream(), a, plane, list, n, d);
+  else hipLaunchKernelGGL((plane_velocity_axis_kernel<false, 2>), grid, dim3(256), 0, hc::stream(), a, plane, list, n, d);
   HC_HIP(hipGetLastError());
   if (!on_device) HC_HIP(hipMemcpyAsync(out, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));   // the staged node list is reused by the next call
+  return HC_OK;
+}
+
+int hcl_plane_velocity(hc_lattice *L, int x, const int *yz, int n, double *out, int on_device) {
+  return plane_velocity("hcl_plane_velocity", L, 0, x, yz, n, out, on_device);
+}
+
+int hcl_plane_velocity_axis(hc_lattice *L, int axis, int plane, const int *idx, int n, double *out, int on_device) {
+  return plane_velocity("hcl_plane_velocity_axis", L, axis, plane, idx, n, out, on_device);
+}
+
+// ---- the pre-inlet's fluid coupling on the device (hcl_preinlet_*)
+struct hc_preinlet {
+  hc_lattice *pre, *domain;   // not owned: the handle is destroyed before either lattice
+  int axis, plane;            // the pre-inlet's plane coordinate[axis] == plane ...
+  int *idx;                   // ... and the in-plane indices of its coupled nodes [n], device
+  int n, first;               // the domain's velocity slots first .. first + n - 1
+  long epoch;                 // the domain's ob_epoch at creation: hcl_open_boundary_clear moves it on
+};
+
+static bool preinlet_slots_gone(const hc_preinlet *P) { return P->epoch != P->domain->ob_epoch || (long)P->first + P->n > (long)P->domain->ob_n; }
+
+// Everything that can change between two calls is taken here, at launch time: the domain's ob_val is reallocated when its
+// slots grow, and hcl_open_boundary_clear drops the slots (then nothing is launched, whatever was declared since: the slots
+// of a later declaration are not the ones this handle was checked against)
+static int preinlet_launch(const char *who, hc_preinlet *P) {
+  hc_lattice *pre = P->pre, *dom = P->domain;
+  if (preinlet_slots_gone(P)) {
+    hc::set_error(std::string(who) + ": the domain no longer holds the coupled slots (open boundaries cleared since hcl_preinlet_create)");
+    return HC_ERR_STATE;
+  }
+  if (P->n == 0) return HC_OK;
+  const LatArgs a = make_args(pre);
+  const dim3 grid((unsigned)((P->n + 255) / 256));
+  const int *idx = P->idx;
+#define HC_COUPLE(OPEN, AXIS, ARGS) \
+  hipLaunchKernelGGL((preinlet_couple_kernel<OPEN, AXIS>), grid, dim3(256), 0, hc::stream(), ARGS, P->plane, idx, P->n, dom->ob_val, P->first)
+  if (pre->ob_n > 0) {
+    const OpenArgs o = open_args(pre, a);
+    if (P->axis == 0) HC_COUPLE(true, 0, o); else if (P->axis == 1) HC_COUPLE(true, 1, o); else HC_COUPLE(true, 2, o);
+  } else {
+    if (P->axis == 0) HC_COUPLE(false, 0, a); else if (P->axis == 1) HC_COUPLE(false, 1, a); else HC_COUPLE(false, 2, a);
+  }
+#undef HC_COUPLE
+  HC_HIP(hipGetLastError());
+  return HC_OK;
+}
+
+int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, int axis, int pre_plane,
+                        const int *pre_idx, int n, int domain_first_slot) {
+  HC_REQUIRE(out && pre && domain && n >= 0 && (n == 0 || pre_idx), "hcl_preinlet_create: bad arguments");
+  HC_REQUIRE(axis >= 0 && axis <= 2, "hcl_preinlet_create: axis must be 0, 1 or 2");
+  HC_REQUIRE(pre->n_slabs == 1 && domain->n_slabs == 1, "hcl_preinlet_create: needs n_slabs = 1 on both lattices");
+  HC_REQUIRE(pre_plane >= 0 && pre_plane < axis_extent(pre, axis), "hcl_preinlet_create: plane outside the pre-inlet lattice");
+  for (int i = 0; i < n; i++) HC_REQUIRE(pre_idx[i] >= 0 && (size_t)pre_idx[i] < plane_nodes(pre, axis), "hcl_preinlet_create: in-plane index out of range");
+  HC_REQUIRE(domain_first_slot >= 0 && (long)domain_first_slot + n <= (long)domain->ob_n, "hcl_preinlet_create: slots out of range on the domain");
+  if (n > 0) {   // every coupled slot belongs to a velocity node (kind bit 1 of the code is clear)
+    long found = 0;
+    for (const int code : domain->ob_hcode) {
+      if (code < 0) continue;
+      const int slot = (code & ((1 << HC_OB_AXIS_SHIFT) - 1)) >> 2;
+      if (slot < domain_first_slot || slot >= domain_first_slot + n) continue;
+      HC_REQUIRE((code & 2) == 0, "hcl_preinlet_create: a coupled slot is a pressure slot; the coupling sets velocities");
+      found++;
+    }
+    HC_REQUIRE(found == n, "hcl_preinlet_create: a coupled slot has no node");
+  }
+  hc_preinlet *P = new hc_preinlet();
+  P->pre = pre; P->domain = domain; P->axis = axis; P->plane = pre_plane; P->idx = nullptr; P->n = n; P->first = domain_first_slot;
+  P->epoch = domain->ob_epoch;
+  if (n > 0) {
+    hipError_t e = hipMalloc((void **)&P->idx, (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpyAsync(P->idx, pre_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream());
+    if (e == hipSuccess) e = hipStreamSynchronize(hc::stream());   // the caller's list may go away after the call
+    if (e != hipSuccess) { if (P->idx) hipFree(P->idx); delete P; HC_HIP(e); }
+  }
+  *out = P;
+  return HC_OK;
+}
+
+int hcl_preinlet_apply(hc_preinlet *P) {
+  HC_REQUIRE(P, "hcl_preinlet_apply: null handle");
+  return preinlet_launch("hcl_preinlet_apply", P);
+}
+
+int hcl_preinlet_iterate(hc_preinlet *P, int n) {
+  HC_REQUIRE(P && n >= 0, "hcl_preinlet_iterate: bad arguments");
+  if (preinlet_slots_gone(P)) return preinlet_launch("hcl_preinlet_iterate", P);   // refused before any step
+  for (int it = 0; it < n; it++) {
+    int rc = hcl_collide_stream(P->pre, 1); if (rc != HC_OK) return rc;
+    if ((rc = hcl_collide_stream(P->domain, 1)) != HC_OK) return rc;
+    if ((rc = preinlet_launch("hcl_preinlet_iterate", P)) != HC_OK) return rc;
+  }
+  return HC_OK;
+}
+
+int hcl_preinlet_destroy(hc_preinlet *P) {
+  if (!P) return HC_OK;
+  hipStreamSynchronize(hc::stream());
+  if (P->idx) hipFree(P->idx);
+  delete P;
   return HC_OK;
 }
 

@@ -236,6 +236,15 @@ class Lattice:
         check(self.lib.hcl_plane_velocity(self.ptr, int(x), ii.ctypes.data_as(C.POINTER(C.c_int)), len(ii), out.ctypes.data, 0))
         return out
 
+    def planeVelocityAxis(self, axis, plane, idx):
+        """the same on the plane coordinate[axis] == plane: idx are in-plane indices as plane_index() forms them
+        (y * nz + z, x * nz + z, x * ny + y for axis 0, 1, 2): [n][3]"""
+        ii = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        out = np.empty((len(ii), 3))
+        check(self.lib.hcl_plane_velocity_axis(self.ptr, int(axis), int(plane), ii.ctypes.data_as(C.POINTER(C.c_int)), len(ii),
+                                               out.ctypes.data, 0))
+        return out
+
     def _add_open_box(self, kind, orientation, box, axis=0):
         bb = (C.c_int * 6)(*[int(v) for v in box])
         first, n = C.c_int(), C.c_int()
@@ -380,45 +389,118 @@ def preinlet_driving_force(Re, nu_lbm, fluid_area, direction="Xpos"):
     return radius, u_max, (-force if direction == "Xpos" else force)
 
 
-class PreInlet:
-    """One-process stand-in for helper/preInlet.h's fluid coupling (x-normal): a pre-inlet lattice and a domain lattice step
-    in the reference's per-iteration order -- both iterate, then applyPreInlet: the pre-inlet evaluates u = j/rho + F/2 on its
-    plane pre_x at the coupled nodes, and the domain takes them as the velocities of its Zou-He velocity nodes at the same
-    global (y, z) on its plane domain_x (0N for Xneg, 0P for Xpos).  The domain thus lags the pre-inlet by one iteration, as
-    in the reference.  yz: [n][2] GLOBAL (y, z) of the coupled nodes; pre_origin / domain_origin: the global (y, z) of each
-    lattice's node (., 0, 0) -- the cross-sections may differ, as the reference's pre-inlet box (the slice's bounding box
-    enlarged by 1) differs from the domain's.  Cells do not cross yet: the coupling is the fluid's."""
+# the reference's six Direction values (helper/preInlet.h): name -> (axis, -1 for *neg / +1 for *pos)
+PREINLET_DIRECTIONS = {"Xneg": (0, -1), "Xpos": (0, 1), "Yneg": (1, -1), "Ypos": (1, 1), "Zneg": (2, -1), "Zpos": (2, 1)}
 
-    def __init__(self, preinlet, domain, yz, pre_x, domain_x, direction="Xpos", pre_origin=(0, 0), domain_origin=(0, 0)):
-        if direction not in ("Xpos", "Xneg"):
-            raise HcError("PreInlet: only the directions Xpos and Xneg are supported")
-        self.pre, self.domain = preinlet, domain
+
+def _preinlet_direction(direction):
+    if direction not in PREINLET_DIRECTIONS:
+        raise HcError("PreInlet: unknown direction %r (Xneg, Xpos, Yneg, Ypos, Zneg, Zpos)" % (direction,))
+    return PREINLET_DIRECTIONS[direction]
+
+
+def preinlet_driving_force_vector(Re, nu_lbm, fluid_area, direction):
+    """preinlet_driving_force in any of the six directions: the same three operations in the same order
+    (PreInlet::calculateDrivingForce), the force on the direction's axis, + for *neg and - for *pos (setDrivingForce), zero
+    on the other axes.  Returns (R, u_max, (F_x, F_y, F_z))."""
+    axis, sign = _preinlet_direction(direction)
+    radius = math.sqrt(fluid_area / math.pi)
+    u_max = Re * nu_lbm / (radius * 2)
+    force = 8 * nu_lbm * (u_max * 0.5) / radius / radius
+    F = [0.0, 0.0, 0.0]
+    F[axis] = -force if sign > 0 else force
+    return radius, u_max, tuple(F)
+
+
+def plane_index(dims, axis, a, b):
+    """the in-plane index hcl_plane_velocity_axis takes: the node's offset with `axis` removed and the remaining axes in
+    lattice order.  a, b: the coordinates on the two other axes in ascending axis order -- (y, z), (x, z), (x, y) for axis
+    0, 1, 2 -- so the index is y * nz + z, x * nz + z, x * ny + y.  dims: (nx, ny, nz).  Pure numpy."""
+    if axis not in (0, 1, 2):
+        raise HcError("plane_index: axis must be 0, 1 or 2")
+    inner = dims[1] if axis == 2 else dims[2]
+    return np.asarray(a, dtype=np.int64) * int(inner) + np.asarray(b, dtype=np.int64)
+
+
+class PreInlet:
+    """One-process stand-in for helper/preInlet.h's fluid coupling in the reference's six directions: a pre-inlet lattice and a
+    domain lattice step in the reference's per-iteration order -- both iterate, then applyPreInlet: the pre-inlet evaluates
+    u = j/rho + F/2 on its plane pre_x at the coupled nodes, and the domain takes them as the velocities of its Zou-He velocity
+    nodes at the same global in-plane coordinates on its plane domain_x.  The domain thus lags the pre-inlet by one iteration,
+    as in the reference.  For a direction on axis a (X: 0, Y: 1, Z: 2), pre_x and domain_x are plane numbers along a, the
+    domain's inlet is an <a>N side for *neg (the pre-inlet lies below the domain and drives along +a) and an <a>P side for
+    *pos, and yz: [n][2] holds the GLOBAL coordinates of the coupled nodes on the two other axes in ascending axis order --
+    (y, z), (x, z), (x, y); pre_origin / domain_origin likewise: the global in-plane coordinates of each lattice's node 0 of
+    those axes -- the cross-sections may differ, as the reference's pre-inlet box (the slice's bounding box enlarged by 1)
+    differs from the domain's.  device=False: applyPreInlet reads the plane velocities back and sets the slots from the host
+    (two waits for the stream per iteration); it and iterate return the velocities sent.  device=True: an hc_preinlet handle
+    (hcl_preinlet_*) does the exchange in one kernel, iterate(n) queues all n iterations in one call, and both return None;
+    sent() reads the slots back either way.  A device coupling holds pointers into both lattices: destroy() it before them.
+    Cells do not cross yet: the coupling is the fluid's."""
+
+    def __init__(self, preinlet, domain, yz, pre_x, domain_x, direction="Xpos", pre_origin=(0, 0), domain_origin=(0, 0),
+                 device=False):
+        axis, sign = _preinlet_direction(direction)
+        self.pre, self.domain = preinlet, domain   # kept alive as long as the coupling
+        self.axis, self.device, self.ptr = axis, bool(device), None
+        others = [d for d in range(3) if d != axis]
+        pdims, ddims = (preinlet.nx, preinlet.ny, preinlet.nz), (domain.nx, domain.ny, domain.nz)
         g = np.asarray(yz, dtype=np.int64).reshape(-1, 2)
-        py, pz = g[:, 0] - int(pre_origin[0]), g[:, 1] - int(pre_origin[1])
-        dy, dz = g[:, 0] - int(domain_origin[0]), g[:, 1] - int(domain_origin[1])
-        if ((py < 0) | (py >= preinlet.ny) | (pz < 0) | (pz >= preinlet.nz)).any():
+        pa, pb = g[:, 0] - int(pre_origin[0]), g[:, 1] - int(pre_origin[1])
+        da, db = g[:, 0] - int(domain_origin[0]), g[:, 1] - int(domain_origin[1])
+        if ((pa < 0) | (pa >= pdims[others[0]]) | (pb < 0) | (pb >= pdims[others[1]])).any():
             raise HcError("PreInlet: a coupled node lies outside the pre-inlet's cross-section")
-        if ((dy < 0) | (dy >= domain.ny) | (dz < 0) | (dz >= domain.nz)).any():
+        if ((da < 0) | (da >= ddims[others[0]]) | (db < 0) | (db >= ddims[others[1]])).any():
             raise HcError("PreInlet: a coupled node lies outside the domain's cross-section")
-        self.pre_yz = np.ascontiguousarray(py * preinlet.nz + pz, dtype=np.int32)
+        self.pre_yz = np.ascontiguousarray(plane_index(pdims, axis, pa, pb), dtype=np.int32)
         self.pre_x, self.domain_x = int(pre_x), int(domain_x)
-        self.domain_nodes = np.stack([np.full(len(g), self.domain_x), dy, dz], axis=1)
-        # Xneg: the pre-inlet lies below the domain and drives along +x, so the domain's inlet is a 0N side; Xpos mirrors it
-        self.first = domain.addOpenBoundaryNodes(0, -1 if direction == "Xneg" else 1, self.domain_nodes)
+        nodes = np.empty((len(g), 3), np.int64)
+        nodes[:, axis], nodes[:, others[0]], nodes[:, others[1]] = self.domain_x, da, db
+        self.domain_nodes = nodes
+        # *neg: the pre-inlet lies below the domain and drives along +axis, so the domain's inlet is an N side; *pos mirrors it
+        # (initializePreInletVelocityBoundary: addVelocityBoundary<axis>N / <axis>P)
+        self.first = domain.addOpenBoundaryNodes(0, sign, self.domain_nodes, axis=axis)
+        if self.device:
+            ptr = C.c_void_p()
+            check(capi.lib().hcl_preinlet_create(C.byref(ptr), preinlet.ptr, domain.ptr, axis, self.pre_x,
+                                                 self.pre_yz.ctypes.data_as(C.POINTER(C.c_int)), len(self.pre_yz), self.first))
+            self.ptr = ptr
 
     def applyPreInlet(self):
-        u = self.pre.planeVelocity(self.pre_x, self.pre_yz)
+        if self.device:
+            check(capi.lib().hcl_preinlet_apply(self._handle()))
+            return None
+        u = self.pre.planeVelocityAxis(self.axis, self.pre_x, self.pre_yz)
         self.domain.setOpenBoundaryVelocitySlots(self.first, u)
         return u
 
     def iterate(self, n=1):
-        """n iterations of (pre-inlet step, domain step, applyPreInlet); returns the last plane velocities sent"""
+        """n iterations of (pre-inlet step, domain step, applyPreInlet).  Host path: returns the last plane velocities sent;
+        device path: one hcl_preinlet_iterate, nothing waits for the device, returns None"""
+        if self.device:
+            check(capi.lib().hcl_preinlet_iterate(self._handle(), int(n)))
+            return None
         u = None
         for _ in range(int(n)):
             self.pre.collideAndStream(1)
             self.domain.collideAndStream(1)
             u = self.applyPreInlet()
         return u
+
+    def sent(self):
+        """[n][3]: the velocities the domain's coupled slots hold now"""
+        return self.domain.openBoundaryValues(self.first, len(self.pre_yz))[:, :3]
+
+    def _handle(self):
+        if self.ptr is None:
+            raise HcError("PreInlet: the device coupling has been destroyed")
+        return self.ptr
+
+    def destroy(self):
+        """frees the device coupling, if any; call it before destroying either lattice"""
+        if self.ptr is not None:
+            check(capi.lib().hcl_preinlet_destroy(self.ptr))
+            self.ptr = None
 
 
 class CellType:

@@ -202,8 +202,34 @@ int hcl_open_boundary_values(hc_lattice *L, int first_slot, int n, double *out);
 /* Cell::computeVelocity on nodes of the plane x of the post-stream state: u = j/rho + F/2 with F the body force (and the
  * force regions) alone -- what HemoCell's force field holds after iterate() and setExternalVector.  yz: [n] in-plane
  * indices y * nz + z (host); out: [n][3] on the device (on_device != 0, ordered on the library's stream) or the host.
- * Bounce-back nodes give 0. */
+ * Bounce-back nodes give 0.  Needs n_slabs = 1.  It is hcl_plane_velocity_axis with axis 0. */
 int hcl_plane_velocity(hc_lattice *L, int x, const int *yz, int n, double *out, int on_device);
+/* The same on the plane coordinate[axis] == plane of any axis (0, 1, 2; x local, 0 .. nx - 1).  idx: [n] in-plane indices, the
+ * node's offset with the axis removed and the remaining axes in lattice order: y * nz + z (axis 0), x * nz + z (axis 1),
+ * x * ny + y (axis 2).  Every rule above holds (n_slabs = 1, bounce-back nodes give 0, a lattice with open-boundary nodes
+ * reports completed moments, also on a plane that lies on or crosses an open face).  Another axis, a plane outside the
+ * lattice or an index outside the plane is HC_ERR_ARG.  The node list is staged from the host and the call ends in a wait
+ * for the library's stream: it is an observer, not a per-iteration path (that is hcl_preinlet_apply). */
+int hcl_plane_velocity_axis(hc_lattice *L, int axis, int plane, const int *idx, int n, double *out, int on_device);
+/* The pre-inlet's fluid coupling kept on the device (helper/preInlet.cpp, applyPreInletVelocityBoundary): the plane velocities
+ * of the lattice `pre` on its plane coordinate[axis] == pre_plane at the in-plane indices pre_idx[0 .. n-1] (as for
+ * hcl_plane_velocity_axis) become the velocities of the domain's open-boundary slots domain_first_slot .. + n - 1, node k
+ * to slot domain_first_slot + k.  create uploads the index list once and checks: n_slabs = 1 on both lattices, plane and
+ * indices in range, the slots exist on the domain and every one of them is a velocity slot (else HC_ERR_ARG).  The handle
+ * holds plain pointers to both lattices and owns neither: destroy it BEFORE either lattice.
+ * apply: one kernel on the library's stream, no staging, no copy and no host wait; it writes u_x, u_y, u_z of the slots and
+ * leaves rho alone.  It reads the domain's slot storage and the pre-inlet's state at the time of the call, so slots
+ * declared on the domain after create (which may move that storage) do no harm.  After hcl_open_boundary_clear on the
+ * domain the coupled slots are gone: apply and iterate then return HC_ERR_STATE and launch nothing, also when nodes were
+ * declared again since -- make a new handle.
+ * iterate: n times (hcl_collide_stream(pre, 1), hcl_collide_stream(domain, 1), apply), the reference's per-iteration order,
+ * all queued on the library's stream without a host wait: the domain lags the pre-inlet by one iteration. */
+typedef struct hc_preinlet hc_preinlet;
+int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, int axis, int pre_plane,
+                        const int *pre_idx, int n, int domain_first_slot);
+int hcl_preinlet_apply(hc_preinlet *P);
+int hcl_preinlet_iterate(hc_preinlet *P, int n);
+int hcl_preinlet_destroy(hc_preinlet *P);
 /* bring the x-halo planes of a slab up to date (width 1 or 2, see hcl_halo_doubles) through the data plane; the
  * download / statistics entry points do it by themselves */
 int hcl_slab_refresh_halos(hc_lattice *L, int width);
