@@ -4,7 +4,9 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include <type_traits>
 #include "../../include/hemocell_amd.h"
+#include "d3q19.h"
 
 namespace hc {
 
@@ -41,12 +43,6 @@ struct ProfScope {
   explicit ProfScope(int kernel);
   ~ProfScope();
 };
-
-// D3Q19, Palabos ordering: opposite of i (1..9) is i+9.
-// (patch/palabos.patch:491-498)
-#define HC_CX {0, -1, 0, 0, -1, -1, -1, -1, 0, 0, 1, 0, 0, 1, 1, 1, 1, 0, 0}
-#define HC_CY {0, 0, -1, 0, -1, 1, 0, 0, -1, -1, 0, 1, 0, 1, -1, 0, 0, 1, 1}
-#define HC_CZ {0, 0, 0, -1, 0, 0, -1, 1, -1, 1, 0, 0, 1, 0, 0, 1, -1, 1, -1}
 
 constexpr int HALO = 2;  // x-halo planes on each side of a slab
 
@@ -103,19 +99,22 @@ __device__ __forceinline__ void region_force(const BodyRegions &r, int xg, int y
 // for x, the normal velocity is u[a] and the tangential pair is (u_x, u_z) for y and (u_y, u_x) for z.  Every sum keeps the
 // operand order of the x completion; the indices are template constants, so f stays in registers.
 // tests/open_boundary_ref.py restates the x completion operation for operation and tests/open_boundary_axis_ref.py the
-// permutation around it.  The collide calls it on fluid nodes before it relaxes, and every observer of an open lattice
-// (rho_u, pi_neq, plane velocity, statistics, the IBM node velocity) before it takes moments.
+// permutation around it.  The collide calls it on fluid nodes before it relaxes, and every observer of an open lattice before
+// it takes moments: observe() in lattice.hip (rho_u, pi_neq, plane velocity and pre-inlet coupling, statistics) and
+// node_velocity() in ibm.hip.  launch_open() below picks the instantiation that does so, for all of them.
 //
 // ob_code[node] = -1, or axis << 29 | slot << 2 | kind: the axis sits above the slot, so a node with normal x carries the code
 // it always carried and slots stay below 1 << 27 (HC_OB_MAX_SLOTS).
 constexpr int HC_OB_AXIS_SHIFT = 29;
 constexpr int HC_OB_MAX_SLOTS = 1 << 27;
+constexpr int ob_axis(int code) { return code >> HC_OB_AXIS_SHIFT; }
+constexpr int ob_slot(int code) { return (code & ((1 << HC_OB_AXIS_SHIFT) - 1)) >> 2; }
+constexpr bool ob_is_pressure(int code) { return (code & 2) != 0; }
 __host__ __device__ constexpr int zh_perm(int axis, int i) {
-  constexpr int cx[HC_Q] = HC_CX, cy[HC_Q] = HC_CY, cz[HC_Q] = HC_CZ;
-  const int x = axis == 1 ? cy[i] : axis == 2 ? cz[i] : cx[i];
-  const int y = axis == 1 ? cx[i] : cy[i];
-  const int z = axis == 2 ? cx[i] : cz[i];
-  for (int j = 0; j < HC_Q; j++) if (cx[j] == x && cy[j] == y && cz[j] == z) return j;
+  const int x = axis == 1 ? HC_CY[i] : axis == 2 ? HC_CZ[i] : HC_CX[i];
+  const int y = axis == 1 ? HC_CX[i] : HC_CY[i];
+  const int z = axis == 2 ? HC_CX[i] : HC_CZ[i];
+  for (int j = 0; j < HC_Q; j++) if (HC_CX[j] == x && HC_CY[j] == y && HC_CZ[j] == z) return j;
   return -1;
 }
 template <int AXIS, int I> inline constexpr int ZH = zh_perm(AXIS, I);
@@ -179,9 +178,9 @@ struct hc_lattice {
   size_t xs;             // elements from x-plane to x-plane: plane, or plane + 8 rows of padding (see hcl_create)
   size_t npad;           // (nx+2*HALO)*xs
   size_t qstride;        // doubles from population q to q+1 of the same node: npad + padding (see hcl_create)
-  double *f[2];          // [19][npad] post-collision populations (fBar), ping-pong
+  double *f[2] = {nullptr, nullptr};   // [19][npad] post-collision populations (fBar), ping-pong
   int cur;               // f[cur] is read by the next collide
-  double *force[3];      // [npad][3] IBM force accumulators (a node's three components side by side), rotated: fcur -> (fcur+1)%3 every step
+  double *force[3] = {nullptr, nullptr, nullptr};   // [npad][3] IBM force accumulators (a node's three components side by side), rotated: fcur -> (fcur+1)%3 every step
   int fcur;              // force[fcur] is the one spread adds to / collide reads; force[(fcur+2)%3] is the previous
                          // step's (what the interpolation after a collide reads, and what the NEXT collide zeroes);
                          // force[(fcur+1)%3] is already clean, so the spread of the next step may run beside this collide
@@ -190,22 +189,22 @@ struct hc_lattice {
   // force component) holding the epoch in which spread last touched the group.  The collide kernel reads /
   // zeroes a group only when its byte equals the buffer's current epoch, so untouched lines cost no traffic.
   // Epochs are never cleared (no races); an aliased stale epoch only causes a harmless extra read / zeroing.
-  uint8_t *fdirty[3];
+  uint8_t *fdirty[3] = {nullptr, nullptr, nullptr};
   uint8_t fepoch[3];
   // one byte per 8 x 8 x 8 brick of the padded lattice: 1 = the brick holds a non-fluid node or touches a face that stencils
   // cannot cross (the IBM kernels skip the mask look-ups for cells whose tile meets no such brick)
-  uint8_t *wallbrick; int nbx, nby, nbz;
-  uint8_t *mask;         // [npad]
+  uint8_t *wallbrick = nullptr; int nbx, nby, nbz;
+  uint8_t *mask = nullptr;   // [npad]
   std::vector<uint8_t> hmask;  // host copy (cell placement tests against it)
   double body[3];
   hc::BodyRegions regions;   // boxes with their own body force (hcl_set_body_force_regions), global node coordinates
   double wall_u[4][3];   // velocities of the moving-wall mask classes 3..6
   // active-node map of the collide kernel: per padded plane and row, the z-span that holds every node
   // which is not an inert solid, flattened so that a launch only creates threads for those spans
-  int *row_z0, *row_cum, *blk_row;   // [NX*ny], [NX*(ny+1)], [NX*(nblk+1)]
+  int *row_z0 = nullptr, *row_cum = nullptr, *blk_row = nullptr;   // [NX*ny], [NX*(ny+1)], [NX*(nblk+1)]
   int nblk, max_active;
-  double *scratch;       // download staging
-  size_t scratch_doubles;
+  double *scratch = nullptr;   // download staging
+  size_t scratch_doubles = 0;
   // slab runs: node velocities u = j/rho + F/2 of the two neighbours' face planes, evaluated there by their owner after the
   // last collide (slab.hip); [side][3][plane].  The interpolation reads them for stencil nodes on the first halo plane
   // instead of gathering 19 populations there.  Valid from the exchange until the next hcl_step_end.
@@ -226,7 +225,20 @@ struct hc_lattice {
   long ob_epoch = 0;                // counts hcl_open_boundary_clear: a pre-inlet coupling (hc_preinlet) made before one is stale
   int *ob_list = nullptr; int ob_list_cap = 0;   // staging of hcl_plane_velocity's node list
   double *ob_out = nullptr; int ob_out_cap = 0;  // ... and of its output when the caller's buffer is on the host
+  ~hc_lattice();   // lattice.hip: frees the device memory above, whatever part of it exists (halo_u belongs to slab.hip)
 };
+
+namespace hc {
+// The one open-boundary dispatch.  A kernel that observes or advances populations has an OPEN instantiation, which takes the
+// plain arguments extended by the open-boundary tables (open_of(L, plain), next to each argument struct) and completes the
+// Zou-He nodes; a lattice runs it while it has such nodes and the plain instantiation, as ever, otherwise.
+// launch(open, args): open is std::true_type / std::false_type, so that decltype(open)::value is a template argument.
+template <class Plain, class Launch>
+inline void launch_open(const hc_lattice *L, const Plain &plain, Launch launch) {
+  if (L->ob_n > 0) launch(std::true_type{}, open_of(L, plain));
+  else launch(std::false_type{}, plain);
+}
+}  // namespace hc
 
 namespace hc {
 int lees_edwards_step(hc_lattice *L);   // lattice.hip: the pass after a step, when enabled

@@ -119,27 +119,13 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const Pops<OPEN>
     const double *hu = v.halo_u[lx < 0 ? 0 : 1];
     if (hu) { const long k = (long)ly * v.nz + lz; u[0] = hu[k]; u[1] = hu[v.ny_nz + k]; u[2] = hu[2L * v.ny_nz + k]; return; }
   }
-  // gather S(node,q) = P(node - c_q, q) with the same wrap rules as the collide kernel
-  long xm = -(long)v.plane, xp = (long)v.plane;
-  if (v.wrap_x) { if (lx == 0) xm = (long)(v.nx - 1) * v.plane; if (lx == v.nx - 1) xp = -(long)(v.nx - 1) * v.plane; }
-  int ym = -v.nz, yp = v.nz, zm = -1, zp = 1; bool ymk = true, ypk = true, zmk = true, zpk = true;
-  if (ly == 0) { if (v.per_y) ym = (v.ny - 1) * v.nz; else ymk = false; }
-  if (ly == v.ny - 1) { if (v.per_y) yp = -(v.ny - 1) * v.nz; else ypk = false; }
-  if (lz == 0) { if (v.per_z) zm = v.nz - 1; else zmk = false; }
-  if (lz == v.nz - 1) { if (v.per_z) zp = -(v.nz - 1); else zpk = false; }
+  // gather S(node,q) = P(node - c_q, q) through the neighbour and wrap rules the collide kernel uses (d3q19.h)
+  const hc::Nbr nb = hc::neighbours(v, v.plane, lx, ly, lz);
   double r = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
   [[maybe_unused]] double f[OPEN ? HC_Q : 1];   // OPEN: the gathered populations are kept, completed, and summed afterwards in the same order
-#define NV_Q(M)                                                                              \
-  M(0, 0, 0, 0) M(1, -1, 0, 0) M(2, 0, -1, 0) M(3, 0, 0, -1) M(4, -1, -1, 0) M(5, -1, 1, 0)  \
-  M(6, -1, 0, -1) M(7, -1, 0, 1) M(8, 0, -1, -1) M(9, 0, -1, 1) M(10, 1, 0, 0) M(11, 0, 1, 0) \
-  M(12, 0, 0, 1) M(13, 1, 1, 0) M(14, 1, -1, 0) M(15, 1, 0, 1) M(16, 1, 0, -1) M(17, 0, 1, 1) \
-  M(18, 0, 1, -1)
 #define M(Q, CX, CY, CZ)                                                              \
   {                                                                                   \
-    long off = 0; bool ok = true;                                                     \
-    if (CX == 1) off += xm; else if (CX == -1) off += xp;                             \
-    if (CY == 1) { off += ym; ok = ok && ymk; } else if (CY == -1) { off += yp; ok = ok && ypk; } \
-    if (CZ == 1) { off += zm; ok = ok && zmk; } else if (CZ == -1) { off += zp; ok = ok && zpk; } \
+    bool ok; const long off = hc::src_off<CX, CY, CZ>(nb, ok);                        \
     const double fq = ok ? pv.f[(long)Q * pv.qs + node + off] : 0.0;                 \
     if constexpr (OPEN) f[Q] = fq;                                                    \
     else {                                                                            \
@@ -149,22 +135,15 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const Pops<OPEN>
       if (CZ == 1) jz += fq; else if (CZ == -1) jz += -fq;                            \
     }                                                                                 \
   }
-  NV_Q(M)
+  FOR_Q(M)
 #undef M
   if constexpr (OPEN) {
     if (v.mask[node] == 0) {
       const int code = pv.ob_code[node];
       if (code >= 0) hc::zou_he_node(f, code, pv.ob_val);
     }
-#define M(Q, CX, CY, CZ)                                                              \
-    r += f[Q];                                                                        \
-    if (CX == 1) jx += f[Q]; else if (CX == -1) jx += -f[Q];                          \
-    if (CY == 1) jy += f[Q]; else if (CY == -1) jy += -f[Q];                          \
-    if (CZ == 1) jz += f[Q]; else if (CZ == -1) jz += -f[Q];
-    NV_Q(M)
-#undef M
+    hc::moments(f, r, jx, jy, jz);
   }
-#undef NV_Q
   const double invRho = 1.0 / (1.0 + r);
   double bx = pv.bx, by = pv.by, bz = pv.bz;
   if (pv.reg.n) {   // a halo plane of a slab, or the wrapped image, is the global node next door
@@ -635,20 +614,25 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
   }
 }
 
-}  // namespace
-
-// launches K<true> with the open-boundary tables while the lattice L has Zou-He nodes, K<false> as ever otherwise
-static OpenPopView open_pops(const hc_lattice *L, const PopView &pv) {
+// state after hcl_step_end: f[cur] holds the populations just written, force[(fcur+2)%3] the force they were collided with
+PopView make_pops(const hc_lattice *L) {
+  return PopView{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
+}
+// the arguments of the open-boundary instantiations (hc::launch_open)
+OpenPopView open_of(const hc_lattice *L, const PopView &pv) {
   OpenPopView o;
   static_cast<PopView &>(o) = pv;
   o.ob_code = L->ob_code; o.ob_val = L->ob_val;
   return o;
 }
+
+}  // namespace
+
+// K<OPEN> through the one open-boundary dispatch (hc::launch_open)
 #define HC_LAUNCH_POPS(K, grid, block, v, pv, ...)                                                                      \
-  do {                                                                                                                  \
-    if (L->ob_n > 0) hipLaunchKernelGGL(K<true>, grid, block, 0, hc::stream(), v, open_pops(L, pv), __VA_ARGS__);       \
-    else hipLaunchKernelGGL(K<false>, grid, block, 0, hc::stream(), v, pv, __VA_ARGS__);                                \
-  } while (0)
+  hc::launch_open(L, pv, [&](auto open, const auto &pops) {                                                             \
+    hipLaunchKernelGGL(K<decltype(open)::value>, grid, block, 0, hc::stream(), v, pops, __VA_ARGS__);                   \
+  })
 
 static int g_ibm_per_vertex = 0;  // 1: one thread per vertex with direct global atomics (kept for A/B and as reference)
 extern "C" int hc_debug_ibm_per_vertex(int on) { g_ibm_per_vertex = on; return HC_OK; }
@@ -761,8 +745,7 @@ int hcp_interpolate(hc_cells *C) {
   hc::ProfScope prof(hc::PK_INTERP);
   const hc_lattice *L = C->L;
   const LatView v = make_view(L);
-  // state after hcl_step_end: f[cur] holds the populations just written, force[(fcur+2)%3] the force they were collided with
-  PopView pv{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
+  const PopView pv = make_pops(L);
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
     if (n == 0) continue;
@@ -790,7 +773,7 @@ int hcl_face_velocity_pack(hc_lattice *L, int side, double *dev_buf) {
   HC_REQUIRE(L && dev_buf && (side == 0 || side == 1), "hcl_face_velocity_pack: bad arguments");
   LatView v = make_view(L);
   v.halo_u[0] = v.halo_u[1] = nullptr;   // own planes only: nothing here reads a halo velocity
-  PopView pv{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
+  const PopView pv = make_pops(L);
   hipLaunchKernelGGL(face_velocity_kernel, dim3((unsigned)((L->plane + 255) / 256), 1, 1), dim3(256), 0, hc::stream(), v, pv, side == 0 ? 0 : L->nx - 1, dev_buf, 0, (double *)nullptr);
   HC_HIP(hipGetLastError());
   return HC_OK;
@@ -802,7 +785,7 @@ int hcl_face_velocity_pack_both(hc_lattice *L, double *dev_lo, double *dev_hi) {
   if (!dev_lo || !dev_hi) return hcl_face_velocity_pack(L, dev_lo ? 0 : 1, dev_lo ? dev_lo : dev_hi);
   LatView v = make_view(L);
   v.halo_u[0] = v.halo_u[1] = nullptr;
-  PopView pv{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
+  const PopView pv = make_pops(L);
   hipLaunchKernelGGL(face_velocity_kernel, dim3((unsigned)((L->plane + 255) / 256), 2, 1), dim3(256), 0, hc::stream(), v, pv, 0, dev_lo, L->nx - 1, dev_hi);
   HC_HIP(hipGetLastError());
   return HC_OK;
@@ -837,7 +820,7 @@ int hcc::interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n
   hc::ProfScope prof(hc::PK_INTERP);
   const hc_lattice *L = C->L;
   const LatView v = make_view(L);
-  PopView pv{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
+  const PopView pv = make_pops(L);
   const long f = C->first[type];
   const int nv = C->types[type]->host.nv;
   HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)n), dim3(nv > 128 ? 256 : 128), v, pv, nv,

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "comm.h"
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 
 using namespace hc;
@@ -65,100 +66,26 @@ __device__ __forceinline__ void body_at(const LatArgs &a, int x, int y, int z, d
   if (a.reg.n) region_force(a.reg, a.x0 + x, y, z, bx, by, bz);
 }
 
-struct Nbr {  // element offsets to the -1 / +1 neighbour along each axis, and validity
-  long xm, xp;
-  int ym, yp, zm, zp;
-  bool ym_ok, yp_ok, zm_ok, zp_ok;
-};
+// the gather's neighbour and wrap rules (d3q19.h) on the arguments of this file's kernels
+__device__ __forceinline__ Nbr neighbours(const LatArgs &a, int x, int y, int z) { return hc::neighbours(a, a.xs, x, y, z); }
 
-__device__ __forceinline__ Nbr neighbours(const LatArgs &a, int x, int y, int z) {
-  Nbr n;
-  n.xm = -a.xs; n.xp = a.xs;
-  if (a.wrap_x) {
-    if (x == 0) n.xm = (long)(a.nx - 1) * a.xs;
-    if (x == a.nx - 1) n.xp = -(long)(a.nx - 1) * a.xs;
-  }
-  n.ym = -a.nz; n.yp = a.nz; n.ym_ok = n.yp_ok = true;
-  if (y == 0) { if (a.per_y) n.ym = (a.ny - 1) * a.nz; else n.ym_ok = false; }
-  if (y == a.ny - 1) { if (a.per_y) n.yp = -(a.ny - 1) * a.nz; else n.yp_ok = false; }
-  n.zm = -1; n.zp = 1; n.zm_ok = n.zp_ok = true;
-  if (z == 0) { if (a.per_z) n.zm = a.nz - 1; else n.zm_ok = false; }
-  if (z == a.nz - 1) { if (a.per_z) n.zp = -(a.nz - 1); else n.zp_ok = false; }
-  return n;
-}
-
-// offset from a node to (node - c_q)   [c = +1 -> the -1 neighbour]
-template <int CX, int CY, int CZ>
-__device__ __forceinline__ long src_off(const Nbr &n, bool &ok) {
-  long off = 0; ok = true;
-  if (CX == 1) off += n.xm; else if (CX == -1) off += n.xp;
-  if (CY == 1) { off += n.ym; ok = ok && n.ym_ok; } else if (CY == -1) { off += n.yp; ok = ok && n.yp_ok; }
-  if (CZ == 1) { off += n.zm; ok = ok && n.zm_ok; } else if (CZ == -1) { off += n.zp; ok = ok && n.zp_ok; }
-  return off;
-}
-// offset from a node to (node + c_q)
-template <int CX, int CY, int CZ>
-__device__ __forceinline__ long dst_off(const Nbr &n, bool &ok) {
-  long off = 0; ok = true;
-  if (CX == 1) off += n.xp; else if (CX == -1) off += n.xm;
-  if (CY == 1) { off += n.yp; ok = ok && n.yp_ok; } else if (CY == -1) { off += n.ym; ok = ok && n.ym_ok; }
-  if (CZ == 1) { off += n.zp; ok = ok && n.zp_ok; } else if (CZ == -1) { off += n.zm; ok = ok && n.zm_ok; }
-  return off;
-}
-
-#define FOR_Q(M)                                                                                     \
-  M(0, 0, 0, 0) M(1, -1, 0, 0) M(2, 0, -1, 0) M(3, 0, 0, -1) M(4, -1, -1, 0) M(5, -1, 1, 0)          \
-  M(6, -1, 0, -1) M(7, -1, 0, 1) M(8, 0, -1, -1) M(9, 0, -1, 1) M(10, 1, 0, 0) M(11, 0, 1, 0)        \
-  M(12, 0, 0, 1) M(13, 1, 1, 0) M(14, 1, -1, 0) M(15, 1, 0, 1) M(16, 1, 0, -1) M(17, 0, 1, 1)        \
-  M(18, 0, 1, -1)
-
-__device__ __forceinline__ constexpr double tq(int q) { return q == 0 ? 1. / 3. : ((q >= 1 && q <= 3) || (q >= 10 && q <= 12)) ? 1. / 18. : 1. / 36.; }
-
-// gather the post-stream populations S(node, q) = P(node - c_q, q)
-__device__ __forceinline__ void pull(const double *__restrict__ fin, long npad, long node, const Nbr &n, double f[HC_Q]) {
-#define M(Q, CX, CY, CZ)                                   \
-  {                                                        \
-    bool ok; long off = src_off<CX, CY, CZ>(n, ok);        \
-    f[Q] = ok ? fin[(long)Q * npad + node + off] : 0.0;    \
-  }
-  FOR_Q(M)
-#undef M
-}
-
-// What an observer sees on an open lattice: the gathered populations of a fluid Zou-He node completed as the collide is about
-// to complete them, so that a velocity node reports u_bc (+ F / 2) and a pressure node its prescribed density instead of
-// moments that count the unknown populations as the zeros that came from outside.  Nothing without OPEN.
+// What an observer sees on a node: the gathered populations f -- on an open lattice those of a fluid Zou-He node completed as the
+// collide is about to complete them, so that a velocity node reports u_bc (+ F / 2) and a pressure node its prescribed density
+// instead of moments that count the unknown populations as the zeros that came from outside -- and their moments.
+struct Moments { double rhoBar, j0, j1, j2, invRho; };
 template <bool OPEN>
-__device__ __forceinline__ void complete_open(const Args<OPEN> &a, long node, double f[HC_Q]) {
+__device__ __forceinline__ Moments observe(const Args<OPEN> &a, int x, int y, int z, long node, double f[HC_Q]) {
+  pull(a.fin, a.qs, node, neighbours(a, x, y, z), f);
   if constexpr (OPEN) {
     if (a.mask[node] == 0) {
       const int code = a.ob_code[node];
       if (code >= 0) zou_he_node(f, code, a.ob_val);
     }
   }
-}
-
-// moments in the oracle's order: ascending q, zero-velocity components skipped
-__device__ __forceinline__ void moments(const double f[HC_Q], double &rhoBar, double &jx, double &jy, double &jz) {
-  double r = 0.0, x = 0.0, y = 0.0, z = 0.0;
-#define M(Q, CX, CY, CZ)              \
-  r += f[Q];                          \
-  if (CX == 1) x += f[Q]; else if (CX == -1) x += -f[Q]; \
-  if (CY == 1) y += f[Q]; else if (CY == -1) y += -f[Q]; \
-  if (CZ == 1) z += f[Q]; else if (CZ == -1) z += -f[Q];
-  FOR_Q(M)
-#undef M
-  rhoBar = r; jx = x; jy = y; jz = z;
-}
-
-template <int CX, int CY, int CZ>
-__device__ __forceinline__ double cdot(double a0, double a1, double a2) {
-  // ((cx*a0 + cy*a1) + cz*a2) with the zero terms dropped (exact)
-  double s = 0.0; bool first = true;
-  if (CX != 0) { s = (CX == 1 ? a0 : -a0); first = false; }
-  if (CY != 0) { double t = (CY == 1 ? a1 : -a1); s = first ? t : s + t; first = false; }
-  if (CZ != 0) { double t = (CZ == 1 ? a2 : -a2); s = first ? t : s + t; first = false; }
-  return s;
+  Moments m;
+  moments(f, m.rhoBar, m.j0, m.j1, m.j2);
+  m.invRho = 1.0 / (1.0 + m.rhoBar);
+  return m;
 }
 
 // GuoExternalForceBGKdynamics::collide, operation order of oracle/hemo_oracle.c collide_guo_bgk
@@ -330,20 +257,15 @@ __global__ void rho_u_kernel(Args<OPEN> a, double *rho, double *u) {
   const int x = a.x_begin + blockIdx.y;
   const int y = p / a.nz, z = p - y * a.nz;
   const long node = (long)(x + HALO) * a.xs + p;
-  const Nbr n = neighbours(a, x, y, z);
   double f[HC_Q];
-  pull(a.fin, a.qs, node, n, f);
-  complete_open<OPEN>(a, node, f);
-  double rhoBar, j0, j1, j2;
-  moments(f, rhoBar, j0, j1, j2);
-  const double invRho = 1.0 / (1.0 + rhoBar);
+  const Moments m = observe<OPEN>(a, x, y, z, node, f);
   const long o = (long)x * a.plane + p;
-  rho[o] = 1.0 + rhoBar;
+  rho[o] = 1.0 + m.rhoBar;
   double bx, by, bz;
   body_at(a, x, y, z, bx, by, bz);
-  u[3 * o] = j0 * invRho + (bx + a.Fin[3 * node]) / 2.0;
-  u[3 * o + 1] = j1 * invRho + (by + a.Fin[3 * node + 1]) / 2.0;
-  u[3 * o + 2] = j2 * invRho + (bz + a.Fin[3 * node + 2]) / 2.0;
+  u[3 * o] = m.j0 * m.invRho + (bx + a.Fin[3 * node]) / 2.0;
+  u[3 * o + 1] = m.j1 * m.invRho + (by + a.Fin[3 * node + 1]) / 2.0;
+  u[3 * o + 2] = m.j2 * m.invRho + (bz + a.Fin[3 * node + 2]) / 2.0;
 }
 
 // Off-equilibrium part of the momentum-flux tensor, as Palabos' momentTemplates::compute_rhoBar_j_PiNeq forms it from the
@@ -356,13 +278,9 @@ __global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
   const int x = a.x_begin + blockIdx.y;
   const int y = p / a.nz, z = p - y * a.nz;
   const long node = (long)(x + HALO) * a.xs + p;
-  const Nbr n = neighbours(a, x, y, z);
   double f[HC_Q];
-  pull(a.fin, a.qs, node, n, f);
-  complete_open<OPEN>(a, node, f);
-  double rhoBar, j0, j1, j2;
-  moments(f, rhoBar, j0, j1, j2);
-  const double invRho = 1.0 / (1.0 + rhoBar);
+  const Moments m = observe<OPEN>(a, x, y, z, node, f);
+  const double rhoBar = m.rhoBar, j0 = m.j0, j1 = m.j1, j2 = m.j2, invRho = m.invRho;
   double xx = 0, xy = 0, xz = 0, yy = 0, yz = 0, zz = 0;
 #define M(Q, CX, CY, CZ)                       \
   if (CX * CX) xx += f[Q];                     \
@@ -383,63 +301,31 @@ __global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
   pi[o + 5] = zz - invRho * j2 * j2 - cs2 * rhoBar;
 }
 
-// Cell::computeVelocity with the body force alone on node P of the plane coordinate[AXIS] == PLANE of the lattice `a`, into the
-// new variables u0, u1, u2.  P is the node's offset with the axis removed: y * nz + z, x * nz + z, x * ny + y for AXIS 0, 1, 2
-// (x local).  Bounce-back nodes give 0.  This is the one statement of the arithmetic: the plane-velocity kernels and the
-// pre-inlet coupling kernel below all expand it, so they cannot drift apart.  It is a macro and not a __device__ function
-// because the compiler inlines the helpers in another order through an intermediate function, and plane_velocity_kernel<false>
-// and <true> then come out with other scalar registers than before; expanded in place they are the code
-// they were, line for line.
-#define PLANE_NODE_VELOCITY(AXIS, PLANE, P)                                                       \
-  const int p = (P);                                                                              \
-  const int x = AXIS == 0 ? (PLANE) : AXIS == 1 ? p / a.nz : p / a.ny;                            \
-  const int y = AXIS == 0 ? p / a.nz : AXIS == 1 ? (PLANE) : p - x * a.ny;                        \
-  const int z = AXIS == 0 ? p - y * a.nz : AXIS == 1 ? p - x * a.nz : (PLANE);                    \
-  const long node = (long)(x + HALO) * a.xs + (AXIS == 0 ? p : y * a.nz + z);                     \
-  double u0 = 0.0, u1 = 0.0, u2 = 0.0;                                                            \
-  if (a.mask[node] == 0) {                                                                        \
-    const Nbr nb = neighbours(a, x, y, z);                                                        \
-    double f[HC_Q];                                                                               \
-    pull(a.fin, a.qs, node, nb, f);                                                               \
-    complete_open<OPEN>(a, node, f);                                                              \
-    double rhoBar, j0, j1, j2;                                                                    \
-    moments(f, rhoBar, j0, j1, j2);                                                               \
-    const double invRho = 1.0 / (1.0 + rhoBar);                                                   \
-    double bx, by, bz;                                                                            \
-    body_at(a, x, y, z, bx, by, bz);                                                              \
-    u0 = j0 * invRho + bx / 2.0; u1 = j1 * invRho + by / 2.0; u2 = j2 * invRho + bz / 2.0;        \
+// Cell::computeVelocity with the body force alone on the listed nodes of the plane coordinate[AXIS] == plane of the lattice `a`:
+// out[stride * k .. + 2] = u(node idx[k]).  idx[k] is the node's offset with the axis removed: y * nz + z, x * nz + z,
+// x * ny + y for AXIS 0, 1, 2 (x local); on a z plane consecutive nodes lie nz doubles apart, as in the Lees-Edwards layers, but
+// a plane is small.  Bounce-back nodes give 0.  hcl_plane_velocity[_axis] writes [n][3]; applyPreInlet on the device
+// (hcl_preinlet_apply) writes the velocity components of the domain's slots, [n][4], and leaves rho (component 3) alone.
+template <bool OPEN, int AXIS>
+__global__ void plane_velocity_kernel(Args<OPEN> a, int plane, const int *idx, int n, double *out, int stride) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const int p = idx[k];
+  const int x = AXIS == 0 ? plane : AXIS == 1 ? p / a.nz : p / a.ny;
+  const int y = AXIS == 0 ? p / a.nz : AXIS == 1 ? plane : p - x * a.ny;
+  const int z = AXIS == 0 ? p - y * a.nz : AXIS == 1 ? p - x * a.nz : plane;
+  const long node = (long)(x + HALO) * a.xs + (AXIS == 0 ? p : y * a.nz + z);
+  double u0 = 0.0, u1 = 0.0, u2 = 0.0;
+  if (a.mask[node] == 0) {
+    double f[HC_Q];
+    const Moments m = observe<OPEN>(a, x, y, z, node, f);
+    double bx, by, bz;
+    body_at(a, x, y, z, bx, by, bz);
+    u0 = m.j0 * m.invRho + bx / 2.0; u1 = m.j1 * m.invRho + by / 2.0; u2 = m.j2 * m.invRho + bz / 2.0;
   }
-
-// hcl_plane_velocity: listed nodes of one x plane; out [n][3]
-template <bool OPEN = false>
-__global__ void plane_velocity_kernel(Args<OPEN> a, int plane, const int *yz, int n, double *out) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= n) return;
-  PLANE_NODE_VELOCITY(0, plane, yz[k])
-  out[3L * k] = u0; out[3L * k + 1] = u1; out[3L * k + 2] = u2;
+  double *o = out + (long)stride * k;
+  o[0] = u0; o[1] = u1; o[2] = u2;
 }
-
-// hcl_plane_velocity_axis on a y plane (AXIS 1) or a z plane (AXIS 2).  On a z plane consecutive nodes lie nz doubles apart,
-// as in the Lees-Edwards layers; a plane is small
-template <bool OPEN, int AXIS>
-__global__ void plane_velocity_axis_kernel(Args<OPEN> a, int plane, const int *idx, int n, double *out) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= n) return;
-  PLANE_NODE_VELOCITY(AXIS, plane, idx[k])
-  out[3L * k] = u0; out[3L * k + 1] = u1; out[3L * k + 2] = u2;
-}
-
-// applyPreInlet on the device (hcl_preinlet_apply): the plane velocities of the pre-inlet lattice `a` at idx[0 .. n-1] go
-// straight into the velocity components of the domain's slots first .. first + n - 1; rho (component 3) is not touched
-template <bool OPEN, int AXIS>
-__global__ void preinlet_couple_kernel(Args<OPEN> a, int plane, const int *idx, int n, double *val, int first) {
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k >= n) return;
-  PLANE_NODE_VELOCITY(AXIS, plane, idx[k])
-  double *v = val + 4L * (first + k);
-  v[0] = u0; v[1] = u1; v[2] = u2;
-}
-#undef PLANE_NODE_VELOCITY
 
 // ob_val[first + i][c0 .. c0 + nc - 1] = src[i][0 .. nc - 1]
 __global__ void ob_set_kernel(double *val, int first, int n, const double *src, int c0, int nc) {
@@ -482,14 +368,9 @@ __global__ __launch_bounds__(256) void fluid_stats_kernel(Args<OPEN> a, int what
     if (a.ibm) { Fx = bx + a.Fin[3 * node]; Fy = by + a.Fin[3 * node + 1]; Fz = bz + a.Fin[3 * node + 2]; }
     double v0 = Fx, v1 = Fy, v2 = Fz;
     if (what == 0) {
-      const Nbr n = neighbours(a, x, y, z);
       double f[HC_Q];
-      pull(a.fin, a.qs, node, n, f);
-      complete_open<OPEN>(a, node, f);
-      double rhoBar, j0, j1, j2;
-      moments(f, rhoBar, j0, j1, j2);
-      const double invRho = 1.0 / (1.0 + rhoBar);
-      v0 = j0 * invRho + Fx / 2.0; v1 = j1 * invRho + Fy / 2.0; v2 = j2 * invRho + Fz / 2.0;
+      const Moments m = observe<OPEN>(a, x, y, z, node, f);
+      v0 = m.j0 * m.invRho + Fx / 2.0; v1 = m.j1 * m.invRho + Fy / 2.0; v2 = m.j2 * m.invRho + Fz / 2.0;
     }
     stat_add(acc, sqrt(v0 * v0 + v1 * v1 + v2 * v2));
   }
@@ -631,8 +512,8 @@ LatArgs make_args(const hc_lattice *L) {
   return a;
 }
 
-// the arguments of the open-boundary instantiations
-OpenArgs open_args(const hc_lattice *L, const LatArgs &a) {
+// the arguments of the open-boundary instantiations (hc::launch_open)
+OpenArgs open_of(const hc_lattice *L, const LatArgs &a) {
   OpenArgs o;
   static_cast<LatArgs &>(o) = a;
   o.ob_code = L->ob_code; o.ob_val = L->ob_val;
@@ -724,12 +605,11 @@ int launch_collide(hc_lattice *L, int x_begin, int nplanes, int x2 = 0, int n2 =
   if (n2 > 0) { a.x_split = nplanes; a.x_jump = x2 - (x_begin + nplanes); }
   const unsigned ny = (unsigned)(nplanes + n2);
   const dim3 grid((unsigned)((L->max_active + 255) / 256), ny, 1);
-  if (L->ob_n > 0) {
-    const OpenArgs o = open_args(L, a);
-    if (L->regions.n) hipLaunchKernelGGL((collide_stream_kernel<true, true>), grid, dim3(256), 0, hc::stream(), o);
-    else hipLaunchKernelGGL((collide_stream_kernel<false, true>), grid, dim3(256), 0, hc::stream(), o);
-  } else if (L->regions.n) hipLaunchKernelGGL(collide_stream_kernel<true>, grid, dim3(256), 0, hc::stream(), a);
-  else hipLaunchKernelGGL(collide_stream_kernel<false>, grid, dim3(256), 0, hc::stream(), a);
+  launch_open(L, a, [&](auto open, const auto &args) {
+    constexpr bool OPEN = decltype(open)::value;
+    if (L->regions.n) hipLaunchKernelGGL((collide_stream_kernel<true, OPEN>), grid, dim3(256), 0, hc::stream(), args);
+    else hipLaunchKernelGGL((collide_stream_kernel<false, OPEN>), grid, dim3(256), 0, hc::stream(), args);
+  });
   HC_HIP(hipGetLastError());
   return HC_OK;
 }
@@ -762,6 +642,36 @@ static bool le_layers_fluid(const hc_lattice *L, const uint8_t *mask, size_t xs)
   return true;
 }
 
+// every device buffer the lattice may hold; each is null until it exists
+hc_lattice::~hc_lattice() {
+  for (void *p : {(void *)f[0], (void *)f[1], (void *)force[0], (void *)force[1], (void *)force[2], (void *)fdirty[0], (void *)fdirty[1], (void *)fdirty[2],
+                  (void *)mask, (void *)scratch, (void *)row_z0, (void *)row_cum, (void *)blk_row, (void *)wallbrick, (void *)le_buf, (void *)ob_code,
+                  (void *)ob_val, (void *)ob_list, (void *)ob_out})
+    if (p) hipFree(p);
+}
+
+// The body of the hcl_download_* entry points: per_node doubles for every bulk node are written to the scratch buffer by
+// launch(scratch, bulk nodes) and copied from there to the host blocks of dst, one after the other.  refresh_halos: the kernel
+// gathers, and on a slab the post-stream view of the face planes pulls from the halo planes.
+struct HostBlock { double *ptr; size_t per_node; };
+template <class Launch>
+static int download(hc_lattice *L, bool refresh_halos, std::initializer_list<HostBlock> dst, Launch launch) {
+  if (refresh_halos && L->n_slabs > 1) { const int rc = hcl_slab_refresh_halos(L, 2); if (rc != HC_OK) return rc; }
+  const size_t n = (size_t)L->nx * L->plane;
+  size_t per_node = 0;
+  for (const HostBlock &b : dst) per_node += b.per_node;
+  const int rc = ensure_scratch(L, n * per_node); if (rc != HC_OK) return rc;
+  launch(L->scratch, n);
+  HC_HIP(hipGetLastError());
+  const double *src = L->scratch;
+  for (const HostBlock &b : dst) {
+    HC_HIP(hipMemcpyAsync(b.ptr, src, n * b.per_node * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+    src += n * b.per_node;
+  }
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  return HC_OK;
+}
+
 static int g_force_plane_padding = 0;   // tests / A-B runs: 1 = pad the planes of every lattice, -1 = of none, 0 = by size
 
 extern "C" {
@@ -776,7 +686,8 @@ int hcl_create(hc_lattice **out, int nx, int ny, int nz, const int periodic[3], 
   HC_REQUIRE((long)ny * nz < (1L << 30) && (long)(nx + 2 * HALO) * (((long)ny + 8) * nz + 32) < (1L << 31), "hcl_create: slab too large for 32-bit plane indexing");
   HC_REQUIRE(omega > 0.0 && omega < 2.0, "hcl_create: omega must be in (0,2)");
   if (hc::stream() == nullptr) { hc::set_error("hcl_create: hc_init() has not been called"); return HC_ERR_STATE; }
-  hc_lattice *L = new hc_lattice();
+  std::unique_ptr<hc_lattice> owner(new hc_lattice());   // an early return below frees whatever exists by then
+  hc_lattice *L = owner.get();
   L->nx = nx; L->ny = ny; L->nz = nz;
   for (int d = 0; d < 3; d++) L->periodic[d] = periodic[d] ? 1 : 0;
   L->x0 = x0; L->nx_global = nx_global; L->n_slabs = n_slabs;
@@ -800,9 +711,6 @@ int hcl_create(hc_lattice **out, int nx, int ny, int nz, const int periodic[3], 
   L->body[0] = L->body[1] = L->body[2] = 0.0;
   L->regions.n = 0;
   for (int c = 0; c < 4; c++) for (int d = 0; d < 3; d++) L->wall_u[c][d] = 0.0;
-  L->scratch = nullptr; L->scratch_doubles = 0;
-  L->f[0] = L->f[1] = nullptr; L->mask = nullptr;
-  for (int k = 0; k < 3; k++) { L->force[k] = nullptr; L->fdirty[k] = nullptr; }
   for (int k = 0; k < 2; k++) {
     HC_HIP(hipMalloc((void **)&L->f[k], L->qstride * HC_Q * sizeof(double)));
     HC_HIP(hipMemsetAsync(L->f[k], 0, L->qstride * HC_Q * sizeof(double), hc::stream()));
@@ -819,12 +727,11 @@ int hcl_create(hc_lattice **out, int nx, int ny, int nz, const int periodic[3], 
     L->fepoch[k] = 1;
   }
   L->hmask.assign(L->npad, 0);   // device numbering; hcl_set_mask marks the padding
-  L->row_z0 = L->row_cum = L->blk_row = nullptr;
-  L->wallbrick = nullptr; L->nbx = (nx + 2 * HALO + 7) / 8; L->nby = (ny + 7) / 8; L->nbz = (nz + 7) / 8;
+  L->nbx = (nx + 2 * HALO + 7) / 8; L->nby = (ny + 7) / 8; L->nbz = (nz + 7) / 8;
   { int rc = rebuild_active_map(L); if (rc != HC_OK) return rc; }
   { int rc = rebuild_wall_bricks(L); if (rc != HC_OK) return rc; }
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  *out = L;
+  *out = owner.release();
   return HC_OK;
 }
 
@@ -832,19 +739,6 @@ int hcl_destroy(hc_lattice *L) {
   if (!L) return HC_OK;
   hcs::lattice_destroyed(L);
   hipStreamSynchronize(hc::stream());
-  for (int k = 0; k < 2; k++) if (L->f[k]) hipFree(L->f[k]);
-  for (int k = 0; k < 3; k++) { if (L->force[k]) hipFree(L->force[k]); if (L->fdirty[k]) hipFree(L->fdirty[k]); }
-  if (L->mask) hipFree(L->mask);
-  if (L->scratch) hipFree(L->scratch);
-  if (L->row_z0) hipFree(L->row_z0);
-  if (L->row_cum) hipFree(L->row_cum);
-  if (L->blk_row) hipFree(L->blk_row);
-  if (L->wallbrick) hipFree(L->wallbrick);
-  if (L->le_buf) hipFree(L->le_buf);
-  if (L->ob_code) hipFree(L->ob_code);
-  if (L->ob_val) hipFree(L->ob_val);
-  if (L->ob_list) hipFree(L->ob_list);
-  if (L->ob_out) hipFree(L->ob_out);
   delete L;
   return HC_OK;
 }
@@ -884,7 +778,6 @@ int hcl_set_mask(hc_lattice *L, const uint8_t *mask_with_halo) {
   // where it came from, so such a node never exchanges anything with the fluid: the collide kernel skips
   // it (no loads, no stores).  Results on fluid nodes are unchanged, bit for bit.
   {
-    static const int cx[HC_Q] = HC_CX, cy[HC_Q] = HC_CY, cz[HC_Q] = HC_CZ;
     const int NX = L->nx + 2 * HALO, ny = L->ny, nz = L->nz;
     std::vector<uint8_t> cls(L->hmask);
     for (int x = 0; x < NX; x++)
@@ -894,7 +787,7 @@ int hcl_set_mask(hc_lattice *L, const uint8_t *mask_with_halo) {
           if (!L->hmask[k]) continue;
           bool fluid_near = false;
           for (int q = 1; q < HC_Q && !fluid_near; q++) {
-            int xx = x + cx[q], yy = y + cy[q], zz = z + cz[q];
+            int xx = x + HC_CX[q], yy = y + HC_CY[q], zz = z + HC_CZ[q];
             if (xx < 0 || xx >= NX) { fluid_near = true; break; }   // beyond the halo: unknown, keep the node active
             if (yy < 0 || yy >= ny) { if (L->periodic[1]) yy = (yy + ny) % ny; else continue; }
             if (zz < 0 || zz >= nz) { if (L->periodic[2]) zz = (zz + nz) % nz; else continue; }
@@ -1044,25 +937,21 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]) {
 // ---- Zou-He open boundaries (the completion is zou_he_node inside the collide)
 // room for `need` slots; the slots from ob_n on start at u = 0, rho = 1
 static int ob_grow(hc_lattice *L, int need) {
-  if (need <= L->ob_cap) {
-    if (need > L->ob_n) {
-      std::vector<double> init((size_t)(need - L->ob_n) * 4, 0.0);
-      for (size_t i = 0; i < init.size(); i += 4) init[i + 3] = 1.0;
-      HC_HIP(hipMemcpyAsync(L->ob_val + (size_t)L->ob_n * 4, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
-      HC_HIP(hipStreamSynchronize(hc::stream()));
-    }
-    return HC_OK;
+  if (need <= L->ob_n) return HC_OK;
+  const int cap = need <= L->ob_cap ? L->ob_cap : std::max(need, 2 * L->ob_cap);
+  double *v = L->ob_val;
+  if (cap > L->ob_cap) {
+    HC_HIP(hipMalloc((void **)&v, (size_t)cap * 4 * sizeof(double)));
+    if (L->ob_val && L->ob_n) HC_HIP(hipMemcpyAsync(v, L->ob_val, (size_t)L->ob_n * 4 * sizeof(double), hipMemcpyDeviceToDevice, hc::stream()));
   }
-  int cap = std::max(need, 2 * L->ob_cap);
-  double *v = nullptr;
-  HC_HIP(hipMalloc((void **)&v, (size_t)cap * 4 * sizeof(double)));
-  std::vector<double> init((size_t)(cap - L->ob_n) * 4, 0.0);
+  std::vector<double> init((size_t)(need - L->ob_n) * 4, 0.0);
   for (size_t i = 0; i < init.size(); i += 4) init[i + 3] = 1.0;   // u = 0, rho = 1
-  if (L->ob_val && L->ob_n) HC_HIP(hipMemcpyAsync(v, L->ob_val, (size_t)L->ob_n * 4 * sizeof(double), hipMemcpyDeviceToDevice, hc::stream()));
   HC_HIP(hipMemcpyAsync(v + (size_t)L->ob_n * 4, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  if (L->ob_val) HC_HIP(hipFree(L->ob_val));
-  L->ob_val = v; L->ob_cap = cap;
+  if (v != L->ob_val) {
+    if (L->ob_val) HC_HIP(hipFree(L->ob_val));
+    L->ob_val = v; L->ob_cap = cap;
+  }
   return HC_OK;
 }
 
@@ -1091,6 +980,12 @@ static int ob_set(hc_lattice *L, const char *what, int first, int n, const doubl
   return HC_OK;
 }
 
+// is the bulk node c = {x, y, z} inside the lattice?  *index: its element in the device numbering
+static bool ob_node(const hc_lattice *L, const int *c, size_t *index) {
+  *index = (size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2];
+  return c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz;
+}
+
 // who: the entry point the caller used, for the messages
 static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int orientation, const int *nodes, int n, int *first_slot) {
   HC_REQUIRE(L && (n == 0 || nodes), who + ": null pointer");
@@ -1107,9 +1002,7 @@ static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int
   {
     std::vector<size_t> seen((size_t)n);
     for (int i = 0; i < n; i++) {
-      const int *c = nodes + 3 * i;
-      HC_REQUIRE(c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz, who + ": node outside the lattice");
-      seen[(size_t)i] = (size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2];
+      HC_REQUIRE(ob_node(L, nodes + 3 * i, &seen[(size_t)i]), who + ": node outside the lattice");
       HC_REQUIRE(!L->ob_code || L->ob_hcode[seen[(size_t)i]] < 0, who + ": node declared twice (it is an open-boundary node already; hcl_open_boundary_clear removes all)");
     }
     std::sort(seen.begin(), seen.end());
@@ -1124,8 +1017,9 @@ static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int
   }
   const int k = (kind == HC_OB_PRESSURE ? 2 : 0) + (orientation > 0 ? 1 : 0);
   for (int i = 0; i < n; i++) {
-    const int *c = nodes + 3 * i;
-    L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]] = (axis << HC_OB_AXIS_SHIFT) | ((L->ob_n + i) << 2) | k;
+    size_t node;
+    ob_node(L, nodes + 3 * i, &node);   // checked above
+    L->ob_hcode[node] = (axis << HC_OB_AXIS_SHIFT) | ((L->ob_n + i) << 2) | k;
   }
   L->ob_n += n;
   HC_HIP(hipMemcpyAsync(L->ob_code, L->ob_hcode.data(), L->npad * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
@@ -1173,31 +1067,24 @@ int hcl_open_boundary_clear(hc_lattice *L) {
   return HC_OK;
 }
 
+// out[i] = part(code of node i), or -1 where the node is outside the lattice or no open-boundary node
+static void ob_lookup(const hc_lattice *L, const int *nodes, int n, int (*part)(int), int *out) {
+  for (int i = 0; i < n; i++) {
+    size_t node;
+    const int code = L->ob_code && ob_node(L, nodes + 3 * i, &node) ? L->ob_hcode[node] : -1;
+    out[i] = code < 0 ? -1 : part(code);
+  }
+}
+
 int hcl_open_boundary_slots(const hc_lattice *L, const int *nodes, int n, int *slots) {
   HC_REQUIRE(L && n >= 0 && (n == 0 || (nodes && slots)), "hcl_open_boundary_slots: bad arguments");
-  for (int i = 0; i < n; i++) {
-    const int *c = nodes + 3 * i;
-    int s = -1;
-    if (L->ob_code && c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz) {
-      const int code = L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]];
-      s = code < 0 ? -1 : (code & ((1 << HC_OB_AXIS_SHIFT) - 1)) >> 2;
-    }
-    slots[i] = s;
-  }
+  ob_lookup(L, nodes, n, ob_slot, slots);
   return HC_OK;
 }
 
 int hcl_open_boundary_axes(const hc_lattice *L, const int *nodes, int n, int *axes) {
   HC_REQUIRE(L && n >= 0 && (n == 0 || (nodes && axes)), "hcl_open_boundary_axes: bad arguments");
-  for (int i = 0; i < n; i++) {
-    const int *c = nodes + 3 * i;
-    int a = -1;
-    if (L->ob_code && c[0] >= 0 && c[0] < L->nx && c[1] >= 0 && c[1] < L->ny && c[2] >= 0 && c[2] < L->nz) {
-      const int code = L->ob_hcode[(size_t)(c[0] + HALO) * L->xs + (size_t)c[1] * L->nz + c[2]];
-      a = code < 0 ? -1 : code >> HC_OB_AXIS_SHIFT;
-    }
-    axes[i] = a;
-  }
+  ob_lookup(L, nodes, n, ob_axis, axes);
   return HC_OK;
 }
 
@@ -1222,7 +1109,22 @@ int hcl_open_boundary_values(hc_lattice *L, int first_slot, int n, double *out) 
 static size_t plane_nodes(const hc_lattice *L, int axis) { return axis == 0 ? L->plane : (size_t)L->nx * (axis == 1 ? L->nz : L->ny); }
 static int axis_extent(const hc_lattice *L, int axis) { return axis == 0 ? L->nx : axis == 1 ? L->ny : L->nz; }
 
-// who: the entry point the caller used, for the messages.  Axis 0 launches plane_velocity_kernel, as it always did
+// plane_velocity_kernel on the plane coordinate[axis] == plane of L: the one place that picks its instantiation
+static int launch_plane_velocity(const hc_lattice *L, int axis, int plane, const int *idx, int n, double *out, int stride) {
+  const dim3 grid((unsigned)((n + 255) / 256));
+  launch_open(L, make_args(L), [&](auto open, const auto &a) {
+    constexpr bool OPEN = decltype(open)::value;
+    switch (axis) {
+      case 0: hipLaunchKernelGGL((plane_velocity_kernel<OPEN, 0>), grid, dim3(256), 0, hc::stream(), a, plane, idx, n, out, stride); break;
+      case 1: hipLaunchKernelGGL((plane_velocity_kernel<OPEN, 1>), grid, dim3(256), 0, hc::stream(), a, plane, idx, n, out, stride); break;
+      default: hipLaunchKernelGGL((plane_velocity_kernel<OPEN, 2>), grid, dim3(256), 0, hc::stream(), a, plane, idx, n, out, stride); break;
+    }
+  });
+  HC_HIP(hipGetLastError());
+  return HC_OK;
+}
+
+// who: the entry point the caller used, for the messages
 static int plane_velocity(const std::string &who, hc_lattice *L, int axis, int plane, const int *idx, int n, double *out, int on_device) {
   HC_REQUIRE(L && n >= 0 && (n == 0 || (idx && out)), who + ": bad arguments");
   HC_REQUIRE(axis >= 0 && axis <= 2, who + ": axis must be 0, 1 or 2");
@@ -1234,18 +1136,7 @@ static int plane_velocity(const std::string &who, hc_lattice *L, int axis, int p
   HC_HIP(hipMemcpyAsync(L->ob_list, idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
   double *d = out;
   if (!on_device) { rc = ob_stage((void **)&L->ob_out, &L->ob_out_cap, 3 * sizeof(double), n); if (rc != HC_OK) return rc; d = L->ob_out; }
-  LatArgs a = make_args(L);
-  const dim3 grid((unsigned)((n + 255) / 256));
-  const int *list = L->ob_list;
-  if (L->ob_n > 0) {
-    const OpenArgs o = open_args(L, a);
-    if (axis == 0) hipLaunchKernelGGL(plane_velocity_kernel<true>, grid, dim3(256), 0, hc::stream(), o, plane, list, n, d);
-    else if (axis == 1) hipLaunchKernelGGL((plane_velocity_axis_kernel<true, 1>), grid, dim3(256), 0, hc::stream(), o, plane, list, n, d);
-    else hipLaunchKernelGGL((plane_velocity_axis_kernel<true, 2>), grid, dim3(256), 0, hc::stream(), o, plane, list, n, d);
-  } else if (axis == 0) hipLaunchKernelGGL(plane_velocity_kernel<false>, grid, dim3(256), 0, hc::stream(), a, plane, list, n, d);
-  else if (axis == 1) hipLaunchKernelGGL((plane_velocity_axis_kernel<false, 1>), grid, dim3(256), 0, hc::stream(), a, plane, list, n, d);
-  else hipLaunchKernelGGL((plane_velocity_axis_kernel<false, 2>), grid, dim3(256), 0, hc::stream(), a, plane, list, n, d);
-  HC_HIP(hipGetLastError());
+  if ((rc = launch_plane_velocity(L, axis, plane, L->ob_list, n, d, 3)) != HC_OK) return rc;
   if (!on_device) HC_HIP(hipMemcpyAsync(out, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));   // the staged node list is reused by the next call
   return HC_OK;
@@ -1263,9 +1154,10 @@ int hcl_plane_velocity_axis(hc_lattice *L, int axis, int plane, const int *idx, 
 struct hc_preinlet {
   hc_lattice *pre, *domain;   // not owned: the handle is destroyed before either lattice
   int axis, plane;            // the pre-inlet's plane coordinate[axis] == plane ...
-  int *idx;                   // ... and the in-plane indices of its coupled nodes [n], device
+  int *idx = nullptr;         // ... and the in-plane indices of its coupled nodes [n], device
   int n, first;               // the domain's velocity slots first .. first + n - 1
   long epoch;                 // the domain's ob_epoch at creation: hcl_open_boundary_clear moves it on
+  ~hc_preinlet() { if (idx) hipFree(idx); }
 };
 
 static bool preinlet_slots_gone(const hc_preinlet *P) { return P->epoch != P->domain->ob_epoch || (long)P->first + P->n > (long)P->domain->ob_n; }
@@ -1280,20 +1172,7 @@ static int preinlet_launch(const char *who, hc_preinlet *P) {
     return HC_ERR_STATE;
   }
   if (P->n == 0) return HC_OK;
-  const LatArgs a = make_args(pre);
-  const dim3 grid((unsigned)((P->n + 255) / 256));
-  const int *idx = P->idx;
-#define HC_COUPLE(OPEN, AXIS, ARGS) \
-  hipLaunchKernelGGL((preinlet_couple_kernel<OPEN, AXIS>), grid, dim3(256), 0, hc::stream(), ARGS, P->plane, idx, P->n, dom->ob_val, P->first)
-  if (pre->ob_n > 0) {
-    const OpenArgs o = open_args(pre, a);
-    if (P->axis == 0) HC_COUPLE(true, 0, o); else if (P->axis == 1) HC_COUPLE(true, 1, o); else HC_COUPLE(true, 2, o);
-  } else {
-    if (P->axis == 0) HC_COUPLE(false, 0, a); else if (P->axis == 1) HC_COUPLE(false, 1, a); else HC_COUPLE(false, 2, a);
-  }
-#undef HC_COUPLE
-  HC_HIP(hipGetLastError());
-  return HC_OK;
+  return launch_plane_velocity(pre, P->axis, P->plane, P->idx, P->n, dom->ob_val + 4L * P->first, 4);
 }
 
 int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, int axis, int pre_plane,
@@ -1308,23 +1187,21 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
     long found = 0;
     for (const int code : domain->ob_hcode) {
       if (code < 0) continue;
-      const int slot = (code & ((1 << HC_OB_AXIS_SHIFT) - 1)) >> 2;
-      if (slot < domain_first_slot || slot >= domain_first_slot + n) continue;
-      HC_REQUIRE((code & 2) == 0, "hcl_preinlet_create: a coupled slot is a pressure slot; the coupling sets velocities");
+      if (ob_slot(code) < domain_first_slot || ob_slot(code) >= domain_first_slot + n) continue;
+      HC_REQUIRE(!ob_is_pressure(code), "hcl_preinlet_create: a coupled slot is a pressure slot; the coupling sets velocities");
       found++;
     }
     HC_REQUIRE(found == n, "hcl_preinlet_create: a coupled slot has no node");
   }
-  hc_preinlet *P = new hc_preinlet();
-  P->pre = pre; P->domain = domain; P->axis = axis; P->plane = pre_plane; P->idx = nullptr; P->n = n; P->first = domain_first_slot;
+  std::unique_ptr<hc_preinlet> P(new hc_preinlet());
+  P->pre = pre; P->domain = domain; P->axis = axis; P->plane = pre_plane; P->n = n; P->first = domain_first_slot;
   P->epoch = domain->ob_epoch;
   if (n > 0) {
-    hipError_t e = hipMalloc((void **)&P->idx, (size_t)n * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpyAsync(P->idx, pre_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream());
-    if (e == hipSuccess) e = hipStreamSynchronize(hc::stream());   // the caller's list may go away after the call
-    if (e != hipSuccess) { if (P->idx) hipFree(P->idx); delete P; HC_HIP(e); }
+    HC_HIP(hipMalloc((void **)&P->idx, (size_t)n * sizeof(int)));
+    HC_HIP(hipMemcpyAsync(P->idx, pre_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
+    HC_HIP(hipStreamSynchronize(hc::stream()));   // the caller's list may go away after the call
   }
-  *out = P;
+  *out = P.release();
   return HC_OK;
 }
 
@@ -1347,22 +1224,15 @@ int hcl_preinlet_iterate(hc_preinlet *P, int n) {
 int hcl_preinlet_destroy(hc_preinlet *P) {
   if (!P) return HC_OK;
   hipStreamSynchronize(hc::stream());
-  if (P->idx) hipFree(P->idx);
   delete P;
   return HC_OK;
 }
 
 int hcl_download_populations(hc_lattice *L, double *f_aos) {
   HC_REQUIRE(L && f_aos, "hcl_download_populations: null pointer");
-  if (L->n_slabs > 1) { const int rc = hcl_slab_refresh_halos(L, 2); if (rc != HC_OK) return rc; }   // the post-stream view pulls from the halo planes
-  const size_t nd = (size_t)L->nx * L->plane * HC_Q;
-  int rc = ensure_scratch(L, nd); if (rc != HC_OK) return rc;
-  LatArgs a = make_args(L);
-  hipLaunchKernelGGL(download_kernel, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch);
-  HC_HIP(hipGetLastError());
-  HC_HIP(hipMemcpyAsync(f_aos, L->scratch, nd * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
-  HC_HIP(hipStreamSynchronize(hc::stream()));
-  return HC_OK;
+  return download(L, true, {{f_aos, HC_Q}}, [&](double *out, size_t) {
+    hipLaunchKernelGGL(download_kernel, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), make_args(L), out);
+  });
 }
 
 int hcl_upload_populations(hc_lattice *L, const double *f_aos) {
@@ -1394,43 +1264,27 @@ int hcl_upload_populations(hc_lattice *L, const double *f_aos) {
 
 int hcl_download_rho_u(hc_lattice *L, double *rho, double *u) {
   HC_REQUIRE(L && rho && u, "hcl_download_rho_u: null pointer");
-  if (L->n_slabs > 1) { const int rc = hcl_slab_refresh_halos(L, 2); if (rc != HC_OK) return rc; }
-  const size_t n = (size_t)L->nx * L->plane;
-  int rc = ensure_scratch(L, n * 4); if (rc != HC_OK) return rc;
-  LatArgs a = make_args(L);
-  if (L->ob_n > 0) hipLaunchKernelGGL(rho_u_kernel<true>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), open_args(L, a), L->scratch, L->scratch + n);
-  else hipLaunchKernelGGL(rho_u_kernel<false>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch, L->scratch + n);
-  HC_HIP(hipGetLastError());
-  HC_HIP(hipMemcpyAsync(rho, L->scratch, n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
-  HC_HIP(hipMemcpyAsync(u, L->scratch + n, 3 * n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
-  HC_HIP(hipStreamSynchronize(hc::stream()));
-  return HC_OK;
+  return download(L, true, {{rho, 1}, {u, 3}}, [&](double *out, size_t n) {
+    launch_open(L, make_args(L), [&](auto open, const auto &a) {
+      hipLaunchKernelGGL(rho_u_kernel<decltype(open)::value>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, out, out + n);
+    });
+  });
 }
 
 int hcl_download_pi_neq(hc_lattice *L, double *pi) {
   HC_REQUIRE(L && pi, "hcl_download_pi_neq: null pointer");
-  if (L->n_slabs > 1) { const int rc = hcl_slab_refresh_halos(L, 2); if (rc != HC_OK) return rc; }
-  const size_t n = (size_t)L->nx * L->plane;
-  int rc = ensure_scratch(L, n * 6); if (rc != HC_OK) return rc;
-  LatArgs a = make_args(L);
-  if (L->ob_n > 0) hipLaunchKernelGGL(pi_neq_kernel<true>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), open_args(L, a), L->scratch);
-  else hipLaunchKernelGGL(pi_neq_kernel<false>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch);
-  HC_HIP(hipGetLastError());
-  HC_HIP(hipMemcpyAsync(pi, L->scratch, 6 * n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
-  HC_HIP(hipStreamSynchronize(hc::stream()));
-  return HC_OK;
+  return download(L, true, {{pi, 6}}, [&](double *out, size_t) {
+    launch_open(L, make_args(L), [&](auto open, const auto &a) {
+      hipLaunchKernelGGL(pi_neq_kernel<decltype(open)::value>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, out);
+    });
+  });
 }
 
 int hcl_download_ibm_force(hc_lattice *L, double *F) {
   HC_REQUIRE(L && F, "hcl_download_ibm_force: null pointer");
-  const size_t n = (size_t)L->nx * L->plane;
-  int rc = ensure_scratch(L, n * 3); if (rc != HC_OK) return rc;
-  LatArgs a = make_args(L);
-  hipLaunchKernelGGL(force_aos_kernel, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, L->scratch);
-  HC_HIP(hipGetLastError());
-  HC_HIP(hipMemcpyAsync(F, L->scratch, 3 * n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
-  HC_HIP(hipStreamSynchronize(hc::stream()));
-  return HC_OK;
+  return download(L, false, {{F, 3}}, [&](double *out, size_t) {
+    hipLaunchKernelGGL(force_aos_kernel, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), make_args(L), out);
+  });
 }
 
 int hcl_zero_ibm_force(hc_lattice *L) {
@@ -1443,9 +1297,9 @@ int hcl_fluid_stats(hc_lattice *L, int what, double out[3], long *n_nodes) {
   HC_REQUIRE(L && out && n_nodes && what >= 0 && what <= 2, "hcl_fluid_stats: bad arguments");
   if (L->n_slabs > 1 && what == 0) { const int rc0 = hcl_slab_refresh_halos(L, 1); if (rc0 != HC_OK) return rc0; }   // velocities on the face planes pull from the halos
   int rc = ensure_scratch(L, (size_t)STAT_BLOCKS * 4); if (rc != HC_OK) return rc;
-  LatArgs a = make_args(L);
-  if (L->ob_n > 0) hipLaunchKernelGGL(fluid_stats_kernel<true>, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), open_args(L, a), what, L->scratch);
-  else hipLaunchKernelGGL(fluid_stats_kernel<false>, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), a, what, L->scratch);
+  launch_open(L, make_args(L), [&](auto open, const auto &a) {
+    hipLaunchKernelGGL(fluid_stats_kernel<decltype(open)::value>, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), a, what, L->scratch);
+  });
   HC_HIP(hipGetLastError());
   return hc::stat_finish(L->scratch, out, n_nodes);
 }
@@ -1460,54 +1314,47 @@ size_t hcl_halo_doubles(const hc_lattice *L, int width) {
 // with c_x = 0 from the face plane itself, the 5 moving towards the neighbour from the plane behind it, and the 5 moving
 // away from the neighbour out of the neighbour's own first plane; the neighbour's next collide pulls the 5 moving towards
 // it from the face plane.  So 14 populations of the face plane and 5 of the plane behind travel: 19 planes, not 24.
-static int halo_copy(hc_lattice *L, int side, int width, double *buf, int to_buf, int next = 0) {
-  HC_REQUIRE(L && buf, "hcl_halo: null pointer");
-  HC_REQUIRE((side == 0 || side == 1) && (width == 1 || width == 2), "hcl_halo: side must be 0/1 and width 1/2");
-  HC_REQUIRE(L->nx >= 2 * width, "hcl_halo: slab thinner than the halo");
+// appends the (population, plane) entries of one face's message to h
+static void halo_entries(const hc_lattice *L, int side, int width, int to_buf, HaloArgs &h) {
   static const int cxm[5] = {1, 4, 5, 6, 7};        // c_x = -1
   static const int cxp[5] = {10, 13, 14, 15, 16};   // c_x = +1
-  HaloArgs h;
-  h.f = L->f[next ? 1 - L->cur : L->cur]; h.buf = buf; h.buf2 = nullptr; h.n_first = 0x7fffffff; h.npad = (long)L->qstride; h.xs = (long)L->xs; h.plane = (int)L->plane; h.to_buf = to_buf; h.n = 0;
   // the populations that travel towards -x (cxm) leave through the low face and arrive in the low neighbour's high
   // halo; those towards +x (cxp) the other way round
   const int *moving = to_buf ? (side == 0 ? cxm : cxp) : (side == 0 ? cxp : cxm);
   // plane next to the face (bulk side when packing, halo side when unpacking) and the one behind it
   const int near = to_buf ? (side == 0 ? HALO : HALO + L->nx - 1) : (side == 0 ? HALO - 1 : HALO + L->nx);
   const int far = to_buf ? (side == 0 ? HALO + 1 : HALO + L->nx - 2) : (side == 0 ? HALO - 2 : HALO + L->nx + 1);
-  if (width == 1) {
-    for (int k = 0; k < 5; k++) { h.pop[h.n] = moving[k]; h.xp[h.n] = near; h.n++; }
-  } else {
-    static const int cx[HC_Q] = HC_CX;
-    for (int q = 0; q < HC_Q; q++) {
-      bool towards = false;
-      for (int k = 0; k < 5; k++) towards = towards || moving[k] == q;
-      if (cx[q] == 0 || towards) { h.pop[h.n] = q; h.xp[h.n] = near; h.n++; }
-    }
-    for (int k = 0; k < 5; k++) { h.pop[h.n] = moving[k]; h.xp[h.n] = far; h.n++; }
+  if (width == 2) {
+    for (int q = 0; q < HC_Q; q++)
+      if (HC_CX[q] == 0 || HC_CX[q] == HC_CX[moving[0]]) { h.pop[h.n] = q; h.xp[h.n] = near; h.n++; }
   }
+  for (int k = 0; k < 5; k++) { h.pop[h.n] = moving[k]; h.xp[h.n] = width == 1 ? near : far; h.n++; }
+}
+// packs (to_buf) or unpacks the entries of h, entries e >= n_first through buf_hi
+static int halo_launch(hc_lattice *L, HaloArgs &h, double *buf, double *buf_hi, int n_first, int to_buf, int next) {
+  h.f = L->f[next ? 1 - L->cur : L->cur]; h.buf = buf; h.buf2 = buf_hi; h.n_first = n_first;
+  h.npad = (long)L->qstride; h.xs = (long)L->xs; h.plane = (int)L->plane; h.to_buf = to_buf;
+  if (h.n == 0) return HC_OK;
   hipLaunchKernelGGL(halo_copy_kernel, dim3((unsigned)((L->plane + 255) / 256), (unsigned)h.n, 1), dim3(256), 0, hc::stream(), h);
   HC_HIP(hipGetLastError());
   return HC_OK;
+}
+static int halo_copy(hc_lattice *L, int side, int width, double *buf, int to_buf, int next = 0) {
+  HC_REQUIRE(L && buf, "hcl_halo: null pointer");
+  HC_REQUIRE((side == 0 || side == 1) && (width == 1 || width == 2), "hcl_halo: side must be 0/1 and width 1/2");
+  HC_REQUIRE(L->nx >= 2 * width, "hcl_halo: slab thinner than the halo");
+  HaloArgs h; h.n = 0;
+  halo_entries(L, side, width, to_buf, h);
+  return halo_launch(L, h, buf, nullptr, 0x7fffffff, to_buf, next);
 }
 // the width-1 message of both faces in one launch (either buffer may be null: a slab at a non-periodic end of the domain)
 static int halo_copy_both(hc_lattice *L, double *buf_lo, double *buf_hi, int to_buf, int next) {
   HC_REQUIRE(L, "hcl_halo: null pointer");
   HC_REQUIRE(L->nx >= 2, "hcl_halo: slab thinner than the halo");
-  static const int cxm[5] = {1, 4, 5, 6, 7};        // c_x = -1
-  static const int cxp[5] = {10, 13, 14, 15, 16};   // c_x = +1
-  HaloArgs h;
-  h.f = L->f[next ? 1 - L->cur : L->cur]; h.npad = (long)L->qstride; h.xs = (long)L->xs; h.plane = (int)L->plane; h.to_buf = to_buf; h.n = 0;
-  h.buf = buf_lo; h.buf2 = buf_hi; h.n_first = buf_lo ? 5 : 0;
-  for (int side = 0; side < 2; side++) {
-    if (!(side == 0 ? buf_lo : buf_hi)) continue;
-    const int *moving = to_buf ? (side == 0 ? cxm : cxp) : (side == 0 ? cxp : cxm);
-    const int near = to_buf ? (side == 0 ? HALO : HALO + L->nx - 1) : (side == 0 ? HALO - 1 : HALO + L->nx);
-    for (int k = 0; k < 5; k++) { h.pop[h.n] = moving[k]; h.xp[h.n] = near; h.n++; }
-  }
-  if (h.n == 0) return HC_OK;
-  hipLaunchKernelGGL(halo_copy_kernel, dim3((unsigned)((L->plane + 255) / 256), (unsigned)h.n, 1), dim3(256), 0, hc::stream(), h);
-  HC_HIP(hipGetLastError());
-  return HC_OK;
+  HaloArgs h; h.n = 0;
+  if (buf_lo) halo_entries(L, 0, 1, to_buf, h);
+  if (buf_hi) halo_entries(L, 1, 1, to_buf, h);
+  return halo_launch(L, h, buf_lo, buf_hi, buf_lo ? 5 : 0, to_buf, next);
 }
 int hcl_halo_pack_both(hc_lattice *L, double *dev_lo, double *dev_hi, int next) { return halo_copy_both(L, dev_lo, dev_hi, 1, next); }
 int hcl_halo_unpack_both(hc_lattice *L, const double *dev_lo, const double *dev_hi) { return halo_copy_both(L, (double *)dev_lo, (double *)dev_hi, 0, 0); }

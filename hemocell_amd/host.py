@@ -42,6 +42,11 @@ PLT_INNER_EDGES = np.array([[60, 65], [62, 64], [37, 42], [54, 56], [34, 40], [2
 _initialised = False
 
 
+def _iptr(array):
+    """a C int pointer to a contiguous numpy int32 array"""
+    return array.ctypes.data_as(C.POINTER(C.c_int))
+
+
 def read_material(path):
     """<MaterialModel> of a cell XML: {tag: float} for the numeric tags and "inner_edges" as an [n][2] int64 array
     (mechanics/commonCellConstants.cpp:139-153 reads <InnerEdges><Edge> a b </Edge>...)"""
@@ -133,7 +138,7 @@ class Lattice:
         bb = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 6)
         ff = np.ascontiguousarray(forces, dtype=np.float64).reshape(-1, 3)
         assert len(bb) == len(ff)
-        check(self.lib.hcl_set_body_force_regions(self.ptr, len(bb), bb.ctypes.data_as(C.POINTER(C.c_int)), dptr(ff)))
+        check(self.lib.hcl_set_body_force_regions(self.ptr, len(bb), _iptr(bb), dptr(ff)))
 
     def setBoundaryVelocity(self, wall_class, u):
         """wall_class an int: velocity of the nodes whose mask value is wall_class (3..6).  Otherwise wall_class is an
@@ -194,15 +199,14 @@ class Lattice:
         nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
         first = C.c_int()
         check(self.lib.hcl_open_boundary_add_axis(self.ptr, int(kind), int(axis), int(orientation),
-                                                  nn.ctypes.data_as(C.POINTER(C.c_int)), len(nn), C.byref(first)))
+                                                  _iptr(nn), len(nn), C.byref(first)))
         return first.value
 
     def openBoundaryAxes(self, nodes):
         """the axis (0, 1, 2) on which each node of [n][3] was declared, or -1"""
         nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
         out = np.empty(len(nn), np.int32)
-        check(self.lib.hcl_open_boundary_axes(self.ptr, nn.ctypes.data_as(C.POINTER(C.c_int)), len(nn),
-                                              out.ctypes.data_as(C.POINTER(C.c_int))))
+        check(self.lib.hcl_open_boundary_axes(self.ptr, _iptr(nn), len(nn), _iptr(out)))
         return out
 
     def clearOpenBoundaries(self):
@@ -211,8 +215,7 @@ class Lattice:
     def openBoundarySlots(self, nodes):
         nn = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1, 3)
         out = np.empty(len(nn), np.int32)
-        check(self.lib.hcl_open_boundary_slots(self.ptr, nn.ctypes.data_as(C.POINTER(C.c_int)), len(nn),
-                                               out.ctypes.data_as(C.POINTER(C.c_int))))
+        check(self.lib.hcl_open_boundary_slots(self.ptr, _iptr(nn), len(nn), _iptr(out)))
         return out
 
     def setOpenBoundaryVelocitySlots(self, first_slot, u):
@@ -233,7 +236,7 @@ class Lattice:
         """Cell::computeVelocity (u = j/rho + F/2, F the body force) on in-plane indices y * nz + z of plane x: [n][3]"""
         ii = np.ascontiguousarray(yz, dtype=np.int32).reshape(-1)
         out = np.empty((len(ii), 3))
-        check(self.lib.hcl_plane_velocity(self.ptr, int(x), ii.ctypes.data_as(C.POINTER(C.c_int)), len(ii), out.ctypes.data, 0))
+        check(self.lib.hcl_plane_velocity(self.ptr, int(x), _iptr(ii), len(ii), out.ctypes.data, 0))
         return out
 
     def planeVelocityAxis(self, axis, plane, idx):
@@ -241,7 +244,7 @@ class Lattice:
         (y * nz + z, x * nz + z, x * ny + y for axis 0, 1, 2): [n][3]"""
         ii = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
         out = np.empty((len(ii), 3))
-        check(self.lib.hcl_plane_velocity_axis(self.ptr, int(axis), int(plane), ii.ctypes.data_as(C.POINTER(C.c_int)), len(ii),
+        check(self.lib.hcl_plane_velocity_axis(self.ptr, int(axis), int(plane), _iptr(ii), len(ii),
                                                out.ctypes.data, 0))
         return out
 
@@ -383,10 +386,8 @@ def preinlet_driving_force(Re, nu_lbm, fluid_area, direction="Xpos"):
     8 nu (u_max / 2) / R / R in the reference's operation order, along -x for Xpos and +x for Xneg.  Returns (R, u_max, F_x)."""
     if direction not in ("Xpos", "Xneg"):
         raise HcError("PreInlet: only the directions Xpos and Xneg are supported")
-    radius = math.sqrt(fluid_area / math.pi)
-    u_max = Re * nu_lbm / (radius * 2)
-    force = 8 * nu_lbm * (u_max * 0.5) / radius / radius
-    return radius, u_max, (-force if direction == "Xpos" else force)
+    radius, u_max, F = preinlet_driving_force_vector(Re, nu_lbm, fluid_area, direction)
+    return radius, u_max, F[0]
 
 
 # the reference's six Direction values (helper/preInlet.h): name -> (axis, -1 for *neg / +1 for *pos)
@@ -400,8 +401,8 @@ def _preinlet_direction(direction):
 
 
 def preinlet_driving_force_vector(Re, nu_lbm, fluid_area, direction):
-    """preinlet_driving_force in any of the six directions: the same three operations in the same order
-    (PreInlet::calculateDrivingForce), the force on the direction's axis, + for *neg and - for *pos (setDrivingForce), zero
+    """preinlet_driving_force in any of the six directions (PreInlet::calculateDrivingForce in the reference's operation
+    order): the force on the direction's axis, + for *neg and - for *pos (setDrivingForce), zero
     on the other axes.  Returns (R, u_max, (F_x, F_y, F_z))."""
     axis, sign = _preinlet_direction(direction)
     radius = math.sqrt(fluid_area / math.pi)
@@ -463,7 +464,7 @@ class PreInlet:
         if self.device:
             ptr = C.c_void_p()
             check(capi.lib().hcl_preinlet_create(C.byref(ptr), preinlet.ptr, domain.ptr, axis, self.pre_x,
-                                                 self.pre_yz.ctypes.data_as(C.POINTER(C.c_int)), len(self.pre_yz), self.first))
+                                                 _iptr(self.pre_yz), len(self.pre_yz), self.first))
             self.ptr = ptr
 
     def applyPreInlet(self):

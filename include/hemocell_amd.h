@@ -60,7 +60,7 @@ int hc_set_overlap(int on);
 int hc_profile_enable(int on);
 int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics", "lees_edwards" (both kernels of the pass) */
 int hc_profile_reset(void);
-/* identifies the build of the dominant kernel: first 16 hex digits of the SHA-256 of csrc/lattice.hip (a committed PMC
+/* identifies the build of the dominant kernel: first 16 hex digits of the SHA-256 of csrc/lattice.hip and csrc/d3q19.h (a committed PMC
  * traffic figure is only quoted next to a timing when it was measured on the same kernel) */
 const char *hc_build_tag(void);
 /* device-to-device copy of `bytes` on the library stream, `repeats` times: read + written GB/s of the GPU in hand */
