@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units that work on membrane vertices
 // (cells.hip: storage and stepping, ibm.hip: spread / interpolate, mechanics.hip: membrane models,
-// exchange.hip: slab envelopes and statistics, repulsion.hip: vertex-vertex and boundary repulsion).
+// exchange.hip: slab envelopes and statistics, repulsion.hip: vertex-vertex and boundary repulsion,
+// preinlet.hip: cell injection and the outflow sink).
 //
 // Layout (HBM): vertices are a structure of arrays pos/vel/frc[3][n], cell major (a cell's nv vertices are
 // contiguous, cells of one type contiguous in a fixed-capacity region), so a wavefront touches 64 consecutive
@@ -211,6 +212,7 @@ VertArrays vert_arrays(hc_cells *C, int t);
 // stage a small host int array on the device in a persistent scratch slot (through a pinned block; stream ordered)
 int stage_ints(hc_cells *C, int which, int **d, const int *h, int n);
 void host_append_state(hc_cells *C, int type, long cell_id);
+int append_cells(hc_cells *C, int type, const long *cell_ids, const int *is_new, int n, long n_new);   // exchange.hip: n_new cells join the end of a type's region (is_new null: all n)
 int interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n, int which);   // ibm.hip: hcp_interpolate_cells through staging slot `which`
 
 }  // namespace hcc

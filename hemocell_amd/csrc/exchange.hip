@@ -134,6 +134,32 @@ static int stat_scratch(hc_cells *C) {
   return HC_OK;
 }
 
+namespace hcc {
+// n_new cells join the end of a type's region: ids [n] with is_new [n] marking the ones that do (null: all of them).  Within
+// capacity only the host's books change (fast path); otherwise the device regions grow through the host staging.  The
+// caller writes the new slots' vertices, tag and dead flags afterwards.
+int append_cells(hc_cells *C, int type, const long *cell_ids, const int *is_new, int n, long n_new) {
+  int rc;
+  if (C->ncells[type] + n_new > C->capc[type]) {
+    // slow path: grow the device regions through the host staging
+    rc = sync_to_host(C); if (rc != HC_OK) return rc;
+    const size_t add = (size_t)C->types[type]->host.nv * 3;
+    for (int i = 0; i < n; i++) {
+      if (is_new && !is_new[i]) continue;
+      C->hpos[type].resize(C->hpos[type].size() + add, 0.0); C->hvel[type].resize(C->hvel[type].size() + add, 0.0); C->hfrc[type].resize(C->hfrc[type].size() + add, 0.0);
+      host_append_state(C, type, cell_ids[i]);   // id, deletion state and force_repulsion grow with the vertices: the state of the cells already here survives
+    }
+    C->host_dirty = true;
+    rc = sync_to_device(C); if (rc != HC_OK) return rc;
+  } else {
+    for (int i = 0; i < n; i++) if (!is_new || is_new[i]) C->hids[type].push_back(cell_ids[i]);
+    C->ncells[type] += n_new;
+    C->nverts += n_new * C->types[type]->host.nv;
+  }
+  return HC_OK;
+}
+}  // namespace hcc
+
 extern "C" {
 
 // The kernel and the copy into pinned staging are enqueued and the call returns; _end waits for that copy alone (an
@@ -211,22 +237,7 @@ int hcp_unpack_cells(hc_cells *C, int type, const int *slots, const long *cell_i
     if (is_new[i]) { HC_REQUIRE(slots[i] == C->ncells[type] + n_new, "hcp_unpack_cells: new cells must be appended in slot order"); n_new++; }
     else HC_REQUIRE(slots[i] >= 0 && slots[i] < C->ncells[type], "hcp_unpack_cells: slot out of range");
   }
-  if (C->ncells[type] + n_new > C->capc[type]) {
-    // slow path: grow the device regions through the host staging
-    rc = sync_to_host(C); if (rc != HC_OK) return rc;
-    const size_t add = (size_t)C->types[type]->host.nv * 3;
-    for (int i = 0; i < n; i++) {
-      if (!is_new[i]) continue;
-      C->hpos[type].resize(C->hpos[type].size() + add, 0.0); C->hvel[type].resize(C->hvel[type].size() + add, 0.0); C->hfrc[type].resize(C->hfrc[type].size() + add, 0.0);
-      host_append_state(C, type, cell_ids[i]);   // id, deletion state and force_repulsion grow with the vertices: the state of the cells already here survives
-    }
-    C->host_dirty = true;
-    rc = sync_to_device(C); if (rc != HC_OK) return rc;
-  } else {
-    for (int i = 0; i < n; i++) if (is_new[i]) C->hids[type].push_back(cell_ids[i]);
-    C->ncells[type] += n_new;
-    C->nverts += n_new * C->types[type]->host.nv;
-  }
+  rc = append_cells(C, type, cell_ids, is_new, n, n_new); if (rc != HC_OK) return rc;
   int *d_slots = nullptr, *d_new = nullptr;
   rc = stage_ints(C, 0, &d_slots, slots, n); if (rc != HC_OK) return rc;
   rc = stage_ints(C, 1, &d_new, is_new, n); if (rc != HC_OK) return rc;

@@ -437,11 +437,26 @@ class PreInlet:
     (two waits for the stream per iteration); it and iterate return the velocities sent.  device=True: an hc_preinlet handle
     (hcl_preinlet_*) does the exchange in one kernel, iterate(n) queues all n iterations in one call, and both return None;
     sent() reads the slots back either way.  A device coupling holds pointers into both lattices: destroy() it before them.
-    Cells do not cross yet: the coupling is the fluid's."""
+    Cells cross with cells=(pre_cells, domain_cells) (device=True only; helper/preInlet.cpp:254-351,
+    applyPreInletParticleBoundary): a complete cell of the pre-inlet whose whole vertex set lies in window=(lo, hi) along the
+    axis, positions taken modulo the pre-inlet's length lap by lap, is copied into the domain at p + shift with the id
+    id + (lap - sign) * id_stride; sink=plane removes the domain's cells that reach past that plane downstream.  iterate(n) is
+    then one hc_preinlet_iterate -- both systems step with their cells (particle_timescale, force_limit,
+    deletion_check_every), the fluid is handed over, and every cells_every iterations the cells are checked (one host wait per
+    check); applyPreInletCells() is one check, cell_counts() = (injected, rejected, removed by the sink, checks).  Partly
+    arrived cells are never added.  Without cells= the coupling is the fluid's alone."""
 
     def __init__(self, preinlet, domain, yz, pre_x, domain_x, direction="Xpos", pre_origin=(0, 0), domain_origin=(0, 0),
-                 device=False):
+                 device=False, cells=None, window=None, shift=(0.0, 0.0, 0.0), id_stride=None, sink=None, cells_every=1,
+                 particle_timescale=1, force_limit=True, deletion_check_every=1):
         axis, sign = _preinlet_direction(direction)
+        if cells is not None:
+            if not device:
+                raise HcError("PreInlet: cells= needs device=True (the cells cross on the device)")
+            if window is None or id_stride is None:
+                raise HcError("PreInlet: cells= needs window=(lo, hi) and id_stride=")
+            if int(cells_every) < 1:
+                raise HcError("PreInlet: cells_every must be >= 1")
         self.pre, self.domain = preinlet, domain   # kept alive as long as the coupling
         self.axis, self.device, self.ptr = axis, bool(device), None
         others = [d for d in range(3) if d != axis]
@@ -466,6 +481,38 @@ class PreInlet:
             check(capi.lib().hcl_preinlet_create(C.byref(ptr), preinlet.ptr, domain.ptr, axis, self.pre_x,
                                                  _iptr(self.pre_yz), len(self.pre_yz), self.first))
             self.ptr = ptr
+        if cells is not None:
+            self.cells, self.cells_ptr, self.iter = tuple(cells), None, 0
+            self.cells_every, self.particle_timescale = int(cells_every), int(particle_timescale)
+            self.force_limit, self.deletion_check_every = bool(force_limit), int(deletion_check_every)
+            sh = np.array(shift, dtype=np.float64).reshape(3)
+            xp = C.c_void_p()
+            try:
+                check(capi.lib().hcp_preinlet_create(C.byref(xp), self.cells[0].ptr, self.cells[1].ptr, axis, sign,
+                                                     float(window[0]), float(window[1]), dptr(sh), int(id_stride)))
+                self.cells_ptr = xp
+                if sink is not None:
+                    check(capi.lib().hcp_preinlet_set_sink(xp, 1, float(sink)))
+            except HcError:
+                self.destroy()
+                raise
+
+    def applyPreInletCells(self):
+        """one check: the sink, then the injection; returns (cells injected, cells removed by the sink)"""
+        a, b = C.c_long(), C.c_long()
+        check(capi.lib().hcp_preinlet_apply(self._cells_handle(), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def cell_counts(self):
+        """(cells injected, rejected, removed by the sink, checks) since the coupling was made"""
+        out = np.zeros(4, dtype=np.int64)
+        check(capi.lib().hcp_preinlet_counts(self._cells_handle(), lptr(out)))
+        return tuple(int(v) for v in out)
+
+    def _cells_handle(self):
+        if getattr(self, "cells_ptr", None) is None:
+            raise HcError("PreInlet: no cell coupling (cells= was not given, or it has been destroyed)")
+        return self.cells_ptr
 
     def applyPreInlet(self):
         if self.device:
@@ -478,6 +525,14 @@ class PreInlet:
     def iterate(self, n=1):
         """n iterations of (pre-inlet step, domain step, applyPreInlet).  Host path: returns the last plane velocities sent;
         device path: one hcl_preinlet_iterate, nothing waits for the device, returns None"""
+        if getattr(self, "cells_ptr", None) is not None:
+            it = C.c_long(self.iter)
+            try:
+                check(capi.lib().hc_preinlet_iterate(self._handle(), self.cells_ptr, C.byref(it), int(n), self.particle_timescale,
+                                                     int(self.force_limit), self.deletion_check_every, self.cells_every))
+            finally:
+                self.iter = it.value
+            return None
         if self.device:
             check(capi.lib().hcl_preinlet_iterate(self._handle(), int(n)))
             return None
@@ -498,7 +553,10 @@ class PreInlet:
         return self.ptr
 
     def destroy(self):
-        """frees the device coupling, if any; call it before destroying either lattice"""
+        """frees the device coupling, if any; call it before destroying either lattice or cell container"""
+        if getattr(self, "cells_ptr", None) is not None:
+            check(capi.lib().hcp_preinlet_destroy(self.cells_ptr))
+            self.cells_ptr = None
         if self.ptr is not None:
             check(capi.lib().hcl_preinlet_destroy(self.ptr))
             self.ptr = None

@@ -491,6 +491,41 @@ int hcp_unpack_cells(hc_cells *C, int type, const int *slots, const long *cell_i
 int hcp_remove_cells(hc_cells *C, int type, const int *slots, int n);
 int hcp_owned_vertices(hc_cells *C, long *n_owned); /* vertices whose nearest node lies in this slab */
 
+/* ---- the pre-inlet's cells (helper/preInlet.cpp:254-351, applyPreInletParticleBoundary; the offsets of
+ * core/hemoCellParticleDataTransfer.cpp:33-65, 229-260).  Positions are kept unwrapped, so a cell of the periodic pre-inlet `pre`
+ * that went `lap` times round its Lp nodes along `axis` sits at lap * Lp + (its place in the box): with cmin, cmax its extent
+ * on the axis, lap = floor(cmin / Lp), and the cell is a candidate when it is complete and lies wholly in the window,
+ * cmin - lap * Lp >= window_lo and cmax - lap * Lp <= window_hi.  A candidate arrives in `domain` at p + shift, on the axis at
+ * p + (shift[axis] - lap * Lp), with the id id + (lap - orientation) * id_stride (orientation -1: a *neg direction, +1: *pos;
+ * the offset of getOffset, positive for *neg), its velocity, force and force_repulsion copied, complete and alive.  Recorded
+ * deviation: the reference copies single particles and deletes partly arrived cells later; here a cell is added only when
+ * its id is absent and its WHOLE vertex set lies in the window -- partly arrived cells are never added.
+ * create checks and refuses (HC_ERR_ARG, nothing launched): n_slabs = 1 on both lattices, the pre-inlet periodic on the axis,
+ * the same number of cell types with the same model and vertex count, a repulsion on both containers or on neither,
+ * 0 <= window_lo < window_hi <= Lp, id_stride > 0.  Not checked: the window must be wider than the largest cell plus the
+ * distance travelled between two checks, or cells pass uninjected; the handle holds plain pointers to both containers and
+ * is destroyed BEFORE either.
+ * set_sink: with on != 0, every apply first removes (hcp_remove_cells) the domain's cells with cmax > plane (orientation -1)
+ * or cmin < plane (+1) on the axis.
+ * apply, on the library's stream: settles both containers, runs one select kernel per type and container, waits for that
+ * kernel alone (an event -- the one host wait of a check), runs the sink, then offers the candidates in ascending (type,
+ * slot) order: one whose new id this handle offered before is skipped; one whose shifted extents leave [0, n - 1] of the
+ * domain on any axis is skipped and counted rejected; one whose new id the domain holds is skipped; the rest are appended
+ * (slots n_cells, n_cells + 1, ...; within capacity without a copy through the host, as hcp_unpack_cells) and copied by one
+ * kernel, slot to slot.
+ * counts: out = {cells injected, rejected, removed by the sink, checks} since create.
+ * hc_preinlet_iterate: n times (hc_iterate(pre, 1), hc_iterate(domain, 1), hcl_preinlet_apply(F), and hcp_preinlet_apply(X)
+ * when the advanced iter is a multiple of cells_every >= 1), the reference driver's order; both systems share iter. */
+typedef struct hc_preinlet_cells hc_preinlet_cells;
+int hcp_preinlet_create(hc_preinlet_cells **out, hc_cells *pre, hc_cells *domain, int axis, int orientation /* -1: *neg, +1: *pos */,
+                        double window_lo, double window_hi, const double shift[3], long id_stride);
+int hcp_preinlet_set_sink(hc_preinlet_cells *X, int on, double plane);
+int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed);
+int hcp_preinlet_counts(const hc_preinlet_cells *X, long out[4]);   /* injected, rejected, removed by the sink, checks */
+int hcp_preinlet_destroy(hc_preinlet_cells *X);
+int hc_preinlet_iterate(hc_preinlet *F, hc_preinlet_cells *X, long *iter, int n, int particle_timescale, int force_limit,
+                        int deletion_check_every, int cells_every);
+
 /* CellInformationFunctionals (helper/cellInfo.cpp:39-80,140-180): per cell volume, area, bbox[6], centroid[3].  For a cell that
  * lost particles at a wall (not yet deleteIncompleteCells'd) bbox and centroid cover the particles left (CellPosition);
  * volume and area are the triangle sums at the stored positions. */
