@@ -17,11 +17,8 @@ using namespace hc;
 
 struct hc_celltype {
   CellTables host;
-  int *d_tri = nullptr, *d_edge = nullptr, *d_ebt = nullptr, *d_ebo = nullptr, *d_iedge = nullptr;
-  int *d_vtri = nullptr, *d_vtri_k = nullptr, *d_vedge = nullptr, *d_vedge_s = nullptr, *d_bsrc = nullptr;
-  int *d_vouter = nullptr, *d_vinner = nullptr, *d_vinner_s = nullptr, *d_ring = nullptr, *d_nring = nullptr;
-  double *d_tri_area_eq = nullptr, *d_edge_len_eq = nullptr, *d_edge_angle_eq = nullptr, *d_patch_eq = nullptr,
-         *d_iedge_len_eq = nullptr;
+  DevBuf<int> d_tri, d_edge, d_ebt, d_ebo, d_iedge, d_vtri, d_vtri_k, d_vedge, d_vedge_s, d_bsrc, d_vouter, d_vinner, d_vinner_s, d_ring, d_nring;
+  DevBuf<double> d_tri_area_eq, d_edge_len_eq, d_edge_angle_eq, d_patch_eq, d_iedge_len_eq;
 };
 
 struct hc_cells {
@@ -42,45 +39,42 @@ struct hc_cells {
   long capc[8] = {0};            // per-type capacity in cells (device regions are fixed-size per type)
   long first[8] = {0};           // first vertex of each type's region on the device
   long cell0[8] = {0};           // first cell slot of each type's region
-  double *pos[3] = {nullptr, nullptr, nullptr}, *vel[3] = {nullptr, nullptr, nullptr}, *frc[3] = {nullptr, nullptr, nullptr};
+  DevBuf<double> pos[3], vel[3], frc[3];   // [cap]
   // Deletion lives on the device (core/hemoCellParticleField.cpp:566-588, :304-321 without a host round trip):
   // d_tag per cell slot: 0 complete, 1 gone (every kernel skips the cell; the slot is reclaimed at the next
   // compaction), 2 incomplete (the reference's state after removeParticles(1) took single particles out: no
   // mechanics, forces zeroed at the next material step, the remaining particles are still spread / interpolated /
   // advanced); d_vdead per vertex: 1 = removed particle.
-  int *d_tag = nullptr;          // [tag_cap] all types, slot order
+  DevBuf<int> d_tag;             // [tag_cap] all types, slot order
   long tag_cap = 0;
-  unsigned char *d_vdead = nullptr;   // [cap]
-  int *h_ntag_dev = nullptr;     // device view of h_ntag
-  int *h_ntag = nullptr;         // pinned host copy of the counters {cells gone and not yet compacted, cells made incomplete}
-  int *d_ntag = nullptr;         // device counters [2]
-  hipEvent_t ntag_ev = nullptr;  // completion of an asynchronous counter read (hc_iterate polls it, never waits)
+  DevBuf<unsigned char> d_vdead; // [cap]
+  MappedBuf<int> h_ntag;         // pinned host copy of the counters {cells gone and not yet compacted, cells made incomplete}; .dev: its device view
+  DevBuf<int> d_ntag;            // device counters [2]
+  Event ntag_ev;                 // completion of an asynchronous counter read (hc_iterate polls it, never waits)
   bool ntag_pending = false, maybe_tagged = false;
   int del_mode = HC_DELETE_PARTICLE;
-  int *d_vert_cell = nullptr;    // [cap] cell slot of every vertex
+  DevBuf<int> d_vert_cell;       // [cap] cell slot of every vertex
   // vertex-vertex repulsion (core/hemoCellParticleField.cpp:677-743); arrays exist only once it is enabled
-  double *rep[3] = {nullptr, nullptr, nullptr};
+  DevBuf<double> rep[3];
   int rep_enabled = 0, rep_timescale = 1; double rep_const = 0, rep_cutoff = 0;
   // boundary particles (core/hemoCellParticleField.cpp:865-918): flag map of the wall nodes that repel vertices
-  int brep_enabled = 0, brep_timescale = 1; double brep_const = 0, brep_cutoff = 0; uint8_t *d_bflag = nullptr;
+  int brep_enabled = 0, brep_timescale = 1; double brep_const = 0, brep_cutoff = 0; DevBuf<uint8_t> d_bflag;
   bool rep_on() const { return rep_enabled || brep_enabled; }
-  unsigned int *d_keys[2] = {nullptr, nullptr}; int *d_vals[2] = {nullptr, nullptr}; void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0; long sort_cap = 0;
+  DevBuf<unsigned int> d_keys[2]; DevBuf<int> d_vals[2]; DevBuf<char> d_sort_tmp; long sort_cap = 0;
   // staged slot lists (envelope exchange, interpolate_cells, remove): pinned host block -> device block, stream ordered;
   // the event guards the pinned block against being rewritten while its copy is still in flight
   // staged slot lists: 0, 1 envelope exchange; 2 reproducible spread; 3 + 2 * type + half: the two halves of a slab's velocity update
-  int *d_iscratch[19] = {nullptr}, *h_iscratch[19] = {nullptr}; hipEvent_t iscratch_ev[19] = {nullptr};
-  // asynchronous cell extents (hcp_cell_extents_begin / _end): device block, pinned host block and event per type
-  double *d_ext[8] = {nullptr}, *h_ext[8] = {nullptr}; long ext_cap[8] = {0}, ext_n[8] = {0}; hipEvent_t ext_done[8] = {nullptr}; bool ext_pending[8] = {false};
+  Staged<int> iscratch[19];
+  // asynchronous cell extents (hcp_cell_extents_begin / _end): mapped pinned block [4 * cells] the kernel writes, and event, per type
+  MappedBuf<double> h_ext[8]; long ext_n[8] = {0}; Event ext_done[8]; bool ext_pending[8] = {false};
   // staging of hcp_add_vertex_force (called every iteration by the stretch drivers): pinned host block + device block
   // [n indices | 3n force components], grown on demand; the event guards the pinned block against reuse in flight
-  char *h_vf = nullptr, *d_vf = nullptr; size_t vf_cap = 0; hipEvent_t vf_done = nullptr;
-  size_t iscratch_cap[19] = {0};
+  Staged<char> vf;
   // reproducible spread (hc_set_reproducible_spread): (node, entry) pairs of every (particle, stencil node), both sort buffers,
   // and the three force components of every entry
-  unsigned int *det_keys[2] = {nullptr, nullptr}; int *det_vals[2] = {nullptr, nullptr}; double *det_val[3] = {nullptr, nullptr, nullptr};
-  void *det_tmp = nullptr; size_t det_tmp_bytes = 0; long det_cap = 0;
-  double *d_stat = nullptr, *h_stat = nullptr;   // [STAT_BLOCKS][4] partials of the statistics reductions, device and pinned host
-  double *d_info = nullptr, *h_info = nullptr; size_t info_cap = 0;   // scratch of the information calls (hcp_cell_info, hcp_mechanics_components, statistics)
+  DevBuf<unsigned int> det_keys[2]; DevBuf<int> det_vals[2]; DevBuf<double> det_val[3]; DevBuf<char> det_tmp; long det_cap = 0;
+  Staged<double> stat;   // [STAT_BLOCKS][4] partials of the statistics reductions, device and pinned host
+  Staged<double> info;   // scratch of the information calls (hcp_cell_info, hcp_mechanics_components, statistics)
   // slab runs: ids of cells this rank compacted away on its own (a host query between two envelope synchronisations:
   // counts, output, deleteIncompleteCells) -- the next synchronisation tells the other holders, or their copy would come
   // back as a fresh complete cell
@@ -90,7 +84,7 @@ struct hc_cells {
   // arrived too late -- a particle already sat on the receiving slab's side when its cell first got there (mapped pinned
   // memory, written by unpack_cells_kernel)
   double e_share = 4.0;
-  int *h_env_viol = nullptr, *d_env_viol = nullptr;
+  MappedBuf<int> h_env_viol;
   std::vector<long> slab_rejected;   // (type, cell id) pairs hcp_add_cell rejected at a wall on this slab, until hcp_slab_sync_placement
   long n_deleted = 0;              // cells removed entirely
   long n_particles_deleted = 0;    // single particles removed (reference mode), including those of cells removed later
@@ -184,14 +178,16 @@ __device__ __forceinline__ void phi2_stencil(const LatView &v, double px, double
 }
 
 struct VertArrays { double *p[3], *v[3], *f[3], *r[3]; unsigned char *dead; int *tag; };   // r: repulsion force arrays or null; dead / tag offset to the type
+// what a launch site takes for one type (vert_arrays): the kernel argument above, and the two pointers of the per-vertex
+// kernels -- vert_cell (offset to the type) holds GLOBAL cell slots, so those kernels index the whole tag array, tag_all,
+// while a per-cell kernel indexes tag, which is offset to the type
+struct TypeArrays : VertArrays { const int *vert_cell; int *tag_all; };
 
 // ----------------------------------------------------------------------------
 template <typename T>
-inline int upload_vec(T **dst, const std::vector<T> &src) {
-  *dst = nullptr;
-  const size_t n = src.size() ? src.size() : 1;
-  HC_HIP(hipMalloc((void **)dst, n * sizeof(T)));
-  if (src.size()) HC_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+inline int upload_vec(DevBuf<T> &dst, const std::vector<T> &src) {
+  const int rc = dst.reserve(src.size() ? src.size() : 1); if (rc != HC_OK) return rc;
+  if (src.size()) HC_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
   return HC_OK;
 }
 template <size_t N>
@@ -202,15 +198,18 @@ inline std::vector<int> flatten(const std::vector<std::array<long, N>> &v) {
 }
 
 // storage management (cells.hip)
-int free_device_arrays(hc_cells *C);
 int sync_to_device(hc_cells *C);   // host staging -> device arrays when the host copy is newer
 int sync_to_host(hc_cells *C);     // device arrays -> host staging before host-side edits
 // make the host's view of the cell set current: reads the deletion counters (one small blocking copy, and only when an
 // advance ran since the last time) and compacts gone cells away.  Every entry point that reports or edits cells calls it.
 int settle(hc_cells *C);
-VertArrays vert_arrays(hc_cells *C, int t);
+TypeArrays vert_arrays(hc_cells *C, int t);
+int ensure_rep(hc_cells *C);       // the three force_repulsion arrays, zeroed, once a repulsion is enabled and the vertex arrays exist
 // stage a small host int array on the device in a persistent scratch slot (through a pinned block; stream ordered)
 int stage_ints(hc_cells *C, int which, int **d, const int *h, int n);
+// the transposing copies between a staging [n][3] and three device arrays, from element `first` on (blocking)
+int upload_xyz(DevBuf<double> dst[3], long first, const double *src, long n);
+int download_xyz(double *dst, const DevBuf<double> src[3], long first, long n);
 void host_append_state(hc_cells *C, int type, long cell_id);
 int append_cells(hc_cells *C, int type, const long *cell_ids, const int *is_new, int n, long n_new);   // exchange.hip: n_new cells join the end of a type's region (is_new null: all n)
 int interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n, int which);   // ibm.hip: hcp_interpolate_cells through staging slot `which`

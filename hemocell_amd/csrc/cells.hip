@@ -7,6 +7,7 @@
 //   core/hemoCell.cpp:299-376                                                 iterate
 #include "cells.h"
 #include <cstddef>
+#include <memory>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -69,23 +70,37 @@ __global__ void fill_vert_cell_kernel(long n, int nv, int cell0, long first, int
 
 namespace hcc {
 
-int free_device_arrays(hc_cells *C) {
-  for (int d = 0; d < 3; d++) {
-    if (C->pos[d]) hipFree(C->pos[d]);
-    if (C->vel[d]) hipFree(C->vel[d]);
-    if (C->frc[d]) hipFree(C->frc[d]);
-    C->pos[d] = C->vel[d] = C->frc[d] = nullptr;
-  }
-  if (C->d_tag) hipFree(C->d_tag);
-  if (C->d_vdead) hipFree(C->d_vdead);
-  C->d_tag = nullptr; C->d_vdead = nullptr; C->cap = 0; C->tag_cap = 0;
+// the regions are about to be laid out anew: every array sized by the vertex or cell capacity goes
+static void drop_regions(hc_cells *C) {
+  for (int d = 0; d < 3; d++) { C->pos[d].reset(); C->vel[d].reset(); C->frc[d].reset(); C->rep[d].reset(); }
+  C->d_tag.reset(); C->d_vdead.reset(); C->d_vert_cell.reset();
+  C->cap = 0; C->tag_cap = 0;
   for (int t = 0; t < 8; t++) C->capc[t] = 0;
-  if (C->d_vert_cell) hipFree(C->d_vert_cell);
-  C->d_vert_cell = nullptr;
-  for (int d = 0; d < 3; d++) { if (C->rep[d]) hipFree(C->rep[d]); C->rep[d] = nullptr; }
-  for (int k = 0; k < 2; k++) { if (C->d_keys[k]) hipFree(C->d_keys[k]); if (C->d_vals[k]) hipFree(C->d_vals[k]); C->d_keys[k] = nullptr; C->d_vals[k] = nullptr; }
-  if (C->d_sort_tmp) hipFree(C->d_sort_tmp);
-  C->d_sort_tmp = nullptr; C->sort_tmp_bytes = 0; C->sort_cap = 0;
+}
+
+int ensure_rep(hc_cells *C) {
+  if (C->rep[0] || C->cap <= 0) return HC_OK;
+  for (int d = 0; d < 3; d++) {
+    const int rc = C->rep[d].reserve((size_t)C->cap); if (rc != HC_OK) return rc;
+    HC_HIP(hipMemset(C->rep[d], 0, C->cap * sizeof(double)));
+  }
+  return HC_OK;
+}
+
+int upload_xyz(DevBuf<double> dst[3], long first, const double *src, long n) {
+  std::vector<double> tmp((size_t)n);
+  for (int d = 0; d < 3; d++) {
+    for (long i = 0; i < n; i++) tmp[(size_t)i] = src[(size_t)(3 * i + d)];
+    HC_HIP(hipMemcpy(dst[d] + first, tmp.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return HC_OK;
+}
+int download_xyz(double *dst, const DevBuf<double> src[3], long first, long n) {
+  std::vector<double> tmp((size_t)n);
+  for (int d = 0; d < 3; d++) {
+    HC_HIP(hipMemcpy(tmp.data(), src[d] + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    for (long i = 0; i < n; i++) dst[(size_t)(3 * i + d)] = tmp[(size_t)i];
+  }
   return HC_OK;
 }
 
@@ -94,13 +109,14 @@ int sync_to_device(hc_cells *C) {
   if (!C->host_dirty) return HC_OK;
   bool grow = false;
   long nverts = 0;
+  int rc;
   for (int t = 0; t < C->ntypes; t++) {
     C->ncells[t] = (long)C->hids[t].size();
     nverts += C->ncells[t] * C->types[t]->host.nv;
     if (C->ncells[t] > C->capc[t]) grow = true;
   }
   if (grow || C->cap == 0) {
-    free_device_arrays(C);
+    drop_regions(C);
     long cap = 0, capcells = 0;
     for (int t = 0; t < C->ntypes; t++) {
       C->capc[t] = C->ncells[t] + C->ncells[t] / 4 + 64;
@@ -108,16 +124,12 @@ int sync_to_device(hc_cells *C) {
       cap += C->capc[t] * C->types[t]->host.nv; capcells += C->capc[t];
     }
     C->cap = cap > 0 ? cap : 1;
-    for (int d = 0; d < 3; d++) {
-      HC_HIP(hipMalloc((void **)&C->pos[d], C->cap * sizeof(double)));
-      HC_HIP(hipMalloc((void **)&C->vel[d], C->cap * sizeof(double)));
-      HC_HIP(hipMalloc((void **)&C->frc[d], C->cap * sizeof(double)));
-    }
-    HC_HIP(hipMalloc((void **)&C->d_vert_cell, C->cap * sizeof(int)));
-    if (C->rep_on()) for (int d = 0; d < 3; d++) { HC_HIP(hipMalloc((void **)&C->rep[d], C->cap * sizeof(double))); HC_HIP(hipMemset(C->rep[d], 0, C->cap * sizeof(double))); }
+    for (int d = 0; d < 3; d++)
+      if ((rc = C->pos[d].reserve((size_t)C->cap)) != HC_OK || (rc = C->vel[d].reserve((size_t)C->cap)) != HC_OK || (rc = C->frc[d].reserve((size_t)C->cap)) != HC_OK) return rc;
+    if ((rc = C->d_vert_cell.reserve((size_t)C->cap)) != HC_OK) return rc;
+    if (C->rep_on() && (rc = ensure_rep(C)) != HC_OK) return rc;
     C->tag_cap = capcells + 1;
-    HC_HIP(hipMalloc((void **)&C->d_tag, C->tag_cap * sizeof(int)));
-    HC_HIP(hipMalloc((void **)&C->d_vdead, (size_t)C->cap));
+    if ((rc = C->d_tag.reserve((size_t)C->tag_cap)) != HC_OK || (rc = C->d_vdead.reserve((size_t)C->cap)) != HC_OK) return rc;
     for (int t = 0; t < C->ntypes; t++) {
       const long n = C->capc[t] * C->types[t]->host.nv;
       hipLaunchKernelGGL(fill_vert_cell_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), n, C->types[t]->host.nv, (int)C->cell0[t], C->first[t], C->d_vert_cell);
@@ -125,18 +137,11 @@ int sync_to_device(hc_cells *C) {
     }
   }
   C->nverts = nverts;
-  std::vector<double> tmp;
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
-    std::vector<double> *src[3] = {&C->hpos[t], &C->hvel[t], &C->hfrc[t]};
-    double **dst[3] = {C->pos, C->vel, C->frc};
-    tmp.resize((size_t)n);
-    for (int w = 0; w < 3; w++)
-      for (int d = 0; d < 3; d++) {
-        for (long i = 0; i < n; i++) tmp[(size_t)i] = (*src[w])[(size_t)(3 * i + d)];
-        HC_HIP(hipMemcpy(dst[w][d] + C->first[t], tmp.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-      }
+    if ((rc = upload_xyz(C->pos, C->first[t], C->hpos[t].data(), n)) != HC_OK || (rc = upload_xyz(C->vel, C->first[t], C->hvel[t].data(), n)) != HC_OK ||
+        (rc = upload_xyz(C->frc, C->first[t], C->hfrc[t].data(), n)) != HC_OK) return rc;
   }
   HC_HIP(hipMemsetAsync(C->d_tag, 0, C->tag_cap * sizeof(int), hc::stream()));
   HC_HIP(hipMemsetAsync(C->d_vdead, 0, (size_t)C->cap, hc::stream()));
@@ -147,13 +152,7 @@ int sync_to_device(hc_cells *C) {
     // deletion state and force_repulsion travel with the cells (a staging written before they existed has none: all live, zero)
     if ((long)C->htag[t].size() == nc) HC_HIP(hipMemcpy(C->d_tag + C->cell0[t], C->htag[t].data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice));
     if ((long)C->hdead[t].size() == n) HC_HIP(hipMemcpy(C->d_vdead + C->first[t], C->hdead[t].data(), (size_t)n, hipMemcpyHostToDevice));
-    if (C->rep[0] && (long)C->hrep[t].size() == 3 * n) {
-      tmp.resize((size_t)n);
-      for (int d = 0; d < 3; d++) {
-        for (long i = 0; i < n; i++) tmp[(size_t)i] = C->hrep[t][(size_t)(3 * i + d)];
-        HC_HIP(hipMemcpy(C->rep[d] + C->first[t], tmp.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-      }
-    }
+    if (C->rep[0] && (long)C->hrep[t].size() == 3 * n && (rc = upload_xyz(C->rep, C->first[t], C->hrep[t].data(), n)) != HC_OK) return rc;
   }
   C->host_dirty = false;
   return HC_OK;
@@ -163,66 +162,58 @@ int sync_to_device(hc_cells *C) {
 int sync_to_host(hc_cells *C) {
   if (C->host_dirty) return HC_OK;  // host already authoritative
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  std::vector<double> tmp;
+  int rc;
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
-    std::vector<double> *dstv[3] = {&C->hpos[t], &C->hvel[t], &C->hfrc[t]};
-    double **src[3] = {C->pos, C->vel, C->frc};
-    tmp.resize((size_t)n);
-    for (int w = 0; w < 3; w++) {
-      dstv[w]->resize((size_t)(3 * n));
-      for (int d = 0; d < 3; d++) {
-        if (n) HC_HIP(hipMemcpy(tmp.data(), src[w][d] + C->first[t], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        for (long i = 0; i < n; i++) (*dstv[w])[(size_t)(3 * i + d)] = tmp[(size_t)i];
-      }
-    }
+    C->hpos[t].resize((size_t)(3 * n)); C->hvel[t].resize((size_t)(3 * n)); C->hfrc[t].resize((size_t)(3 * n));
     C->htag[t].assign((size_t)C->ncells[t], 0); C->hdead[t].assign((size_t)n, 0);
-    if (C->ncells[t] && C->d_tag) {
+    C->hrep[t].clear();
+    if (n == 0) continue;
+    if ((rc = download_xyz(C->hpos[t].data(), C->pos, C->first[t], n)) != HC_OK || (rc = download_xyz(C->hvel[t].data(), C->vel, C->first[t], n)) != HC_OK ||
+        (rc = download_xyz(C->hfrc[t].data(), C->frc, C->first[t], n)) != HC_OK) return rc;
+    if (C->d_tag) {
       HC_HIP(hipMemcpy(C->htag[t].data(), C->d_tag + C->cell0[t], (size_t)C->ncells[t] * sizeof(int), hipMemcpyDeviceToHost));
       HC_HIP(hipMemcpy(C->hdead[t].data(), C->d_vdead + C->first[t], (size_t)n, hipMemcpyDeviceToHost));
     }
-    C->hrep[t].clear();
-    if (C->rep[0] && n) {
+    if (C->rep[0]) {
       C->hrep[t].resize((size_t)(3 * n));
-      for (int d = 0; d < 3; d++) {
-        HC_HIP(hipMemcpy(tmp.data(), C->rep[d] + C->first[t], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        for (long i = 0; i < n; i++) C->hrep[t][(size_t)(3 * i + d)] = tmp[(size_t)i];
-      }
+      if ((rc = download_xyz(C->hrep[t].data(), C->rep, C->first[t], n)) != HC_OK) return rc;
     }
   }
   return HC_OK;
 }
 
-VertArrays vert_arrays(hc_cells *C, int t) {
-  VertArrays a;
+// Every launch site takes its per-type pointers from here.  r is set when the repulsion arrays exist, which is when a
+// repulsion is enabled: enabling one allocates them (hcp_set_repulsion and hcp_set_boundary_repulsion, through ensure_rep,
+// after a sync_to_device, which leaves cap > 0), a regrowth of the regions re-creates them under rep_on(), and nothing ever
+// disables a repulsion or frees them otherwise.  So after a sync_to_device, r[0] != nullptr is rep_on().
+TypeArrays vert_arrays(hc_cells *C, int t) {
+  TypeArrays a;
   for (int d = 0; d < 3; d++) {
     a.p[d] = C->pos[d] + C->first[t]; a.v[d] = C->vel[d] + C->first[t]; a.f[d] = C->frc[d] + C->first[t];
     a.r[d] = C->rep[d] ? C->rep[d] + C->first[t] : nullptr;
   }
   a.dead = C->d_vdead + C->first[t]; a.tag = C->d_tag + C->cell0[t];
+  a.vert_cell = C->d_vert_cell + C->first[t]; a.tag_all = C->d_tag;
   return a;
 }
 // stage a small host int array on the device in a persistent scratch slot.  The source is copied into a pinned block
 // first, so the caller's array may be a temporary and the copy really is asynchronous; the copy and every later use are
 // ordered on the stream in use.  The slot's event tells when the pinned block may be rewritten.
 int stage_ints(hc_cells *C, int which, int **d, const int *h, int n) {
-  if (!C->iscratch_ev[which]) HC_HIP(hipEventCreateWithFlags(&C->iscratch_ev[which], hipEventDisableTiming));
-  else HC_HIP(hipEventSynchronize(C->iscratch_ev[which]));   // the previous copy has left the pinned block (normally long ago)
-  if ((size_t)n > C->iscratch_cap[which]) {
+  Staged<int> &s = C->iscratch[which];
+  if (!s.ev) { const int rc = s.ev.create(); if (rc != HC_OK) return rc; }
+  else HC_HIP(hipEventSynchronize(s.ev));   // the previous copy has left the pinned block (normally long ago)
+  if ((size_t)n > s.cap()) {
     HC_HIP(hipDeviceSynchronize());   // the old device block may still be in use on either stream
-    if (C->d_iscratch[which]) HC_HIP(hipFree(C->d_iscratch[which]));
-    if (C->h_iscratch[which]) HC_HIP(hipHostFree(C->h_iscratch[which]));
-    C->d_iscratch[which] = C->h_iscratch[which] = nullptr;
-    C->iscratch_cap[which] = (size_t)n * 2 + 256;
-    HC_HIP(hipMalloc((void **)&C->d_iscratch[which], C->iscratch_cap[which] * sizeof(int)));
-    HC_HIP(hipHostMalloc((void **)&C->h_iscratch[which], C->iscratch_cap[which] * sizeof(int), hipHostMallocDefault));
+    const int rc = s.reserve((size_t)n * 2 + 256); if (rc != HC_OK) return rc;
   }
   if (n > 0) {
-    std::memcpy(C->h_iscratch[which], h, (size_t)n * sizeof(int));
-    HC_HIP(hipMemcpyAsync(C->d_iscratch[which], C->h_iscratch[which], (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
-    HC_HIP(hipEventRecord(C->iscratch_ev[which], hc::stream()));
+    std::memcpy(s.h, h, (size_t)n * sizeof(int));
+    HC_HIP(hipMemcpyAsync(s.d, s.h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
+    HC_HIP(hipEventRecord(s.ev, hc::stream()));
   }
-  *d = C->d_iscratch[which];
+  *d = s.d;
   return HC_OK;
 }
 
@@ -240,23 +231,23 @@ void host_append_state(hc_cells *C, int type, long cell_id) {
 // hcp_celltype_create / _create_wbc / _create_ex: mesh, tables and moduli on the host, then the tables to the device
 int celltype_create(const char *fn, hc_celltype **out, const hc_params *P, const hc_celltype_spec &S) {
   if (hc::stream() == nullptr) { hc::set_error(std::string(fn) + ": hc_init() has not been called"); return HC_ERR_STATE; }
-  hc_celltype *T = new hc_celltype();
+  std::unique_ptr<hc_celltype> T(new hc_celltype());   // an early return frees the tables uploaded by then
   std::string err = build_cell_tables(T->host, *P, S);
-  if (!err.empty()) { delete T; hc::set_error(std::string(fn) + ": " + err); return HC_ERR_ARG; }
+  if (!err.empty()) { hc::set_error(std::string(fn) + ": " + err); return HC_ERR_ARG; }
   const CellTables &H = T->host;
   int rc = HC_OK;
-  auto up_i = [&](int **d, const std::vector<int> &v) { if (rc == HC_OK) rc = upload_vec(d, v); };
-  auto up_d = [&](double **d, const std::vector<double> &v) { if (rc == HC_OK) rc = upload_vec(d, v); };
-  up_i(&T->d_tri, flatten(H.triangles)); up_i(&T->d_edge, flatten(H.edges));
-  up_i(&T->d_ebt, flatten(H.edge_bending_triangles)); up_i(&T->d_ebo, flatten(H.edge_bending_outer));
-  up_i(&T->d_iedge, flatten(H.inner_edges));
-  up_i(&T->d_vtri, H.vtri); up_i(&T->d_vtri_k, H.vtri_k); up_i(&T->d_vedge, H.vedge); up_i(&T->d_vedge_s, H.vedge_s);
-  up_i(&T->d_bsrc, H.bsrc); up_i(&T->d_vouter, H.vouter); up_i(&T->d_vinner, H.vinner); up_i(&T->d_vinner_s, H.vinner_s);
-  up_i(&T->d_ring, flatten(H.vertex_vertexes)); up_i(&T->d_nring, H.vertex_n_vertexes);
-  up_d(&T->d_tri_area_eq, H.triangle_area_eq); up_d(&T->d_edge_len_eq, H.edge_length_eq);
-  up_d(&T->d_edge_angle_eq, H.edge_angle_eq); up_d(&T->d_patch_eq, H.patch_dist_eq); up_d(&T->d_iedge_len_eq, H.inner_edge_length_eq);
+  auto up_i = [&](DevBuf<int> &d, const std::vector<int> &v) { if (rc == HC_OK) rc = upload_vec(d, v); };
+  auto up_d = [&](DevBuf<double> &d, const std::vector<double> &v) { if (rc == HC_OK) rc = upload_vec(d, v); };
+  up_i(T->d_tri, flatten(H.triangles)); up_i(T->d_edge, flatten(H.edges));
+  up_i(T->d_ebt, flatten(H.edge_bending_triangles)); up_i(T->d_ebo, flatten(H.edge_bending_outer));
+  up_i(T->d_iedge, flatten(H.inner_edges));
+  up_i(T->d_vtri, H.vtri); up_i(T->d_vtri_k, H.vtri_k); up_i(T->d_vedge, H.vedge); up_i(T->d_vedge_s, H.vedge_s);
+  up_i(T->d_bsrc, H.bsrc); up_i(T->d_vouter, H.vouter); up_i(T->d_vinner, H.vinner); up_i(T->d_vinner_s, H.vinner_s);
+  up_i(T->d_ring, flatten(H.vertex_vertexes)); up_i(T->d_nring, H.vertex_n_vertexes);
+  up_d(T->d_tri_area_eq, H.triangle_area_eq); up_d(T->d_edge_len_eq, H.edge_length_eq);
+  up_d(T->d_edge_angle_eq, H.edge_angle_eq); up_d(T->d_patch_eq, H.patch_dist_eq); up_d(T->d_iedge_len_eq, H.inner_edge_length_eq);
   if (rc != HC_OK) return rc;
-  *out = T;
+  *out = T.release();
   return HC_OK;
 }
 
@@ -301,12 +292,6 @@ int hcp_celltype_wbc_constants(const hc_celltype *T, double out[4]) {
 }
 
 int hcp_celltype_destroy(hc_celltype *T) {
-  if (!T) return HC_OK;
-  int *ip[] = {T->d_tri, T->d_edge, T->d_ebt, T->d_ebo, T->d_iedge, T->d_vtri, T->d_vtri_k, T->d_vedge, T->d_vedge_s, T->d_bsrc,
-               T->d_vouter, T->d_vinner, T->d_vinner_s, T->d_ring, T->d_nring};
-  double *dp[] = {T->d_tri_area_eq, T->d_edge_len_eq, T->d_edge_angle_eq, T->d_patch_eq, T->d_iedge_len_eq};
-  for (int *p : ip) if (p) hipFree(p);
-  for (double *p : dp) if (p) hipFree(p);
   delete T;
   return HC_OK;
 }
@@ -351,19 +336,17 @@ int hcp_celltype_tables2(const hc_celltype *T, long *edge_bending_triangles, lon
 
 int hcp_create(hc_cells **out, hc_lattice *L, const hc_params *P) {
   HC_REQUIRE(out && L && P, "hcp_create: null pointer");
-  hc_cells *C = new hc_cells();
+  std::unique_ptr<hc_cells> C(new hc_cells());
   C->L = L; C->P = *P;
   L->ibm = 1;
-  HC_HIP(hipHostMalloc((void **)&C->h_ntag, 4 * sizeof(int), hipHostMallocMapped));
-  HC_HIP(hipHostGetDevicePointer((void **)&C->h_ntag_dev, C->h_ntag, 0));
+  int rc;
+  if ((rc = C->h_ntag.reserve(4)) != HC_OK) return rc;
   for (int k = 0; k < 4; k++) C->h_ntag[k] = 0;
-  HC_HIP(hipMalloc((void **)&C->d_ntag, 4 * sizeof(int)));
+  if ((rc = C->d_ntag.reserve(4)) != HC_OK) return rc;
   HC_HIP(hipMemset(C->d_ntag, 0, 4 * sizeof(int)));
-  HC_HIP(hipEventCreateWithFlags(&C->ntag_ev, hipEventDisableTiming));
-  HC_HIP(hipHostMalloc((void **)&C->h_env_viol, sizeof(int), hipHostMallocMapped));
-  HC_HIP(hipHostGetDevicePointer((void **)&C->d_env_viol, C->h_env_viol, 0));
+  if ((rc = C->ntag_ev.create()) != HC_OK || (rc = C->h_env_viol.reserve(1)) != HC_OK) return rc;
   *C->h_env_viol = 0;
-  *out = C;
+  *out = C.release();
   return HC_OK;
 }
 
@@ -402,26 +385,7 @@ int hcp_envelope(const hc_cells *C, double *share_in_use, long *late_copies) {
 
 int hcp_destroy(hc_cells *C) {
   if (!C) return HC_OK;
-  hipStreamSynchronize(hc::stream());
-  free_device_arrays(C);
-  if (C->h_ntag) hipHostFree(C->h_ntag);
-  if (C->d_ntag) hipFree(C->d_ntag);
-  if (C->ntag_ev) hipEventDestroy(C->ntag_ev);
-  if (C->h_env_viol) hipHostFree(C->h_env_viol);
-  if (C->d_bflag) hipFree(C->d_bflag);
-  for (int k = 0; k < 19; k++) { if (C->h_iscratch[k]) hipHostFree(C->h_iscratch[k]); if (C->iscratch_ev[k]) hipEventDestroy(C->iscratch_ev[k]); }
-  for (int k = 0; k < 2; k++) { if (C->det_keys[k]) hipFree(C->det_keys[k]); if (C->det_vals[k]) hipFree(C->det_vals[k]); }
-  for (int k = 0; k < 3; k++) if (C->det_val[k]) hipFree(C->det_val[k]);
-  if (C->det_tmp) hipFree(C->det_tmp);
-  for (int t = 0; t < 8; t++) { if (C->h_ext[t]) hipHostFree(C->h_ext[t]); if (C->ext_done[t]) hipEventDestroy(C->ext_done[t]); }   // d_ext is the device view of h_ext
-  if (C->d_stat) hipFree(C->d_stat);
-  if (C->h_stat) hipHostFree(C->h_stat);
-  if (C->d_info) hipFree(C->d_info);
-  if (C->h_info) hipHostFree(C->h_info);
-  if (C->h_vf) hipHostFree(C->h_vf);
-  if (C->d_vf) hipFree(C->d_vf);
-  if (C->vf_done) hipEventDestroy(C->vf_done);
-  for (int k = 0; k < 19; k++) if (C->d_iscratch[k]) hipFree(C->d_iscratch[k]);
+  (void)hipStreamSynchronize(hc::stream());
   delete C;
   return HC_OK;
 }
@@ -698,21 +662,16 @@ int hcp_add_vertex_force(hc_cells *C, const long *vertex_index, int n, const dou
   }
   for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
   const size_t bytes = (size_t)n * (sizeof(long) + 3 * sizeof(double));
-  if (bytes > C->vf_cap) {
+  Staged<char> &vf = C->vf;
+  if (bytes > vf.cap()) {
     HC_HIP(hipStreamSynchronize(hc::stream()));
-    if (C->h_vf) HC_HIP(hipHostFree(C->h_vf));
-    if (C->d_vf) HC_HIP(hipFree(C->d_vf));
-    C->h_vf = C->d_vf = nullptr; C->vf_cap = 0;
-    HC_HIP(hipHostMalloc((void **)&C->h_vf, 2 * bytes, hipHostMallocDefault));
-    HC_HIP(hipMalloc((void **)&C->d_vf, 2 * bytes));
-    C->vf_cap = 2 * bytes;
-    if (!C->vf_done) HC_HIP(hipEventCreateWithFlags(&C->vf_done, hipEventDisableTiming));
+    if ((rc = vf.reserve(2 * bytes)) != HC_OK || (rc = vf.ev.create()) != HC_OK) return rc;
   } else {
-    HC_HIP(hipEventSynchronize(C->vf_done));   // the previous call's copy has left the pinned block
+    HC_HIP(hipEventSynchronize(vf.ev));   // the previous call's copy has left the pinned block
   }
   // staged round by round, list order within a round
-  long *h_idx = reinterpret_cast<long *>(C->h_vf);
-  double *h_f = reinterpret_cast<double *>(C->h_vf + (size_t)n * sizeof(long));
+  long *h_idx = reinterpret_cast<long *>(vf.h.p);
+  double *h_f = reinterpret_cast<double *>(vf.h + (size_t)n * sizeof(long));
   {
     std::vector<long> next(start.begin(), start.end() - 1);
     for (int i = 0; i < n; i++) {
@@ -721,10 +680,10 @@ int hcp_add_vertex_force(hc_cells *C, const long *vertex_index, int n, const dou
       for (int d = 0; d < 3; d++) h_f[3 * j + d] = f[3 * (size_t)i + d];
     }
   }
-  HC_HIP(hipMemcpyAsync(C->d_vf, C->h_vf, bytes, hipMemcpyHostToDevice, hc::stream()));
-  HC_HIP(hipEventRecord(C->vf_done, hc::stream()));
-  const long *d_idx = (const long *)C->d_vf;
-  const double *d_f = (const double *)(C->d_vf + (size_t)n * sizeof(long));
+  HC_HIP(hipMemcpyAsync(vf.d, vf.h, bytes, hipMemcpyHostToDevice, hc::stream()));
+  HC_HIP(hipEventRecord(vf.ev, hc::stream()));
+  const long *d_idx = (const long *)vf.d.p;
+  const double *d_f = (const double *)(vf.d + (size_t)n * sizeof(long));
   for (size_t k = 0; k + 1 < start.size(); k++) {
     const int m = (int)(start[k + 1] - start[k]);
     hipLaunchKernelGGL(add_vertex_force_kernel, dim3((m + 255) / 256), dim3(256), 0, hc::stream(), m, d_idx + start[k], d_f + 3 * start[k],
@@ -782,7 +741,7 @@ int settle(hc_cells *C) {
   if (C->host_dirty || !C->d_ntag) return HC_OK;      // the host staging is authoritative: nothing ran on the device since
   if (!C->maybe_tagged && !C->ntag_pending) return HC_OK;
   C->maybe_tagged = false; C->ntag_pending = false;
-  hipLaunchKernelGGL(publish_counters_kernel, dim3(1), dim3(1), 0, hc::stream(), (const int *)C->d_ntag, C->h_ntag_dev);
+  hipLaunchKernelGGL(publish_counters_kernel, dim3(1), dim3(1), 0, hc::stream(), (const int *)C->d_ntag, C->h_ntag.dev);
   HC_HIP(hipGetLastError());
   HC_HIP(hipStreamSynchronize(hc::stream()));
   return apply_counters(C);
@@ -798,7 +757,7 @@ static int poll_deletions(hc_cells *C, bool start_next) {
     int rc = apply_counters(C); if (rc != HC_OK) return rc;
   }
   if (start_next && C->maybe_tagged) {
-    hipLaunchKernelGGL(publish_counters_kernel, dim3(1), dim3(1), 0, hc::stream(), (const int *)C->d_ntag, C->h_ntag_dev);
+    hipLaunchKernelGGL(publish_counters_kernel, dim3(1), dim3(1), 0, hc::stream(), (const int *)C->d_ntag, C->h_ntag.dev);
     HC_HIP(hipGetLastError());
     HC_HIP(hipEventRecord(C->ntag_ev, hc::stream()));
     C->ntag_pending = true; C->maybe_tagged = false;
@@ -858,11 +817,11 @@ int hcp_advance(hc_cells *C, int check_deletions) {
     hc::ProfScope prof(hc::PK_ADVANCE);
     const LatView v = make_view(C->L);
     for (int t = 0; t < C->ntypes; t++) {
-      const long n = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+      const long n = C->ncells[t] * C->types[t]->host.nv;
       if (n == 0) continue;
-      hipLaunchKernelGGL(advance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, C->pos[0] + f, C->pos[1] + f,
-                         C->pos[2] + f, (const double *)(C->vel[0] + f), (const double *)(C->vel[1] + f), (const double *)(C->vel[2] + f),
-                         (const int *)(C->d_vert_cell + f), C->d_tag, C->d_vdead + f, C->d_ntag, C->del_mode == HC_DELETE_CELL ? 1 : 0);
+      const TypeArrays a = vert_arrays(C, t);
+      hipLaunchKernelGGL(advance_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
+                         a.vert_cell, a.tag_all, a.dead, C->d_ntag, C->del_mode == HC_DELETE_CELL ? 1 : 0);
       HC_HIP(hipGetLastError());
     }
     C->maybe_tagged = true;

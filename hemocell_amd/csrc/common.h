@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include <vector>
 #include <type_traits>
 #include "../../include/hemocell_amd.h"
@@ -34,6 +35,71 @@ bool forked();   // between fork() and join()
       return HC_ERR_ARG;                      \
     }                                         \
   } while (0)
+
+// Owning device buffer, pinned host buffer and event.  Move-only; each frees in its destructor and converts to the raw pointer
+// or handle, so launch sites and pointer arithmetic read as they do with raw pointers.  reserve(n) returns at once when the
+// capacity suffices; otherwise it frees and allocates exactly n elements.  It keeps no old contents, zeroes nothing and waits
+// for nothing: the caller chooses the slack, does the wait that must precede the free and any memset.  After a failure the
+// buffer is empty.
+template <class T> struct DevBuf {
+  T *p = nullptr; size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept { swap(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept { swap(o); return *this; }   // the old block goes with o
+  ~DevBuf() { reset(); }
+  void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+  void reset() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  operator T *() const { return p; }
+  int reserve(size_t n) {
+    if (n <= cap) return HC_OK;
+    reset();
+    const hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+    if (e != hipSuccess) { p = nullptr; return hip_fail(e, "hipMalloc", __FILE__, __LINE__); }
+    cap = n;
+    return HC_OK;
+  }
+};
+template <class T> struct PinBuf {
+  T *p = nullptr, *dev = nullptr; size_t cap = 0; unsigned flags;   // dev: the device view of a hipHostMallocMapped block
+  explicit PinBuf(unsigned f = hipHostMallocDefault) : flags(f) {}
+  PinBuf(PinBuf &&o) noexcept : flags(o.flags) { swap(o); }
+  PinBuf &operator=(PinBuf &&o) noexcept { swap(o); return *this; }
+  ~PinBuf() { reset(); }
+  void swap(PinBuf &o) { std::swap(p, o.p); std::swap(dev, o.dev); std::swap(cap, o.cap); std::swap(flags, o.flags); }
+  void reset() { if (p) (void)hipHostFree(p); p = dev = nullptr; cap = 0; }
+  operator T *() const { return p; }
+  int reserve(size_t n) {
+    if (n <= cap) return HC_OK;
+    reset();
+    hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), flags);
+    if (e != hipSuccess) p = nullptr;
+    else if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer((void **)&dev, p, 0);
+    if (e != hipSuccess) { reset(); return hip_fail(e, "hipHostMalloc", __FILE__, __LINE__); }
+    cap = n;
+    return HC_OK;
+  }
+};
+template <class T> struct MappedBuf : PinBuf<T> { MappedBuf() : PinBuf<T>(hipHostMallocMapped) {} };   // arrays of them need a default constructor
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept { std::swap(e, o.e); }
+  Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  operator hipEvent_t() const { return e; }
+  int create() {   // on first use; hipEventDisableTiming
+    if (e) return HC_OK;
+    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (r != hipSuccess) { e = nullptr; return hip_fail(r, "hipEventCreateWithFlags", __FILE__, __LINE__); }
+    return HC_OK;
+  }
+};
+// device block, pinned host block of the same size and the event that guards the pinned block while a copy is in flight
+template <class T> struct Staged {
+  DevBuf<T> d; PinBuf<T> h; Event ev;
+  size_t cap() const { return d.cap < h.cap ? d.cap : h.cap; }
+  int reserve(size_t n) { const int rc = d.reserve(n); return rc != HC_OK ? rc : h.reserve(n); }
+};
 
 // per-kernel hipEvent timing (hc_profile_*)
 enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them
@@ -178,9 +244,9 @@ struct hc_lattice {
   size_t xs;             // elements from x-plane to x-plane: plane, or plane + 8 rows of padding (see hcl_create)
   size_t npad;           // (nx+2*HALO)*xs
   size_t qstride;        // doubles from population q to q+1 of the same node: npad + padding (see hcl_create)
-  double *f[2] = {nullptr, nullptr};   // [19][npad] post-collision populations (fBar), ping-pong
+  hc::DevBuf<double> f[2];   // [19][npad] post-collision populations (fBar), ping-pong
   int cur;               // f[cur] is read by the next collide
-  double *force[3] = {nullptr, nullptr, nullptr};   // [npad][3] IBM force accumulators (a node's three components side by side), rotated: fcur -> (fcur+1)%3 every step
+  hc::DevBuf<double> force[3];   // [npad][3] IBM force accumulators (a node's three components side by side), rotated: fcur -> (fcur+1)%3 every step
   int fcur;              // force[fcur] is the one spread adds to / collide reads; force[(fcur+2)%3] is the previous
                          // step's (what the interpolation after a collide reads, and what the NEXT collide zeroes);
                          // force[(fcur+1)%3] is already clean, so the spread of the next step may run beside this collide
@@ -189,43 +255,41 @@ struct hc_lattice {
   // force component) holding the epoch in which spread last touched the group.  The collide kernel reads /
   // zeroes a group only when its byte equals the buffer's current epoch, so untouched lines cost no traffic.
   // Epochs are never cleared (no races); an aliased stale epoch only causes a harmless extra read / zeroing.
-  uint8_t *fdirty[3] = {nullptr, nullptr, nullptr};
+  hc::DevBuf<uint8_t> fdirty[3];
   uint8_t fepoch[3];
   // one byte per 8 x 8 x 8 brick of the padded lattice: 1 = the brick holds a non-fluid node or touches a face that stencils
   // cannot cross (the IBM kernels skip the mask look-ups for cells whose tile meets no such brick)
-  uint8_t *wallbrick = nullptr; int nbx, nby, nbz;
-  uint8_t *mask = nullptr;   // [npad]
+  hc::DevBuf<uint8_t> wallbrick; int nbx, nby, nbz;
+  hc::DevBuf<uint8_t> mask;   // [npad]
   std::vector<uint8_t> hmask;  // host copy (cell placement tests against it)
   double body[3];
   hc::BodyRegions regions;   // boxes with their own body force (hcl_set_body_force_regions), global node coordinates
   double wall_u[4][3];   // velocities of the moving-wall mask classes 3..6
   // active-node map of the collide kernel: per padded plane and row, the z-span that holds every node
   // which is not an inert solid, flattened so that a launch only creates threads for those spans
-  int *row_z0 = nullptr, *row_cum = nullptr, *blk_row = nullptr;   // [NX*ny], [NX*(ny+1)], [NX*(nblk+1)]
+  hc::DevBuf<int> row_z0, row_cum, blk_row;   // [NX*ny], [NX*(ny+1)], [NX*(nblk+1)]
   int nblk, max_active;
-  double *scratch = nullptr;   // download staging
-  size_t scratch_doubles = 0;
+  hc::DevBuf<double> scratch;   // download staging
   // slab runs: node velocities u = j/rho + F/2 of the two neighbours' face planes, evaluated there by their owner after the
   // last collide (slab.hip); [side][3][plane].  The interpolation reads them for stencil nodes on the first halo plane
   // instead of gathering 19 populations there.  Valid from the exchange until the next hcl_step_end.
-  double *halo_u[2] = {nullptr, nullptr};
+  hc::DevBuf<double> halo_u[2];   // filled and reset by slab.hip
   bool halo_u_valid = false;
   // Lees-Edwards pass (hcl_set_lees_edwards): run after every hcl_step_end of hcl_collide_stream / hc_iterate.  le_D is the
   // current displacement; with le_d != 0, hc_iterate sets it to fmod(le_d * iter, nx) after each step
   bool le_on = false;
   double le_D = 0.0, le_d = 0.0, le_v_top = 0.0, le_v_bottom = 0.0;
-  double *le_buf = nullptr;   // [2][19][nx ny] post-pass values of the top and bottom layers
+  hc::DevBuf<double> le_buf;   // [2][19][nx ny] post-pass values of the top and bottom layers
   // Zou-He open boundaries (hcl_open_boundary_add_axis): ob_code[node] = -1 for every other node, else
   // axis << 29 | slot << 2 | kind (zou_he_node above); ob_val[slot] = {u_x, u_y, u_z, rho} in lattice axes.  The collide runs
   // its open-boundary instantiation while ob_n > 0.
-  int *ob_code = nullptr;           // [npad], device
+  hc::DevBuf<int> ob_code;          // [npad], device
   std::vector<int> ob_hcode;        // host copy
-  double *ob_val = nullptr;         // [ob_cap][4], device
+  hc::DevBuf<double> ob_val;        // [ob_cap][4], device
   int ob_n = 0, ob_cap = 0;
   long ob_epoch = 0;                // counts hcl_open_boundary_clear: a pre-inlet coupling (hc_preinlet) made before one is stale
-  int *ob_list = nullptr; int ob_list_cap = 0;   // staging of hcl_plane_velocity's node list
-  double *ob_out = nullptr; int ob_out_cap = 0;  // ... and of its output when the caller's buffer is on the host
-  ~hc_lattice();   // lattice.hip: frees the device memory above, whatever part of it exists (halo_u belongs to slab.hip)
+  hc::DevBuf<int> ob_list;      // staging of hcl_plane_velocity's node list
+  hc::DevBuf<double> ob_out;    // ... and of its output when the caller's buffer is on the host
 };
 
 namespace hc {

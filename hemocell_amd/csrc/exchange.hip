@@ -127,12 +127,7 @@ __global__ __launch_bounds__(256) void owned_count_kernel(long n, const double *
 }  // namespace
 
 // persistent device / pinned host block of the statistics reductions (no allocation per call)
-static int stat_scratch(hc_cells *C) {
-  if (C->d_stat) return HC_OK;
-  HC_HIP(hipMalloc((void **)&C->d_stat, (size_t)STAT_BLOCKS * 4 * sizeof(double)));
-  HC_HIP(hipHostMalloc((void **)&C->h_stat, (size_t)STAT_BLOCKS * 4 * sizeof(double), hipHostMallocDefault));
-  return HC_OK;
-}
+static int stat_scratch(hc_cells *C) { return C->stat.reserve((size_t)STAT_BLOCKS * 4); }
 
 namespace hcc {
 // n_new cells join the end of a type's region: ids [n] with is_new [n] marking the ones that do (null: all of them).  Within
@@ -171,21 +166,16 @@ int hcp_cell_extents_begin(hc_cells *C, int type) {
   const long nc = C->ncells[type];
   C->ext_n[type] = nc; C->ext_pending[type] = true;
   if (nc == 0) return HC_OK;
-  if (nc > C->ext_cap[type]) {
+  if ((size_t)(4 * nc) > C->h_ext[type].cap) {
     if (C->ext_done[type]) HC_HIP(hipEventSynchronize(C->ext_done[type]));
-    if (C->h_ext[type]) HC_HIP(hipHostFree(C->h_ext[type]));
-    C->d_ext[type] = C->h_ext[type] = nullptr; C->ext_cap[type] = 0;
-    const long cap = nc + nc / 4 + 64;
     // the kernel stores its few KB straight into pinned host memory: no copy operation sits in the stream between this
     // kernel and the next one (an asynchronous device-to-host copy there held the following spread back by ~0.1 ms)
-    HC_HIP(hipHostMalloc((void **)&C->h_ext[type], (size_t)(4 * cap) * sizeof(double), hipHostMallocMapped));
-    HC_HIP(hipHostGetDevicePointer((void **)&C->d_ext[type], C->h_ext[type], 0));
-    C->ext_cap[type] = cap;
+    rc = C->h_ext[type].reserve((size_t)(4 * (nc + nc / 4 + 64))); if (rc != HC_OK) return rc;
   }
-  if (!C->ext_done[type]) HC_HIP(hipEventCreateWithFlags(&C->ext_done[type], hipEventDisableTiming));
-  hipLaunchKernelGGL(cell_extent_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), C->types[type]->host.nv,
-                     (const double *)(C->pos[0] + C->first[type]), C->d_ext[type], C->L->x0, C->L->nx, (const int *)(C->d_tag + C->cell0[type]),
-                     (const unsigned char *)(C->d_vdead + C->first[type]));
+  rc = C->ext_done[type].create(); if (rc != HC_OK) return rc;
+  const TypeArrays a = vert_arrays(C, type);
+  hipLaunchKernelGGL(cell_extent_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), C->types[type]->host.nv, a.p[0], C->h_ext[type].dev, C->L->x0, C->L->nx,
+                     a.tag, a.dead);
   HC_HIP(hipGetLastError());
   HC_HIP(hipEventRecord(C->ext_done[type], hc::stream()));
   return HC_OK;
@@ -242,7 +232,7 @@ int hcp_unpack_cells(hc_cells *C, int type, const int *slots, const long *cell_i
   rc = stage_ints(C, 0, &d_slots, slots, n); if (rc != HC_OK) return rc;
   rc = stage_ints(C, 1, &d_new, is_new, n); if (rc != HC_OK) return rc;
   hipLaunchKernelGGL(unpack_cells_kernel, dim3((unsigned)n), dim3(256), 0, hc::stream(), C->types[type]->host.nv, C->rep_on() ? 12 : 9, (const int *)d_slots, (const int *)d_new,
-                     vert_arrays(C, type), dev_buf, C->L->x0, C->L->nx, C->d_env_viol);
+                     vert_arrays(C, type), dev_buf, C->L->x0, C->L->nx, C->h_env_viol.dev);
   HC_HIP(hipGetLastError());
   return HC_OK;
 }
@@ -287,18 +277,18 @@ int hcp_owned_vertices(hc_cells *C, long *n_owned) {
   HC_REQUIRE(C && n_owned, "hcp_owned_vertices: null pointer");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
   rc = stat_scratch(C); if (rc != HC_OK) return rc;
-  unsigned long long *d = reinterpret_cast<unsigned long long *>(C->d_stat);
+  unsigned long long *d = reinterpret_cast<unsigned long long *>(C->stat.d.p);
   HC_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), hc::stream()));
   for (int t = 0; t < C->ntypes; t++) {
-    const long n = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+    const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
-    hipLaunchKernelGGL(owned_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), n, (const double *)(C->pos[0] + f), C->L->x0, C->L->nx, d,
-                       (const int *)(C->d_vert_cell + f), (const int *)C->d_tag, (const unsigned char *)(C->d_vdead + f));
+    const TypeArrays a = vert_arrays(C, t);
+    hipLaunchKernelGGL(owned_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), n, a.p[0], C->L->x0, C->L->nx, d, a.vert_cell, a.tag_all, a.dead);
   }
   HC_HIP(hipGetLastError());
-  HC_HIP(hipMemcpyAsync(C->h_stat, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipMemcpyAsync(C->stat.h, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  *n_owned = (long)*reinterpret_cast<unsigned long long *>(C->h_stat);
+  *n_owned = (long)*reinterpret_cast<unsigned long long *>(C->stat.h.p);
   return HC_OK;
 }
 
@@ -308,23 +298,21 @@ int hcp_vertex_stats(hc_cells *C, int what, double out[3], long *n) {
   HC_REQUIRE(C && out && n && (what == 1 || what == 2), "hcp_vertex_stats: bad arguments (what: 1 velocity, 2 force)");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
   rc = stat_scratch(C); if (rc != HC_OK) return rc;
-  double *d_partial = C->d_stat;
+  double *d_partial = C->stat.d;
   HC_HIP(hipMemsetAsync(d_partial, 0, (size_t)STAT_BLOCKS * 4 * sizeof(double), hc::stream()));
   const hc_lattice *L = C->L;
   int launched = 0;
   for (int t = 0; t < C->ntypes; t++) {
-    const long nt = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+    const long nt = C->ncells[t] * C->types[t]->host.nv;
     if (nt == 0) continue;
-    double **src = what == 1 ? C->vel : C->frc;
-    hipLaunchKernelGGL(vertex_stats_kernel, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), nt, what, L->n_slabs == 1 ? 1 : 0, L->x0, L->nx,
-                       (const double *)(C->pos[0] + f), (const double *)(src[0] + f), (const double *)(src[1] + f), (const double *)(src[2] + f),
-                       C->rep[0] ? (const double *)(C->rep[0] + f) : nullptr, C->rep[1] ? (const double *)(C->rep[1] + f) : nullptr,
-                       C->rep[2] ? (const double *)(C->rep[2] + f) : nullptr, d_partial, launched, (const int *)(C->d_vert_cell + f), (const int *)C->d_tag,
-                       (const unsigned char *)(C->d_vdead + f));
+    const TypeArrays a = vert_arrays(C, t);   // r: set where the site's own test, rep[d] != nullptr, set it
+    double *const *src = what == 1 ? a.v : a.f;
+    hipLaunchKernelGGL(vertex_stats_kernel, dim3(STAT_BLOCKS), dim3(256), 0, hc::stream(), nt, what, L->n_slabs == 1 ? 1 : 0, L->x0, L->nx, a.p[0], src[0], src[1], src[2],
+                       a.r[0], a.r[1], a.r[2], d_partial, launched, a.vert_cell, a.tag_all, a.dead);
     launched = 1;
   }
   HC_HIP(hipGetLastError());
-  return hc::stat_finish(d_partial, out, n, C->h_stat);
+  return hc::stat_finish(d_partial, out, n, C->stat.h);
 }
 
 

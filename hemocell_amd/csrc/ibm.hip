@@ -648,17 +648,17 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
   const LatView v = make_view(C->L);
   HC_REQUIRE(v.npad * 3 < 0xffffffffL && C->nverts * 8 < 0x7fffffffL, "reproducible spread: lattice or vertex count beyond its 32-bit keys");
   const long n_e = C->nverts * 8;
+  int rc;
   if (n_e > C->det_cap) {
     HC_HIP(hipDeviceSynchronize());
-    for (int k = 0; k < 2; k++) { if (C->det_keys[k]) HC_HIP(hipFree(C->det_keys[k])); if (C->det_vals[k]) HC_HIP(hipFree(C->det_vals[k])); C->det_keys[k] = nullptr; C->det_vals[k] = nullptr; }
-    for (int k = 0; k < 3; k++) { if (C->det_val[k]) HC_HIP(hipFree(C->det_val[k])); C->det_val[k] = nullptr; }
-    if (C->det_tmp) HC_HIP(hipFree(C->det_tmp));
-    C->det_tmp = nullptr; C->det_tmp_bytes = 0;
-    C->det_cap = n_e + n_e / 4 + 4096;
-    for (int k = 0; k < 2; k++) { HC_HIP(hipMalloc((void **)&C->det_keys[k], C->det_cap * sizeof(unsigned int))); HC_HIP(hipMalloc((void **)&C->det_vals[k], C->det_cap * sizeof(int))); }
-    for (int k = 0; k < 3; k++) HC_HIP(hipMalloc((void **)&C->det_val[k], C->det_cap * sizeof(double)));
-    HC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, C->det_tmp_bytes, C->det_keys[0], C->det_keys[1], C->det_vals[0], C->det_vals[1], (int)C->det_cap, 0, 32, hc::stream()));
-    HC_HIP(hipMalloc(&C->det_tmp, C->det_tmp_bytes));
+    const long cap = n_e + n_e / 4 + 4096;
+    C->det_cap = 0;
+    for (int k = 0; k < 2; k++) if ((rc = C->det_keys[k].reserve((size_t)cap)) != HC_OK || (rc = C->det_vals[k].reserve((size_t)cap)) != HC_OK) return rc;
+    for (int k = 0; k < 3; k++) if ((rc = C->det_val[k].reserve((size_t)cap)) != HC_OK) return rc;
+    size_t tmp_bytes = 0;
+    HC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, C->det_keys[0].p, C->det_keys[1].p, C->det_vals[0].p, C->det_vals[1].p, (int)cap, 0, 32, hc::stream()));
+    if ((rc = C->det_tmp.reserve(tmp_bytes)) != HC_OK) return rc;
+    C->det_cap = cap;
   }
   // cell slots in ascending cell id, type by type: the canonical order of the entries
   std::vector<int> order((size_t)0);
@@ -672,17 +672,15 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
     std::stable_sort(order.begin() + (long)o, order.end(), [&](int a, int b) { return ids[(size_t)a] < ids[(size_t)b]; });
   }
   int *d_order = nullptr;
-  int rc = stage_ints(C, 2, &d_order, order.data(), (int)order.size()); if (rc != HC_OK) return rc;
+  rc = stage_ints(C, 2, &d_order, order.data(), (int)order.size()); if (rc != HC_OK) return rc;
   long ebase = 0;
   for (int t = 0; t < C->ntypes; t++) {
     const int nv = C->types[t]->host.nv;
-    const long n = C->ncells[t] * nv, f = C->first[t];
+    const long n = C->ncells[t] * nv;
     if (n == 0) continue;
-    const bool rep = C->rep_on();
+    const TypeArrays a = vert_arrays(C, t);   // r is set exactly when rep_on(), see vert_arrays: hcp_spread has synchronised to the device
     hipLaunchKernelGGL(spread_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, nv, n, (const int *)(d_order + obase[(size_t)t]), ebase,
-                       (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f), C->frc[0] + f, C->frc[1] + f, C->frc[2] + f,
-                       rep ? (const double *)(C->rep[0] + f) : nullptr, rep ? (const double *)(C->rep[1] + f) : nullptr, rep ? (const double *)(C->rep[2] + f) : nullptr,
-                       force_limit, C->P.f_limit, (const int *)(C->d_tag + C->cell0[t]), (const unsigned char *)(C->d_vdead + f), C->det_keys[0], C->det_vals[0],
+                       a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], force_limit, C->P.f_limit, a.tag, a.dead, C->det_keys[0], C->det_vals[0],
                        C->det_val[0], C->det_val[1], C->det_val[2]);
     HC_HIP(hipGetLastError());
     ebase += n;
@@ -690,8 +688,8 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
   // only the bits a node index needs: 2^bits > npad, so the low bits of an invalid key (all ones) still sort behind every node
   int bits = 1;
   while (bits < 32 && (1L << bits) <= v.npad) bits++;
-  size_t tmp = C->det_tmp_bytes;
-  HC_HIP(hipcub::DeviceRadixSort::SortPairs(C->det_tmp, tmp, C->det_keys[0], C->det_keys[1], C->det_vals[0], C->det_vals[1], (int)n_e, 0, bits, hc::stream()));
+  size_t tmp = C->det_tmp.cap;
+  HC_HIP(hipcub::DeviceRadixSort::SortPairs(C->det_tmp.p, tmp, C->det_keys[0].p, C->det_keys[1].p, C->det_vals[0].p, C->det_vals[1].p, (int)n_e, 0, bits, hc::stream()));
   hipLaunchKernelGGL(spread_gather_kernel, dim3((unsigned)((n_e + 255) / 256)), dim3(256), 0, hc::stream(), v, n_e, (const unsigned int *)C->det_keys[1],
                      (const int *)C->det_vals[1], (const double *)C->det_val[0], (const double *)C->det_val[1], (const double *)C->det_val[2], C->L->force[C->L->fcur]);
   HC_HIP(hipGetLastError());
@@ -718,21 +716,16 @@ int hcp_spread(hc_cells *C, int force_limit) {
   if (reproducible()) return spread_reproducible(C, force_limit);
   const LatView v = make_view(C->L);
   for (int t = 0; t < C->ntypes; t++) {
-    const long n = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+    const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
     const int nv = C->types[t]->host.nv;
-    const double *rp[3] = {C->rep_on() ? C->rep[0] + f : nullptr, C->rep_on() ? C->rep[1] + f : nullptr, C->rep_on() ? C->rep[2] + f : nullptr};
+    const TypeArrays a = vert_arrays(C, t);   // r is set exactly when rep_on(), see vert_arrays: the sync_to_device above has run
     if (g_ibm_per_vertex)
-      hipLaunchKernelGGL(ibm_spread_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n,
-                         (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                         C->frc[0] + f, C->frc[1] + f, C->frc[2] + f, rp[0], rp[1], rp[2], C->L->force[C->L->fcur], force_limit, C->P.f_limit,
-                         (const int *)(C->d_vert_cell + f), (const int *)C->d_tag, (const unsigned char *)(C->d_vdead + f));
-    else {
-      hipLaunchKernelGGL(ibm_spread_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), 0, hc::stream(), v, nv,
-                         (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                         C->frc[0] + f, C->frc[1] + f, C->frc[2] + f, rp[0], rp[1], rp[2], C->L->force[C->L->fcur], force_limit, C->P.f_limit, 1,
-                         (const int *)(C->d_tag + C->cell0[t]), (const unsigned char *)(C->d_vdead + f));
-    }
+      hipLaunchKernelGGL(ibm_spread_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2],
+                         a.r[0], a.r[1], a.r[2], C->L->force[C->L->fcur], force_limit, C->P.f_limit, a.vert_cell, a.tag_all, a.dead);
+    else
+      hipLaunchKernelGGL(ibm_spread_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), 0, hc::stream(), v, nv, a.p[0], a.p[1], a.p[2],
+                         a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], C->L->force[C->L->fcur], force_limit, C->P.f_limit, 1, a.tag, a.dead);
     HC_HIP(hipGetLastError());
   }
   return HC_OK;
@@ -747,20 +740,16 @@ int hcp_interpolate(hc_cells *C) {
   const LatView v = make_view(L);
   const PopView pv = make_pops(L);
   for (int t = 0; t < C->ntypes; t++) {
-    const long n = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+    const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
     const int nv = C->types[t]->host.nv;
+    const TypeArrays a = vert_arrays(C, t);
     if (g_ibm_per_vertex)
-      HC_LAUNCH_POPS(ibm_interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), v, pv, n,
-                         (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                         C->vel[0] + f, C->vel[1] + f, C->vel[2] + f, (const int *)(C->d_vert_cell + f), (const int *)C->d_tag,
-                         (const unsigned char *)(C->d_vdead + f));
-    else {
-      HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), v, pv, nv,
-                         (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                         C->vel[0] + f, C->vel[1] + f, C->vel[2] + f, (const int *)nullptr, 1, (const int *)(C->d_tag + C->cell0[t]),
-                         (const unsigned char *)(C->d_vdead + f));
-    }
+      HC_LAUNCH_POPS(ibm_interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), v, pv, n, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
+                     a.vert_cell, a.tag_all, a.dead);
+    else
+      HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), v, pv, nv, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
+                     (const int *)nullptr, 1, a.tag, a.dead);
     HC_HIP(hipGetLastError());
   }
   return HC_OK;
@@ -794,12 +783,11 @@ int hcl_face_velocity_pack_both(hc_lattice *L, double *dev_lo, double *dev_hi) {
 // inspection: the same plane of velocities on the host, [3][ny*nz] (tests; the message itself never touches the host)
 int hcl_download_face_velocity(hc_lattice *L, int side, double *host_u) {
   HC_REQUIRE(L && host_u && (side == 0 || side == 1), "hcl_download_face_velocity: bad arguments");
-  double *d = nullptr;
-  HC_HIP(hipMalloc((void **)&d, 3 * L->plane * sizeof(double)));
-  int rc = hcl_face_velocity_pack(L, side, d);
+  hc::DevBuf<double> d;
+  int rc = d.reserve(3 * L->plane); if (rc != HC_OK) return rc;
+  rc = hcl_face_velocity_pack(L, side, d);
   if (rc == HC_OK && hipMemcpyAsync(host_u, d, 3 * L->plane * sizeof(double), hipMemcpyDeviceToHost, hc::stream()) != hipSuccess) { hc::set_error("hcl_download_face_velocity: copy failed"); rc = HC_ERR_HIP; }
   if (rc == HC_OK && hipStreamSynchronize(hc::stream()) != hipSuccess) { hc::set_error("hcl_download_face_velocity: synchronise failed"); rc = HC_ERR_HIP; }
-  hipFree(d);
   return rc;
 }
 
@@ -821,12 +809,10 @@ int hcc::interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n
   const hc_lattice *L = C->L;
   const LatView v = make_view(L);
   const PopView pv = make_pops(L);
-  const long f = C->first[type];
+  const TypeArrays a = vert_arrays(C, type);
   const int nv = C->types[type]->host.nv;
-  HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)n), dim3(nv > 128 ? 256 : 128), v, pv, nv,
-                     (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                     C->vel[0] + f, C->vel[1] + f, C->vel[2] + f, (const int *)d_slots, 0, (const int *)(C->d_tag + C->cell0[type]),
-                     (const unsigned char *)(C->d_vdead + f));
+  HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)n), dim3(nv > 128 ? 256 : 128), v, pv, nv, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
+                 (const int *)d_slots, 0, a.tag, a.dead);
   HC_HIP(hipGetLastError());
   return HC_OK;
 }

@@ -522,14 +522,7 @@ OpenArgs open_of(const hc_lattice *L, const LatArgs &a) {
 
 dim3 plane_grid(const hc_lattice *L, int nplanes) { return dim3((unsigned)((L->plane + 255) / 256), (unsigned)nplanes, 1); }
 
-int ensure_scratch(hc_lattice *L, size_t doubles) {
-  if (L->scratch_doubles >= doubles) return HC_OK;
-  if (L->scratch) HC_HIP(hipFree(L->scratch));
-  L->scratch = nullptr; L->scratch_doubles = 0;
-  HC_HIP(hipMalloc((void **)&L->scratch, doubles * sizeof(double)));
-  L->scratch_doubles = doubles;
-  return HC_OK;
-}
+int ensure_scratch(hc_lattice *L, size_t doubles) { return L->scratch.reserve(doubles); }
 
 // (re)build the active-span map from the host mask classes
 int rebuild_active_map(hc_lattice *L) {
@@ -562,10 +555,9 @@ int rebuild_active_map(hc_lattice *L) {
       blk[(size_t)x * (nblk + 1) + b] = y;
     }
   }
-  for (int **p : {&L->row_z0, &L->row_cum, &L->blk_row}) if (*p) { HC_HIP(hipFree(*p)); *p = nullptr; }
-  HC_HIP(hipMalloc((void **)&L->row_z0, z0.size() * sizeof(int)));
-  HC_HIP(hipMalloc((void **)&L->row_cum, cum.size() * sizeof(int)));
-  HC_HIP(hipMalloc((void **)&L->blk_row, blk.size() * sizeof(int)));
+  for (hc::DevBuf<int> *b : {&L->row_z0, &L->row_cum, &L->blk_row}) b->reset();   // new blocks every time: the free waits for kernels that read the old map
+  int rc;
+  if ((rc = L->row_z0.reserve(z0.size())) != HC_OK || (rc = L->row_cum.reserve(cum.size())) != HC_OK || (rc = L->blk_row.reserve(blk.size())) != HC_OK) return rc;
   HC_HIP(hipMemcpy(L->row_z0, z0.data(), z0.size() * sizeof(int), hipMemcpyHostToDevice));
   HC_HIP(hipMemcpy(L->row_cum, cum.data(), cum.size() * sizeof(int), hipMemcpyHostToDevice));
   HC_HIP(hipMemcpy(L->blk_row, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -592,7 +584,7 @@ int rebuild_wall_bricks(hc_lattice *L) {
           }
         flag[((size_t)bx * L->nby + by) * L->nbz + bz] = near ? 1 : 0;
       }
-  if (!L->wallbrick) HC_HIP(hipMalloc((void **)&L->wallbrick, flag.size()));
+  { const int rc = L->wallbrick.reserve(flag.size()); if (rc != HC_OK) return rc; }
   HC_HIP(hipMemcpy(L->wallbrick, flag.data(), flag.size(), hipMemcpyHostToDevice));
   return HC_OK;
 }
@@ -640,14 +632,6 @@ static bool le_layers_fluid(const hc_lattice *L, const uint8_t *mask, size_t xs)
       for (int k = 0; k < 4; k++)
         if (mask[(size_t)x * xs + (size_t)y * L->nz + zs[k]] != 0) return false;
   return true;
-}
-
-// every device buffer the lattice may hold; each is null until it exists
-hc_lattice::~hc_lattice() {
-  for (void *p : {(void *)f[0], (void *)f[1], (void *)force[0], (void *)force[1], (void *)force[2], (void *)fdirty[0], (void *)fdirty[1], (void *)fdirty[2],
-                  (void *)mask, (void *)scratch, (void *)row_z0, (void *)row_cum, (void *)blk_row, (void *)wallbrick, (void *)le_buf, (void *)ob_code,
-                  (void *)ob_val, (void *)ob_list, (void *)ob_out})
-    if (p) hipFree(p);
 }
 
 // The body of the hcl_download_* entry points: per_node doubles for every bulk node are written to the scratch buffer by
@@ -711,25 +695,25 @@ int hcl_create(hc_lattice **out, int nx, int ny, int nz, const int periodic[3], 
   L->body[0] = L->body[1] = L->body[2] = 0.0;
   L->regions.n = 0;
   for (int c = 0; c < 4; c++) for (int d = 0; d < 3; d++) L->wall_u[c][d] = 0.0;
+  int rc;
   for (int k = 0; k < 2; k++) {
-    HC_HIP(hipMalloc((void **)&L->f[k], L->qstride * HC_Q * sizeof(double)));
+    if ((rc = L->f[k].reserve(L->qstride * HC_Q)) != HC_OK) return rc;
     HC_HIP(hipMemsetAsync(L->f[k], 0, L->qstride * HC_Q * sizeof(double), hc::stream()));
   }
   for (int k = 0; k < 3; k++) {
-    HC_HIP(hipMalloc((void **)&L->force[k], L->npad * 3 * sizeof(double)));
+    if ((rc = L->force[k].reserve(L->npad * 3)) != HC_OK) return rc;
     HC_HIP(hipMemsetAsync(L->force[k], 0, L->npad * 3 * sizeof(double), hc::stream()));
   }
-  HC_HIP(hipMalloc((void **)&L->mask, L->npad));
+  if ((rc = L->mask.reserve(L->npad)) != HC_OK) return rc;
   HC_HIP(hipMemsetAsync(L->mask, 0, L->npad, hc::stream()));
   for (int k = 0; k < 3; k++) {
-    HC_HIP(hipMalloc((void **)&L->fdirty[k], L->npad / 16 + 1));
+    if ((rc = L->fdirty[k].reserve(L->npad / 16 + 1)) != HC_OK) return rc;
     HC_HIP(hipMemsetAsync(L->fdirty[k], 0, L->npad / 16 + 1, hc::stream()));
     L->fepoch[k] = 1;
   }
   L->hmask.assign(L->npad, 0);   // device numbering; hcl_set_mask marks the padding
   L->nbx = (nx + 2 * HALO + 7) / 8; L->nby = (ny + 7) / 8; L->nbz = (nz + 7) / 8;
-  { int rc = rebuild_active_map(L); if (rc != HC_OK) return rc; }
-  { int rc = rebuild_wall_bricks(L); if (rc != HC_OK) return rc; }
+  if ((rc = rebuild_active_map(L)) != HC_OK || (rc = rebuild_wall_bricks(L)) != HC_OK) return rc;
   HC_HIP(hipStreamSynchronize(hc::stream()));
   *out = owner.release();
   return HC_OK;
@@ -909,7 +893,7 @@ int hcl_set_lees_edwards(hc_lattice *L, double v_top, double v_bottom) {
     hc::set_error("hcl_set_lees_edwards: the layers z = 0, 1, nz-2 and nz-1 must hold fluid nodes only");
     return HC_ERR_STATE;
   }
-  if (!L->le_buf) HC_HIP(hipMalloc((void **)&L->le_buf, (size_t)2 * HC_Q * L->nx * L->ny * sizeof(double)));
+  { const int rc = L->le_buf.reserve((size_t)2 * HC_Q * L->nx * L->ny); if (rc != HC_OK) return rc; }
   L->le_on = true; L->le_v_top = v_top; L->le_v_bottom = v_bottom; L->le_D = 0.0; L->le_d = 0.0;
   return HC_OK;
 }
@@ -939,28 +923,18 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]) {
 static int ob_grow(hc_lattice *L, int need) {
   if (need <= L->ob_n) return HC_OK;
   const int cap = need <= L->ob_cap ? L->ob_cap : std::max(need, 2 * L->ob_cap);
+  hc::DevBuf<double> grown;   // the larger block, while the old one still holds the slots to carry over
   double *v = L->ob_val;
   if (cap > L->ob_cap) {
-    HC_HIP(hipMalloc((void **)&v, (size_t)cap * 4 * sizeof(double)));
+    const int rc = grown.reserve((size_t)cap * 4); if (rc != HC_OK) return rc;
+    v = grown;
     if (L->ob_val && L->ob_n) HC_HIP(hipMemcpyAsync(v, L->ob_val, (size_t)L->ob_n * 4 * sizeof(double), hipMemcpyDeviceToDevice, hc::stream()));
   }
   std::vector<double> init((size_t)(need - L->ob_n) * 4, 0.0);
   for (size_t i = 0; i < init.size(); i += 4) init[i + 3] = 1.0;   // u = 0, rho = 1
   HC_HIP(hipMemcpyAsync(v + (size_t)L->ob_n * 4, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  if (v != L->ob_val) {
-    if (L->ob_val) HC_HIP(hipFree(L->ob_val));
-    L->ob_val = v; L->ob_cap = cap;
-  }
-  return HC_OK;
-}
-
-static int ob_stage(void **buf, int *cap, size_t elem, int n) {
-  if (n <= *cap) return HC_OK;
-  if (*buf) HC_HIP(hipFree(*buf));
-  *buf = nullptr; *cap = 0;
-  HC_HIP(hipMalloc(buf, (size_t)n * elem));
-  *cap = n;
+  if (grown) { L->ob_val = std::move(grown); L->ob_cap = cap; }   // the old block is freed on return, after the wait above
   return HC_OK;
 }
 
@@ -1012,7 +986,7 @@ static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int
   if (n == 0) return HC_OK;
   int rc = ob_grow(L, L->ob_n + n); if (rc != HC_OK) return rc;
   if (!L->ob_code) {
-    HC_HIP(hipMalloc((void **)&L->ob_code, L->npad * sizeof(int)));
+    rc = L->ob_code.reserve(L->npad); if (rc != HC_OK) return rc;
     L->ob_hcode.assign(L->npad, -1);
   }
   const int k = (kind == HC_OB_PRESSURE ? 2 : 0) + (orientation > 0 ? 1 : 0);
@@ -1132,10 +1106,10 @@ static int plane_velocity(const std::string &who, hc_lattice *L, int axis, int p
   HC_REQUIRE(L->n_slabs == 1, who + ": needs n_slabs = 1");
   for (int i = 0; i < n; i++) HC_REQUIRE(idx[i] >= 0 && (size_t)idx[i] < plane_nodes(L, axis), who + ": in-plane index out of range");
   if (n == 0) return HC_OK;
-  int rc = ob_stage((void **)&L->ob_list, &L->ob_list_cap, sizeof(int), n); if (rc != HC_OK) return rc;
+  int rc = L->ob_list.reserve((size_t)n); if (rc != HC_OK) return rc;
   HC_HIP(hipMemcpyAsync(L->ob_list, idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
   double *d = out;
-  if (!on_device) { rc = ob_stage((void **)&L->ob_out, &L->ob_out_cap, 3 * sizeof(double), n); if (rc != HC_OK) return rc; d = L->ob_out; }
+  if (!on_device) { rc = L->ob_out.reserve((size_t)3 * n); if (rc != HC_OK) return rc; d = L->ob_out; }
   if ((rc = launch_plane_velocity(L, axis, plane, L->ob_list, n, d, 3)) != HC_OK) return rc;
   if (!on_device) HC_HIP(hipMemcpyAsync(out, d, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));   // the staged node list is reused by the next call
@@ -1154,10 +1128,9 @@ int hcl_plane_velocity_axis(hc_lattice *L, int axis, int plane, const int *idx, 
 struct hc_preinlet {
   hc_lattice *pre, *domain;   // not owned: the handle is destroyed before either lattice
   int axis, plane;            // the pre-inlet's plane coordinate[axis] == plane ...
-  int *idx = nullptr;         // ... and the in-plane indices of its coupled nodes [n], device
+  hc::DevBuf<int> idx;        // ... and the in-plane indices of its coupled nodes [n], device
   int n, first;               // the domain's velocity slots first .. first + n - 1
   long epoch;                 // the domain's ob_epoch at creation: hcl_open_boundary_clear moves it on
-  ~hc_preinlet() { if (idx) hipFree(idx); }
 };
 
 static bool preinlet_slots_gone(const hc_preinlet *P) { return P->epoch != P->domain->ob_epoch || (long)P->first + P->n > (long)P->domain->ob_n; }
@@ -1197,7 +1170,7 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
   P->pre = pre; P->domain = domain; P->axis = axis; P->plane = pre_plane; P->n = n; P->first = domain_first_slot;
   P->epoch = domain->ob_epoch;
   if (n > 0) {
-    HC_HIP(hipMalloc((void **)&P->idx, (size_t)n * sizeof(int)));
+    const int rc = P->idx.reserve((size_t)n); if (rc != HC_OK) return rc;
     HC_HIP(hipMemcpyAsync(P->idx, pre_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
     HC_HIP(hipStreamSynchronize(hc::stream()));   // the caller's list may go away after the call
   }

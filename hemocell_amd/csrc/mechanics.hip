@@ -447,16 +447,9 @@ int hcp_mechanics(hc_cells *C, long iter, int forced) {
 // persistent device + pinned host scratch of the information calls (drivers call them at every measurement step):
 // no allocation, one asynchronous copy into pinned memory, one wait
 static int info_scratch(hc_cells *C, size_t doubles) {
-  if (C->info_cap >= doubles) return HC_OK;
+  if (C->info.cap() >= doubles) return HC_OK;
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  if (C->d_info) HC_HIP(hipFree(C->d_info));
-  if (C->h_info) HC_HIP(hipHostFree(C->h_info));
-  C->d_info = C->h_info = nullptr; C->info_cap = 0;
-  const size_t cap = doubles + doubles / 4 + 1024;
-  HC_HIP(hipMalloc((void **)&C->d_info, cap * sizeof(double)));
-  HC_HIP(hipHostMalloc((void **)&C->h_info, cap * sizeof(double), hipHostMallocDefault));
-  C->info_cap = cap;
-  return HC_OK;
+  return C->info.reserve(doubles + doubles / 4 + 1024);
 }
 
 int hcp_mechanics_components(hc_cells *C, int type, double *comp) {
@@ -466,10 +459,10 @@ int hcp_mechanics_components(hc_cells *C, int type, double *comp) {
   const long n = C->ncells[type] * C->types[type]->host.nv;
   if (n == 0) return HC_OK;
   rc = info_scratch(C, (size_t)(18 * n)); if (rc != HC_OK) return rc;
-  rc = launch_mechanics(C, type, C->d_info); if (rc != HC_OK) return rc;
-  HC_HIP(hipMemcpyAsync(C->h_info, C->d_info, (size_t)(18 * n) * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+  rc = launch_mechanics(C, type, C->info.d); if (rc != HC_OK) return rc;
+  HC_HIP(hipMemcpyAsync(C->info.h, C->info.d, (size_t)(18 * n) * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  std::memcpy(comp, C->h_info, (size_t)(18 * n) * sizeof(double));
+  std::memcpy(comp, C->info.h, (size_t)(18 * n) * sizeof(double));
   return HC_OK;
 }
 
@@ -481,18 +474,18 @@ int hcp_cell_info(hc_cells *C, int type, double *volume, double *area, double *b
   if (nc == 0) return HC_OK;
   const CellTables &T = C->types[type]->host;
   rc = info_scratch(C, (size_t)(11 * nc)); if (rc != HC_OK) return rc;
-  double *d = C->d_info;
-  const long f = C->first[type];
-  hipLaunchKernelGGL(cell_info_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), T.nv, T.nt, (const int *)C->types[type]->d_tri,
-                     (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                     (const int *)(C->d_tag + C->cell0[type]), (const unsigned char *)(C->d_vdead + f), d, d + nc, d + 2 * nc, d + 8 * nc);
+  double *d = C->info.d;
+  const double *h = C->info.h;
+  const TypeArrays a = vert_arrays(C, type);
+  hipLaunchKernelGGL(cell_info_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), T.nv, T.nt, C->types[type]->d_tri, a.p[0], a.p[1], a.p[2], a.tag, a.dead,
+                     d, d + nc, d + 2 * nc, d + 8 * nc);
   HC_HIP(hipGetLastError());
-  HC_HIP(hipMemcpyAsync(C->h_info, d, (size_t)(11 * nc) * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipMemcpyAsync(C->info.h, d, (size_t)(11 * nc) * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  std::memcpy(volume, C->h_info, (size_t)nc * sizeof(double));
-  std::memcpy(area, C->h_info + nc, (size_t)nc * sizeof(double));
-  std::memcpy(bbox, C->h_info + 2 * nc, (size_t)(6 * nc) * sizeof(double));
-  std::memcpy(centroid, C->h_info + 8 * nc, (size_t)(3 * nc) * sizeof(double));
+  std::memcpy(volume, h, (size_t)nc * sizeof(double));
+  std::memcpy(area, h + nc, (size_t)nc * sizeof(double));
+  std::memcpy(bbox, h + 2 * nc, (size_t)(6 * nc) * sizeof(double));
+  std::memcpy(centroid, h + 8 * nc, (size_t)(3 * nc) * sizeof(double));
   return HC_OK;
 }
 

@@ -85,9 +85,7 @@ __global__ __launch_bounds__(256) void preinlet_copy_kernel(int nv, int n, const
   }
 }
 
-struct SelectBlock {   // mapped pinned block the select kernel writes, all types of one container back to back
-  double *h = nullptr, *d = nullptr; long cap = 0;
-};
+using SelectBlock = MappedBuf<double>;   // mapped pinned block the select kernel writes, SEL doubles per cell, all types of one container back to back
 
 }  // namespace
 
@@ -100,25 +98,16 @@ struct hc_preinlet_cells {
   long injected = 0, rejected = 0, removed = 0, checks = 0;
   std::set<std::pair<int, long>> offered;   // (type, id') already offered to the domain
   SelectBlock sel[2];
-  hipEvent_t done = nullptr;
-  ~hc_preinlet_cells() {
-    for (SelectBlock &b : sel) if (b.h) hipHostFree(b.h);
-    if (done) hipEventDestroy(done);
-  }
+  Event done;
 };
 
 static int axis_nodes(const hc_lattice *L, int axis) { return axis == 0 ? L->nx : axis == 1 ? L->ny : L->nz; }
 
 // room for `total` cell slots in a select block; the old block is given up only once the last check has left it
 static int reserve_select(hc_preinlet_cells *X, SelectBlock &b, long total) {
-  if (total <= b.cap) return HC_OK;
-  if (b.h) { HC_HIP(hipEventSynchronize(X->done)); HC_HIP(hipHostFree(b.h)); }
-  b.h = b.d = nullptr; b.cap = 0;
-  const long cap = total + total / 4 + 64;
-  HC_HIP(hipHostMalloc((void **)&b.h, (size_t)(SEL * cap) * sizeof(double), hipHostMallocMapped));
-  HC_HIP(hipHostGetDevicePointer((void **)&b.d, b.h, 0));
-  b.cap = cap;
-  return HC_OK;
+  if ((size_t)(SEL * total) <= b.cap) return HC_OK;
+  if (b) HC_HIP(hipEventSynchronize(X->done));
+  return b.reserve((size_t)(SEL * (total + total / 4 + 64)));
 }
 
 // the select kernel over every type of a container; block row of (type t, slot c) = first[t] + c
@@ -129,11 +118,11 @@ static int launch_select(hc_preinlet_cells *X, int which, hc_cells *C, double Lp
   SelectBlock &b = X->sel[which];
   { int rc = reserve_select(X, b, total); if (rc != HC_OK) return rc; }
   for (int t = 0; t < C->ntypes; t++) {
-    const long nc = C->ncells[t], f = C->first[t];
+    const long nc = C->ncells[t];
     if (nc == 0) continue;
-    hipLaunchKernelGGL(preinlet_select_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), C->types[t]->host.nv, (const double *)(C->pos[0] + f),
-                       (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f), (const int *)(C->d_tag + C->cell0[t]),
-                       (const unsigned char *)(C->d_vdead + f), X->axis, Lp, lo, hi, b.d + SEL * first[(size_t)t]);
+    const TypeArrays a = vert_arrays(C, t);
+    hipLaunchKernelGGL(preinlet_select_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), C->types[t]->host.nv, a.p[0], a.p[1], a.p[2], a.tag, a.dead,
+                       X->axis, Lp, lo, hi, b.dev + SEL * first[(size_t)t]);
     HC_HIP(hipGetLastError());
   }
   return HC_OK;
@@ -161,7 +150,7 @@ int hcp_preinlet_create(hc_preinlet_cells **out, hc_cells *pre, hc_cells *domain
   std::unique_ptr<hc_preinlet_cells> X(new hc_preinlet_cells());
   X->pre = pre; X->dom = domain; X->axis = axis; X->orient = orientation; X->lo = window_lo; X->hi = window_hi; X->Lp = Lp; X->stride = id_stride;
   for (int d = 0; d < 3; d++) X->shift[d] = shift[d];
-  HC_HIP(hipEventCreateWithFlags(&X->done, hipEventDisableTiming));
+  { const int rc = X->done.create(); if (rc != HC_OK) return rc; }
   hc_cells *both[2] = {pre, domain};
   for (int w = 0; w < 2; w++) {   // the blocks of the cells held now, so that a check allocates only when the cell set has outgrown them
     long total = 0;
@@ -186,7 +175,7 @@ int hcp_preinlet_counts(const hc_preinlet_cells *X, long out[4]) {
 
 int hcp_preinlet_destroy(hc_preinlet_cells *X) {
   if (!X) return HC_OK;
-  hipStreamSynchronize(hc::stream());
+  (void)hipStreamSynchronize(hc::stream());
   delete X;
   return HC_OK;
 }
@@ -214,7 +203,7 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
   std::vector<Cand> cand[8];
   for (int t = 0; t < ntypes; t++)
     for (long c = 0; c < P->ncells[t]; c++) {
-      const double *r = X->sel[0].h + SEL * (pfirst[(size_t)t] + c);
+      const double *r = X->sel[0] + SEL * (pfirst[(size_t)t] + c);
       if (r[0] == 0.0) continue;
       Cand k; k.slot = (int)c; k.lap = (long)r[1];
       for (int e = 0; e < 6; e++) k.ext[e] = r[2 + e];
@@ -227,7 +216,7 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
     for (int t = 0; t < ntypes; t++) {
       std::vector<int> gone;
       for (long c = 0; c < D->ncells[t]; c++) {
-        const double *r = X->sel[1].h + SEL * (dfirst[(size_t)t] + c);
+        const double *r = X->sel[1] + SEL * (dfirst[(size_t)t] + c);
         const double cmin = r[2 + 2 * X->axis], cmax = r[3 + 2 * X->axis];
         if (cmin > cmax) continue;   // no live vertex
         if (X->orient < 0 ? cmax > X->sink_plane : cmin < X->sink_plane) gone.push_back((int)c);

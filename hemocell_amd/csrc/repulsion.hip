@@ -120,11 +120,8 @@ int hcp_set_repulsion(hc_cells *C, double r_const, double r_cutoff_lu, int times
   HC_REQUIRE(C && r_cutoff_lu > 0 && timescale >= 1, "hcp_set_repulsion: bad arguments");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
   C->rep_const = r_const; C->rep_cutoff = r_cutoff_lu; C->rep_timescale = timescale;
-  if (!C->rep_enabled) {
-    C->rep_enabled = 1;
-    if (C->cap > 0) for (int d = 0; d < 3; d++) { HC_HIP(hipMalloc((void **)&C->rep[d], C->cap * sizeof(double))); HC_HIP(hipMemset(C->rep[d], 0, C->cap * sizeof(double))); }
-  }
-  return HC_OK;
+  C->rep_enabled = 1;
+  return ensure_rep(C);
 }
 
 // cellfields->applyRepulsionForce() (core/hemoCell.cpp:307-309 -> core/hemoCellParticleField.cpp:696-743)
@@ -133,31 +130,31 @@ int hcp_repulsion(hc_cells *C) {
   HC_REQUIRE(C->rep_enabled, "hcp_repulsion: call hcp_set_repulsion first");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
   if (C->nverts == 0) return HC_OK;
-  if (!C->rep[0]) for (int d = 0; d < 3; d++) { HC_HIP(hipMalloc((void **)&C->rep[d], C->cap * sizeof(double))); HC_HIP(hipMemset(C->rep[d], 0, C->cap * sizeof(double))); }
+  if ((rc = ensure_rep(C)) != HC_OK) return rc;
   const long n = C->nverts;
   if (n > C->sort_cap) {
     HC_HIP(hipStreamSynchronize(hc::stream()));
-    for (int k = 0; k < 2; k++) { if (C->d_keys[k]) HC_HIP(hipFree(C->d_keys[k])); if (C->d_vals[k]) HC_HIP(hipFree(C->d_vals[k])); }
-    if (C->d_sort_tmp) HC_HIP(hipFree(C->d_sort_tmp));
-    C->sort_cap = n + n / 4 + 1024;
-    for (int k = 0; k < 2; k++) { HC_HIP(hipMalloc((void **)&C->d_keys[k], C->sort_cap * sizeof(unsigned int))); HC_HIP(hipMalloc((void **)&C->d_vals[k], C->sort_cap * sizeof(int))); }
-    C->sort_tmp_bytes = 0; C->d_sort_tmp = nullptr;
-    HC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, C->sort_tmp_bytes, C->d_keys[0], C->d_keys[1], C->d_vals[0], C->d_vals[1], (int)C->sort_cap, 0, 32, hc::stream()));
-    HC_HIP(hipMalloc(&C->d_sort_tmp, C->sort_tmp_bytes));
+    const long cap = n + n / 4 + 1024;
+    C->sort_cap = 0;
+    for (int k = 0; k < 2; k++) if ((rc = C->d_keys[k].reserve((size_t)cap)) != HC_OK || (rc = C->d_vals[k].reserve((size_t)cap)) != HC_OK) return rc;
+    size_t tmp_bytes = 0;
+    HC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, C->d_keys[0].p, C->d_keys[1].p, C->d_vals[0].p, C->d_vals[1].p, (int)cap, 0, 32, hc::stream()));
+    if ((rc = C->d_sort_tmp.reserve(tmp_bytes)) != HC_OK) return rc;
+    C->sort_cap = cap;
   }
   const LatView v = make_view(C->L);
   long packed0 = 0;
   for (int t = 0; t < C->ntypes; t++) {
-    const long nt = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+    const long nt = C->ncells[t] * C->types[t]->host.nv;
     if (nt == 0) continue;
-    hipLaunchKernelGGL(rep_keys_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, hc::stream(), v, nt, f, packed0,
-                       (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f), C->d_keys[0], C->d_vals[0],
-                       (const int *)(C->d_vert_cell + f), (const int *)C->d_tag, (const unsigned char *)(C->d_vdead + f));
+    const TypeArrays a = vert_arrays(C, t);
+    hipLaunchKernelGGL(rep_keys_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, hc::stream(), v, nt, C->first[t], packed0, a.p[0], a.p[1], a.p[2],
+                       C->d_keys[0], C->d_vals[0], a.vert_cell, a.tag_all, a.dead);
     HC_HIP(hipGetLastError());
     packed0 += nt;
   }
-  size_t tmp = C->sort_tmp_bytes;
-  HC_HIP(hipcub::DeviceRadixSort::SortPairs(C->d_sort_tmp, tmp, C->d_keys[0], C->d_keys[1], C->d_vals[0], C->d_vals[1], (int)n, 0, 32, hc::stream()));
+  size_t tmp = C->d_sort_tmp.cap;
+  HC_HIP(hipcub::DeviceRadixSort::SortPairs(C->d_sort_tmp.p, tmp, C->d_keys[0].p, C->d_keys[1].p, C->d_vals[0].p, C->d_vals[1].p, (int)n, 0, 32, hc::stream()));
   hipLaunchKernelGGL(rep_force_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, C->cap, n, (const unsigned int *)C->d_keys[1],
                      (const int *)C->d_vals[1], (const int *)C->d_vert_cell, (const double *)C->pos[0], (const double *)C->pos[1], (const double *)C->pos[2],
                      C->rep[0], C->rep[1], C->rep[2], C->rep_const, C->rep_cutoff);
@@ -197,14 +194,11 @@ int hcp_set_boundary_repulsion(hc_cells *C, double br_const, double br_cutoff_lu
         }
         if (near) flag[(size_t)xp * L->xs + (size_t)y * nz + z] = 1;
       }
-  if (!C->d_bflag) HC_HIP(hipMalloc((void **)&C->d_bflag, L->npad));
+  if ((rc = C->d_bflag.reserve(L->npad)) != HC_OK) return rc;
   HC_HIP(hipMemcpy(C->d_bflag, flag.data(), L->npad, hipMemcpyHostToDevice));
   C->brep_const = br_const; C->brep_cutoff = br_cutoff_lu; C->brep_timescale = timescale;
-  if (!C->brep_enabled) {
-    C->brep_enabled = 1;
-    if (C->cap > 0 && !C->rep[0]) for (int d = 0; d < 3; d++) { HC_HIP(hipMalloc((void **)&C->rep[d], C->cap * sizeof(double))); HC_HIP(hipMemset(C->rep[d], 0, C->cap * sizeof(double))); }
-  }
-  return HC_OK;
+  C->brep_enabled = 1;
+  return ensure_rep(C);
 }
 
 // cellfields->applyBoundaryRepulsionForce() (core/hemoCell.cpp:310-312 -> core/hemoCellParticleField.cpp:891-918)
@@ -213,15 +207,14 @@ int hcp_boundary_repulsion(hc_cells *C) {
   HC_REQUIRE(C->brep_enabled, "hcp_boundary_repulsion: call hcp_set_boundary_repulsion first");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
   if (C->nverts == 0) return HC_OK;
-  if (!C->rep[0]) for (int d = 0; d < 3; d++) { HC_HIP(hipMalloc((void **)&C->rep[d], C->cap * sizeof(double))); HC_HIP(hipMemset(C->rep[d], 0, C->cap * sizeof(double))); }
+  if ((rc = ensure_rep(C)) != HC_OK) return rc;
   const LatView v = make_view(C->L);
   for (int t = 0; t < C->ntypes; t++) {
-    const long n = C->ncells[t] * C->types[t]->host.nv, f = C->first[t];
+    const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
-    hipLaunchKernelGGL(boundary_rep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, (const uint8_t *)C->d_bflag,
-                       (const double *)(C->pos[0] + f), (const double *)(C->pos[1] + f), (const double *)(C->pos[2] + f),
-                       C->rep[0] + f, C->rep[1] + f, C->rep[2] + f, C->brep_const, C->brep_cutoff,
-                       (const int *)(C->d_vert_cell + f), (const int *)C->d_tag, (const unsigned char *)(C->d_vdead + f));
+    const TypeArrays a = vert_arrays(C, t);   // r exists: ensure_rep above
+    hipLaunchKernelGGL(boundary_rep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, C->d_bflag, a.p[0], a.p[1], a.p[2],
+                       a.r[0], a.r[1], a.r[2], C->brep_const, C->brep_cutoff, a.vert_cell, a.tag_all, a.dead);
     HC_HIP(hipGetLastError());
   }
   return HC_OK;
@@ -233,16 +226,11 @@ int hcp_download_repulsion(hc_cells *C, double *out) {
   int rc = settle(C); if (rc != HC_OK) return rc;
   rc = sync_to_device(C); if (rc != HC_OK) return rc;
   HC_HIP(hipStreamSynchronize(hc::stream()));
-  std::vector<double> tmp;
   size_t o = 0;
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
-    tmp.resize((size_t)n);
-    for (int d = 0; d < 3; d++) {
-      if (n && C->rep[d]) HC_HIP(hipMemcpy(tmp.data(), C->rep[d] + C->first[t], (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-      else std::fill(tmp.begin(), tmp.end(), 0.0);
-      for (long i = 0; i < n; i++) out[o + 3 * (size_t)i + d] = tmp[(size_t)i];
-    }
+    if (!C->rep[0]) std::fill(out + o, out + o + 3 * (size_t)n, 0.0);
+    else if (n && (rc = download_xyz(out + o, C->rep, C->first[t], n)) != HC_OK) return rc;
     o += 3 * (size_t)n;
   }
   return HC_OK;

@@ -28,6 +28,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -40,48 +41,42 @@ double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock
 struct Slab {
   hc_lattice *L = nullptr;
   hc_cells *C = nullptr;                     // null: fluid only
-  double *hs[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *hr[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [width - 1][side] device buffers
+  DevBuf<double> hs[2][2], hr[2][2];         // [width - 1][side] device buffers
   int pending_width = 0;                     // a face exchange of this width is on its way and not yet unpacked
   bool halo_fresh = false;                   // the halo planes of f[cur] hold what the next collide needs
   bool spread_done = false;                  // the spread of the coming iteration already ran beside the last collide
   bool planned = false;                      // the cell extents for the coming envelope sync are on their way to the host
   // envelope synchronisation: id headers [side][type][MAX_HDR] (pinned staging, device send / receive, pinned landing)
-  long *h_hdr_s = nullptr, *h_hdr_r = nullptr, *d_hdr_s = nullptr, *d_hdr_r = nullptr; int hdr_types = 0;
-  hipEvent_t hdr_ev = nullptr, rec_ready = nullptr, rec_done = nullptr, halo_packed = nullptr, halo_arrived = nullptr, u_packed = nullptr, u_arrived = nullptr;
-  double *us[2] = {nullptr, nullptr};         // face-plane velocities on their way to the neighbours ([side][3][plane]; they land in L->halo_u)
-  double *d_rec_s[2] = {nullptr, nullptr}, *d_rec_r[2] = {nullptr, nullptr}; size_t rec_cap_s[2] = {0, 0}, rec_cap_r[2] = {0, 0};
+  Staged<long> hdr_s, hdr_r; int hdr_types = 0;   // hdr_r.ev: the headers have landed
+  Event rec_ready, rec_done, halo_packed, halo_arrived, u_packed, u_arrived;
+  DevBuf<double> us[2];                      // face-plane velocities on their way to the neighbours ([side][3][plane]; they land in L->halo_u)
+  DevBuf<double> d_rec_s[2], d_rec_r[2];
   double stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
-std::map<hc_lattice *, Slab *> g_slabs;
+std::map<hc_lattice *, std::unique_ptr<Slab>> g_slabs;
 
 bool periodic_x(const hc_lattice *L) { return L->periodic[0] != 0; }
 
 int make_slab(hc_lattice *L, hc_cells *C, Slab **out) {
   auto it = g_slabs.find(L);
-  Slab *S = it == g_slabs.end() ? nullptr : it->second;
+  Slab *S = it == g_slabs.end() ? nullptr : it->second.get();
   if (!S) {
     if (!hcm::active()) { hc::set_error("a lattice with n_slabs > 1 needs the ranks connected first (hc_comm_init_env / hc_comm_init)"); return HC_ERR_STATE; }
     if (hcm::world() != L->n_slabs && !(hcm::world() == 1 && L->n_slabs >= 1)) { hc::set_error("the lattice was created for " + std::to_string(L->n_slabs) + " slabs but the world has " + std::to_string(hcm::world()) + " ranks"); return HC_ERR_STATE; }
-    S = new Slab(); S->L = L;
+    std::unique_ptr<Slab> fresh(new Slab());   // an early return frees what exists by then (halo_u: with the lattice)
+    S = fresh.get(); S->L = L;
+    int rc;
     for (int w = 0; w < 2; w++)
-      for (int side = 0; side < 2; side++) {
-        HC_HIP(hipMalloc((void **)&S->hs[w][side], hcl_halo_doubles(L, w + 1) * sizeof(double)));
-        HC_HIP(hipMalloc((void **)&S->hr[w][side], hcl_halo_doubles(L, w + 1) * sizeof(double)));
-      }
-    HC_HIP(hipEventCreateWithFlags(&S->hdr_ev, hipEventDisableTiming));
-    HC_HIP(hipEventCreateWithFlags(&S->rec_ready, hipEventDisableTiming));
-    HC_HIP(hipEventCreateWithFlags(&S->rec_done, hipEventDisableTiming));
-    HC_HIP(hipEventCreateWithFlags(&S->halo_packed, hipEventDisableTiming));
-    HC_HIP(hipEventCreateWithFlags(&S->halo_arrived, hipEventDisableTiming));
-    HC_HIP(hipEventCreateWithFlags(&S->u_packed, hipEventDisableTiming));
-    HC_HIP(hipEventCreateWithFlags(&S->u_arrived, hipEventDisableTiming));
+      for (int side = 0; side < 2; side++)
+        if ((rc = S->hs[w][side].reserve(hcl_halo_doubles(L, w + 1))) != HC_OK || (rc = S->hr[w][side].reserve(hcl_halo_doubles(L, w + 1))) != HC_OK) return rc;
+    for (Event *e : {&S->hdr_r.ev, &S->rec_ready, &S->rec_done, &S->halo_packed, &S->halo_arrived, &S->u_packed, &S->u_arrived})
+      if ((rc = e->create()) != HC_OK) return rc;
     for (int side = 0; side < 2; side++) {
-      HC_HIP(hipMalloc((void **)&S->us[side], 3 * L->plane * sizeof(double)));
-      HC_HIP(hipMalloc((void **)&L->halo_u[side], 3 * L->plane * sizeof(double)));
+      if ((rc = S->us[side].reserve(3 * L->plane)) != HC_OK || (rc = L->halo_u[side].reserve(3 * L->plane)) != HC_OK) return rc;
       HC_HIP(hipMemset(L->halo_u[side], 0, 3 * L->plane * sizeof(double)));
     }
     L->halo_u_valid = false;
-    g_slabs[L] = S;
+    g_slabs[L] = std::move(fresh);
   }
   if (C) {
     double dmax = 0.0;
@@ -91,15 +86,9 @@ int make_slab(hc_lattice *L, hc_cells *C, Slab **out) {
     S->C = C;
     if (S->hdr_types < C->ntypes) {
       HC_HIP(hipDeviceSynchronize());
-      if (S->h_hdr_s) HC_HIP(hipHostFree(S->h_hdr_s));
-      if (S->h_hdr_r) HC_HIP(hipHostFree(S->h_hdr_r));
-      if (S->d_hdr_s) HC_HIP(hipFree(S->d_hdr_s));
-      if (S->d_hdr_r) HC_HIP(hipFree(S->d_hdr_r));
-      const size_t bytes = (size_t)2 * C->ntypes * MAX_HDR * sizeof(long);
-      HC_HIP(hipHostMalloc((void **)&S->h_hdr_s, bytes, hipHostMallocDefault));
-      HC_HIP(hipHostMalloc((void **)&S->h_hdr_r, bytes, hipHostMallocDefault));
-      HC_HIP(hipMalloc((void **)&S->d_hdr_s, bytes));
-      HC_HIP(hipMalloc((void **)&S->d_hdr_r, bytes));
+      const size_t longs = (size_t)2 * C->ntypes * MAX_HDR;
+      int rc;
+      if ((rc = S->hdr_s.reserve(longs)) != HC_OK || (rc = S->hdr_r.reserve(longs)) != HC_OK) return rc;
       S->hdr_types = C->ntypes;
     }
   }
@@ -220,7 +209,7 @@ int sync_begin(Slab *S, std::vector<Plan> &plans) {
     C->ext_pending[t] = false;
     P.n = C->ext_n[t];
     if (P.n) HC_HIP(hipEventSynchronize(C->ext_done[t]));
-    P.ext.assign(C->h_ext[t], C->h_ext[t] + 4 * P.n);
+    P.ext.assign(C->h_ext[t].p, C->h_ext[t].p + 4 * P.n);
     const std::vector<long> &ids = C->hids[t];
     for (long c = 0; c < P.n; c++) {
       const double *e = &P.ext[(size_t)(4 * c)];
@@ -234,7 +223,7 @@ int sync_begin(Slab *S, std::vector<Plan> &plans) {
       std::stable_sort(P.send[side].begin(), P.send[side].end(), [&](int a, int b) { return ids[(size_t)a] < ids[(size_t)b]; });
       const size_t k = P.send[side].size(), g = P.gone.size(), gb = P.gone_before.size();
       if (k + g + gb + 2 > (size_t)MAX_HDR) { hc::set_error("more cells cross one slab face (" + std::to_string(k) + ") than the id header holds"); return HC_ERR_STATE; }
-      long *h = S->h_hdr_s + ((size_t)side * C->ntypes + t) * MAX_HDR;
+      long *h = S->hdr_s.h + ((size_t)side * C->ntypes + t) * MAX_HDR;
       h[0] = (long)k;
       for (size_t i = 0; i < k; i++) h[1 + i] = ids[(size_t)P.send[side][i]];
       h[1 + k] = (long)(g + gb);
@@ -245,24 +234,19 @@ int sync_begin(Slab *S, std::vector<Plan> &plans) {
   S->stats[6] += wall_s() - t_wait;
   const size_t side_bytes = (size_t)C->ntypes * MAX_HDR * sizeof(long);
   const hipStream_t X = transfer_stream();   // the headers depend on host data only: nothing to wait for
-  HC_HIP(hipMemcpyAsync(S->d_hdr_s, S->h_hdr_s, 2 * side_bytes, hipMemcpyHostToDevice, X));
-  int rc = hcm::exchange(X, periodic_x(L), S->d_hdr_s, side_bytes, (char *)S->d_hdr_s + side_bytes, side_bytes, S->d_hdr_r, side_bytes,
-                         (char *)S->d_hdr_r + side_bytes, side_bytes);
+  long *d_s = S->hdr_s.d, *d_r = S->hdr_r.d;
+  HC_HIP(hipMemcpyAsync(d_s, S->hdr_s.h, 2 * side_bytes, hipMemcpyHostToDevice, X));
+  int rc = hcm::exchange(X, periodic_x(L), d_s, side_bytes, (char *)d_s + side_bytes, side_bytes, d_r, side_bytes, (char *)d_r + side_bytes, side_bytes);
   if (rc != HC_OK) return rc;
-  HC_HIP(hipMemcpyAsync(S->h_hdr_r, S->d_hdr_r, 2 * side_bytes, hipMemcpyDeviceToHost, X));
-  HC_HIP(hipEventRecord(S->hdr_ev, X));
+  HC_HIP(hipMemcpyAsync(S->hdr_r.h, d_r, 2 * side_bytes, hipMemcpyDeviceToHost, X));
+  HC_HIP(hipEventRecord(S->hdr_r.ev, X));
   return HC_OK;
 }
 
-int grow(double **buf, size_t *cap, size_t doubles) {
-  if (*cap >= doubles) return HC_OK;
+int grow(DevBuf<double> &buf, size_t doubles) {
+  if (buf.cap >= doubles) return HC_OK;
   HC_HIP(hipDeviceSynchronize());   // rare: the old block may still be in use on either stream
-  if (*buf) HC_HIP(hipFree(*buf));
-  *buf = nullptr; *cap = 0;
-  const size_t n = doubles + doubles / 2 + 4096;
-  HC_HIP(hipMalloc((void **)buf, n * sizeof(double)));
-  *cap = n;
-  return HC_OK;
+  return buf.reserve(doubles + doubles / 2 + 4096);
 }
 
 // second part (main stream): the records of the crossing cells carry interpolated velocities, so those cells are
@@ -271,7 +255,7 @@ int sync_records(Slab *S, std::vector<Plan> &plans, hipStream_t comm_stream) {
   hc_cells *C = S->C; hc_lattice *L = S->L;
   int lo, hi; hcm::neighbours(periodic_x(L), lo, hi);
   const double t_wait = wall_s();
-  HC_HIP(hipEventSynchronize(S->hdr_ev));
+  HC_HIP(hipEventSynchronize(S->hdr_r.ev));
   S->stats[6] += wall_s() - t_wait;
   size_t send_d[2] = {0, 0}, recv_d[2] = {0, 0};
   for (int t = 0; t < C->ntypes; t++) {
@@ -280,7 +264,7 @@ int sync_records(Slab *S, std::vector<Plan> &plans, hipStream_t comm_stream) {
     for (int side = 0; side < 2; side++) {
       P.ids_r[side].clear(); P.tag_r[side].clear();
       if ((side == 0 ? lo : hi) < 0) continue;
-      const long *h = S->h_hdr_r + ((size_t)side * C->ntypes + t) * MAX_HDR;
+      const long *h = S->hdr_r.h + ((size_t)side * C->ntypes + t) * MAX_HDR;
       const long k = h[0];
       if (k < 0 || k + 2 > MAX_HDR) { hc::set_error("corrupt id header from a neighbour"); return HC_ERR_STATE; }
       const long g = h[1 + k];
@@ -295,8 +279,8 @@ int sync_records(Slab *S, std::vector<Plan> &plans, hipStream_t comm_stream) {
     if (!both.empty()) { const int rc = hcp_interpolate_cells(C, t, both.data(), (int)both.size()); if (rc != HC_OK) return rc; }
   }
   for (int side = 0; side < 2; side++) {
-    int rc = grow(&S->d_rec_s[side], &S->rec_cap_s[side], send_d[side]); if (rc != HC_OK) return rc;
-    rc = grow(&S->d_rec_r[side], &S->rec_cap_r[side], recv_d[side]); if (rc != HC_OK) return rc;
+    int rc = grow(S->d_rec_s[side], send_d[side]); if (rc != HC_OK) return rc;
+    rc = grow(S->d_rec_r[side], recv_d[side]); if (rc != HC_OK) return rc;
   }
   // periodic images are shifted by the domain length when they cross the seam (core/hemoCellParticleDataTransfer.cpp:33-65)
   const double shift[2] = {(periodic_x(L) && L->x0 == 0) ? (double)L->nx_global : 0.0,
@@ -523,18 +507,9 @@ void halos_stale(hc_lattice *L) {
 void lattice_destroyed(hc_lattice *L) {
   auto it = g_slabs.find(L);
   if (it == g_slabs.end()) return;
-  Slab *S = it->second;
-  hipDeviceSynchronize();
-  for (int w = 0; w < 2; w++) for (int side = 0; side < 2; side++) { if (S->hs[w][side]) hipFree(S->hs[w][side]); if (S->hr[w][side]) hipFree(S->hr[w][side]); }
-  if (S->h_hdr_s) hipHostFree(S->h_hdr_s);
-  if (S->h_hdr_r) hipHostFree(S->h_hdr_r);
-  if (S->d_hdr_s) hipFree(S->d_hdr_s);
-  if (S->d_hdr_r) hipFree(S->d_hdr_r);
-  for (int side = 0; side < 2; side++) { if (S->d_rec_s[side]) hipFree(S->d_rec_s[side]); if (S->d_rec_r[side]) hipFree(S->d_rec_r[side]); }
-  for (hipEvent_t e : {S->hdr_ev, S->rec_ready, S->rec_done, S->halo_packed, S->halo_arrived, S->u_packed, S->u_arrived}) if (e) hipEventDestroy(e);
-  for (int side = 0; side < 2; side++) { if (S->us[side]) hipFree(S->us[side]); if (L->halo_u[side]) hipFree(L->halo_u[side]); L->halo_u[side] = nullptr; }
+  (void)hipDeviceSynchronize();
+  for (int side = 0; side < 2; side++) L->halo_u[side].reset();
   L->halo_u_valid = false;
-  delete S;
   g_slabs.erase(it);
 }
 
