@@ -20,7 +20,9 @@ __global__ void rep_keys_kernel(LatView v, long n, long first, long packed0, con
   if (i >= n) return;
   long lx = nearest_node(px[i]) - v.x0, ly = nearest_node(py[i]), lz = nearest_node(pz[i]);
   bool ok = !dead[i] && tag[vert_cell[i]] != 1;   // removed particles and gone cells are in no bin
-  if (v.wrap_x) lx = pmod(lx, v.nx); else ok = ok && (lx >= -HALO && lx < v.nx + HALO);
+  // a slab bins the copies on its halo planes; a single open domain bins what update_pg bins (:158-161): nothing outside it
+  const int hx = v.halo_x ? HALO : 0;
+  if (v.wrap_x) lx = pmod(lx, v.nx); else ok = ok && (lx >= -hx && lx < v.nx + hx);
   if (ly < 0 || ly >= v.ny) { if (v.per_y) ly = pmod(ly, v.ny); else ok = false; }
   if (lz < 0 || lz >= v.nz) { if (v.per_z) lz = pmod(lz, v.nz); else ok = false; }
   keys[packed0 + i] = ok ? (unsigned int)((lx + HALO) * (long)v.plane + ly * v.nz + lz) : 0xffffffffu;
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(256) void rep_force_kernel(LatView v, long cap, lon
         for (int dz = -1; dz <= 1; dz++) {
           long bx = lxp + dx, by = ly + dy, bz = lz + dz;
           if (v.wrap_x) { if (bx < HALO) bx += v.nx; else if (bx >= v.nx + HALO) bx -= v.nx; }
-          else if (bx < 0 || bx >= v.nx + 2 * HALO) continue;
+          else if (v.halo_x ? (bx < 0 || bx >= v.nx + 2 * HALO) : (bx < HALO || bx >= v.nx + HALO)) continue;   // bx is padded
           if (by < 0) { if (!v.per_y) continue; by += v.ny; } else if (by >= v.ny) { if (!v.per_y) continue; by -= v.ny; }
           if (bz < 0) { if (!v.per_z) continue; bz += v.nz; } else if (bz >= v.nz) { if (!v.per_z) continue; bz -= v.nz; }
           const unsigned int nkey = (unsigned int)(bx * (long)v.plane + by * v.nz + bz);
