@@ -156,8 +156,11 @@ __device__ __forceinline__ void node_velocity(const LatView &v, const Pops<OPEN>
   u[2] = jz * invRho + (bz + pv.F[3 * node + 2]) / 2.0;
 }
 
-// node velocities of one face plane of a slab (lx = 0 or nx - 1), for the neighbour whose first halo plane it is
-__global__ __launch_bounds__(256) void face_velocity_kernel(LatView v, PopView pv, int lx0, double *out0, int lx1, double *out1) {
+// node velocities of one face plane of a slab (lx = 0 or nx - 1), for the neighbour whose first halo plane it is.  OPEN: a fluid
+// open-boundary node of the plane sends the moments of its completed populations (a velocity node u_bc + F / 2), the rule the
+// neighbour's interpolation follows for its own nodes; with plain moments the unknown populations would count as zeros
+template <bool OPEN = false>
+__global__ __launch_bounds__(256) void face_velocity_kernel(LatView v, Pops<OPEN> pv, int lx0, double *out0, int lx1, double *out1) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= v.ny_nz) return;
   const int lx = blockIdx.y ? lx1 : lx0;           // blockIdx.y: which of the (up to two) planes of the launch
@@ -165,7 +168,7 @@ __global__ __launch_bounds__(256) void face_velocity_kernel(LatView v, PopView p
   const int ly = k / v.nz, lz = k - ly * v.nz;
   const long node = (long)(lx + HALO) * v.plane + (long)ly * v.nz + lz;
   double u[3] = {0.0, 0.0, 0.0};
-  if (v.mask[node] == 0) node_velocity<false>(v, pv, lx, ly, lz, node, u);   // stencils admit fluid nodes only; slabs have no open boundaries
+  if (v.mask[node] == 0) node_velocity<OPEN>(v, pv, lx, ly, lz, node, u);   // stencils admit fluid nodes only
   out[k] = u[0]; out[v.ny_nz + k] = u[1]; out[2L * v.ny_nz + k] = u[2];
 }
 
@@ -757,13 +760,14 @@ int hcp_interpolate(hc_cells *C) {
 
 // the message of a velocity update (slab.hip): u = j/rho + F/2 on this slab's face plane `side`, post-stream state, packed as
 // [3][ny*nz] for the neighbour on that side.  The face plane and the plane behind it have been collided and the halo plane
-// in front of it holds the neighbour's crossing populations.
+// in front of it holds the neighbour's crossing populations.  A lattice with open-boundary nodes runs the OPEN instantiation,
+// like the interpolation kernels (launch_open).
 int hcl_face_velocity_pack(hc_lattice *L, int side, double *dev_buf) {
   HC_REQUIRE(L && dev_buf && (side == 0 || side == 1), "hcl_face_velocity_pack: bad arguments");
   LatView v = make_view(L);
   v.halo_u[0] = v.halo_u[1] = nullptr;   // own planes only: nothing here reads a halo velocity
   const PopView pv = make_pops(L);
-  hipLaunchKernelGGL(face_velocity_kernel, dim3((unsigned)((L->plane + 255) / 256), 1, 1), dim3(256), 0, hc::stream(), v, pv, side == 0 ? 0 : L->nx - 1, dev_buf, 0, (double *)nullptr);
+  HC_LAUNCH_POPS(face_velocity_kernel, dim3((unsigned)((L->plane + 255) / 256), 1, 1), dim3(256), v, pv, side == 0 ? 0 : L->nx - 1, dev_buf, 0, (double *)nullptr);
   HC_HIP(hipGetLastError());
   return HC_OK;
 }
@@ -775,7 +779,7 @@ int hcl_face_velocity_pack_both(hc_lattice *L, double *dev_lo, double *dev_hi) {
   LatView v = make_view(L);
   v.halo_u[0] = v.halo_u[1] = nullptr;
   const PopView pv = make_pops(L);
-  hipLaunchKernelGGL(face_velocity_kernel, dim3((unsigned)((L->plane + 255) / 256), 2, 1), dim3(256), 0, hc::stream(), v, pv, 0, dev_lo, L->nx - 1, dev_hi);
+  HC_LAUNCH_POPS(face_velocity_kernel, dim3((unsigned)((L->plane + 255) / 256), 2, 1), dim3(256), v, pv, 0, dev_lo, L->nx - 1, dev_hi);
   HC_HIP(hipGetLastError());
   return HC_OK;
 }

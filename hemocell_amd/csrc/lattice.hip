@@ -963,7 +963,12 @@ static bool ob_node(const hc_lattice *L, const int *c, size_t *index) {
 // who: the entry point the caller used, for the messages
 static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int orientation, const int *nodes, int n, int *first_slot) {
   HC_REQUIRE(L && (n == 0 || nodes), who + ": null pointer");
-  HC_REQUIRE(L->n_slabs == 1, who + ": open boundaries need the whole domain on one GPU (n_slabs = 1)");
+  // A slab declares its own nodes, in local coordinates and with slots of its own.  The completion touches the node's gathered
+  // populations only, and on a face plane those have crossed with the step's face message (an x-normal node at a domain end
+  // gathers the zeros of a halo plane nobody fills, as the single domain does), so nothing else of the schedule changes.
+  // Like every step and observer of a slab, the declaration belongs to a connected run: a lone lattice that merely names
+  // n_slabs > 1 is refused as it always was.
+  HC_REQUIRE(L->n_slabs == 1 || hcm::active(), who + ": open boundaries on a lattice with n_slabs > 1 need the ranks connected first (hc_comm_init_env / hc_comm_init); an unconnected lattice takes them with n_slabs = 1");
   HC_REQUIRE(kind == HC_OB_VELOCITY || kind == HC_OB_PRESSURE, who + ": kind must be HC_OB_VELOCITY or HC_OB_PRESSURE");
   HC_REQUIRE(orientation == -1 || orientation == 1, who + ": orientation must be -1 (N) or +1 (P)");
   HC_REQUIRE(axis >= 0 && axis <= 2, who + ": axis must be 0, 1 or 2");
@@ -1152,7 +1157,9 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
                         const int *pre_idx, int n, int domain_first_slot) {
   HC_REQUIRE(out && pre && domain && n >= 0 && (n == 0 || pre_idx), "hcl_preinlet_create: bad arguments");
   HC_REQUIRE(axis >= 0 && axis <= 2, "hcl_preinlet_create: axis must be 0, 1 or 2");
-  HC_REQUIRE(pre->n_slabs == 1 && domain->n_slabs == 1, "hcl_preinlet_create: needs n_slabs = 1 on both lattices");
+  HC_REQUIRE(pre->n_slabs == 1, "hcl_preinlet_create: needs n_slabs = 1 on the pre-inlet lattice");
+  // a slab domain: the inlet plane of an x direction lies on one rank, whose local slots these are; a y or z plane would span the ranks
+  HC_REQUIRE(domain->n_slabs == 1 || axis == 0, "hcl_preinlet_create: axis 1 and 2 need n_slabs = 1 on the domain; a slab domain is coupled along x only (axis 0)");
   HC_REQUIRE(pre_plane >= 0 && pre_plane < axis_extent(pre, axis), "hcl_preinlet_create: plane outside the pre-inlet lattice");
   for (int i = 0; i < n; i++) HC_REQUIRE(pre_idx[i] >= 0 && (size_t)pre_idx[i] < plane_nodes(pre, axis), "hcl_preinlet_create: in-plane index out of range");
   HC_REQUIRE(domain_first_slot >= 0 && (long)domain_first_slot + n <= (long)domain->ob_n, "hcl_preinlet_create: slots out of range on the domain");

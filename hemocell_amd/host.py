@@ -444,12 +444,22 @@ class PreInlet:
     then one hc_preinlet_iterate -- both systems step with their cells (particle_timescale, force_limit,
     deletion_check_every), the fluid is handed over, and every cells_every iterations the cells are checked (one host wait per
     check); applyPreInletCells() is one check, cell_counts() = (injected, rejected, removed by the sink, checks).  Partly
-    arrived cells are never added.  Without cells= the coupling is the fluid's alone."""
+    arrived cells are never added.  Without cells= the coupling is the fluid's alone.
+    The domain may be one x-slab of a multi-rank run (n_slabs > 1) for the fluid coupling along x: the object lives on the rank
+    that holds the inlet plane -- rank 0 with plane 0 for Xneg, the last rank with plane nx - 1 for Xpos -- beside its own
+    whole pre-inlet lattice; domain_x is that rank's local plane and the slots are its local slots.  The domain's step inside
+    iterate(n) is then collective: every other rank steps its slab the same number of times (collideAndStream(n) or
+    HemoCell.iterate(n)).  Other directions, a pre-inlet on slabs and cells= with a slab are refused."""
 
     def __init__(self, preinlet, domain, yz, pre_x, domain_x, direction="Xpos", pre_origin=(0, 0), domain_origin=(0, 0),
                  device=False, cells=None, window=None, shift=(0.0, 0.0, 0.0), id_stride=None, sink=None, cells_every=1,
                  particle_timescale=1, force_limit=True, deletion_check_every=1):
         axis, sign = _preinlet_direction(direction)
+        if getattr(preinlet, "n_slabs", 1) != 1:
+            raise HcError("PreInlet: the pre-inlet lattice needs n_slabs = 1 (it lives whole on the rank that holds the inlet plane)")
+        if getattr(domain, "n_slabs", 1) != 1 and axis != 0:
+            raise HcError("PreInlet: direction %s needs n_slabs = 1 on the domain; a slab is fed along x only "
+                          "(Xneg on rank 0, Xpos on the last rank)" % direction)
         if cells is not None:
             if not device:
                 raise HcError("PreInlet: cells= needs device=True (the cells cross on the device)")

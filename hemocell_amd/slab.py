@@ -52,6 +52,32 @@ def comm_finalize():
     host.check(host.capi.lib().hc_comm_finalize())
 
 
+def open_boundary_rows(where_global, x0, nx, nc=None, values=None):
+    """The part of an open-boundary declaration that falls on the slab [x0, x0 + nx).  where_global: an inclusive box
+    (x0, x1, y0, y1, z0, z1) or an [n][3] node list, GLOBAL node coordinates; its nodes are taken in box order (x outermost, z
+    innermost) or list order.  Returns (box, nodes, rows, values): the box clipped to the slab and translated to local
+    coordinates (None for a node list, or where the box misses the slab), the slab's nodes [m][3] in local coordinates, their
+    rows in the global order -- ascending, so the per-rank lists concatenated in rank order are the global order of a box --
+    and, with nc and values (one value or one per node, nc components each), this slab's rows of them [m][nc].  Pure numpy."""
+    w = np.asarray(where_global, dtype=np.int64)
+    box = None
+    if w.shape == (6,):
+        g = np.mgrid[w[0]:w[1] + 1, w[2]:w[3] + 1, w[4]:w[5] + 1].reshape(3, -1).T
+        lo, hi = max(int(w[0]), x0), min(int(w[1]), x0 + nx - 1)
+        if lo <= hi and w[2] <= w[3] and w[4] <= w[5]:
+            box = (lo - x0, hi - x0, int(w[2]), int(w[3]), int(w[4]), int(w[5]))
+    else:
+        g = w.reshape(-1, 3)
+    rows = np.flatnonzero((g[:, 0] >= x0) & (g[:, 0] < x0 + nx))
+    nodes = g[rows] - np.array([x0, 0, 0], dtype=np.int64)
+    vals = None
+    if values is not None:
+        v = np.asarray(values, dtype=np.float64)
+        v = np.broadcast_to(v.reshape(-1, nc) if v.size != nc else v.reshape(1, nc), (len(g), nc))
+        vals = np.ascontiguousarray(v[rows])
+    return box, nodes, rows, vals
+
+
 class SlabRunner:
     def __init__(self, nx_local, ny, nz, rank, world, P, periodic=(True, False, False), particle_timescale=5,
                  material_timescale=20, deletion_check_every=1, fluid_only=False, n_slabs=None):
@@ -77,6 +103,27 @@ class SlabRunner:
 
     def define_bounce_back(self, mask_global):
         self.lattice.defineBounceBack(mask_global)
+
+    # ---- Zou-He open boundaries in GLOBAL node coordinates: every rank makes the same call and keeps what lies on its slab
+    # (open_boundary_rows); the slots are the slab's own
+    def add_open_boundary(self, kind, axis, orientation, box_global):
+        """kind 0 = velocity, 1 = pressure; axis 0, 1, 2; orientation -1 = N, +1 = P; box_global inclusive.  Returns
+        (first_slot, n) on this slab, its nodes in box order; n == 0 where the box misses the slab."""
+        _, nodes, _, _ = open_boundary_rows(box_global, self.x0, self.nx)
+        first = self.lattice.addOpenBoundaryNodes(kind, orientation, nodes, axis=axis)
+        return first, len(nodes)
+
+    def set_open_velocity(self, where_global, u):
+        """setBoundaryVelocity on a global box or [n][3] node list: one velocity or one per node in that global order"""
+        _, nodes, _, vals = open_boundary_rows(where_global, self.x0, self.nx, 3, u)
+        if len(nodes):
+            self.lattice.setBoundaryVelocity(nodes, vals)
+
+    def set_open_density(self, where_global, rho):
+        """setBoundaryDensity likewise: one density or one per node"""
+        _, nodes, _, vals = open_boundary_rows(where_global, self.x0, self.nx, 1, rho)
+        if len(nodes):
+            self.lattice.setBoundaryDensity(nodes, vals)
 
     def add_cell_type(self, celltype):
         return self.cells.addCellType(celltype, self.k_m)

@@ -171,8 +171,13 @@ int hcl_lees_edwards_state(const hc_lattice *L, double out[4]);
  * the velocity statistic of hcl_fluid_stats (what 0), the IBM interpolation) takes its moments of the COMPLETED populations
  * of a fluid open-boundary node: a velocity node reports u_bc + F / 2, a pressure node its prescribed density.  The force
  * and mass statistics (what 1, 2) are untouched: mass is the sum of the STORED populations, which is what is conserved.  Lattices without open boundaries run the
- * collide and the observers exactly as before.  Needs n_slabs = 1 and a lattice without a Lees-Edwards boundary (and
- * hcl_set_lees_edwards refuses a lattice with open-boundary nodes): the two do not combine. */
+ * collide and the observers exactly as before.  Needs a lattice without a Lees-Edwards boundary (and
+ * hcl_set_lees_edwards refuses a lattice with open-boundary nodes): the two do not combine.
+ * On a slab of a multi-rank run (n_slabs > 1, ranks connected -- an unconnected lattice takes open boundaries with n_slabs = 1
+ * only) every rank declares the nodes of its own slab, in LOCAL coordinates and with slots of its own; a node outside the slab
+ * is "node outside the lattice".  Nodes of any axis may lie on a slab's face planes, x-normal ones also on a plane that has a
+ * neighbour.  The slab schedule and the observers then give the single domain's bits, and the face-velocity message
+ * (hcl_face_velocity_pack) carries completed moments for the open nodes of a face plane. */
 #define HC_OB_VELOCITY 0
 #define HC_OB_PRESSURE 1
 int hcl_open_boundary_add(hc_lattice *L, int kind, int orientation, const int *nodes, int n, int *first_slot);
@@ -183,7 +188,7 @@ int hcl_open_boundary_add_box(hc_lattice *L, int kind, int orientation, const in
  * c_axis = -1.  The completion on axis a is the x completion with the roles of x and a exchanged: the normal velocity is
  * u[a], a pressure node takes the prescribed rho, the normal velocity from the known populations and tangential velocity 0.
  * The values of a slot stay {u_x, u_y, u_z, rho} in lattice axes whatever the axis.  Every rule above holds unchanged (one
- * slot per node, on whatever axis it was declared; n_slabs = 1; no Lees-Edwards; bounce-back nodes stay bounce-back), and
+ * slot per node, on whatever axis it was declared; local coordinates on a slab; no Lees-Edwards; bounce-back nodes stay bounce-back), and
  * so do the observers.  Nodes where two open faces meet get no dynamics of their own: they are the caller's to make walls.
  * hcl_open_boundary_add and _add_box are these with axis 0.  A lattice holds fewer than 2^27 open-boundary nodes. */
 int hcl_open_boundary_add_axis(hc_lattice *L, int kind, int axis, int orientation, const int *nodes, int n, int *first_slot);
@@ -214,8 +219,10 @@ int hcl_plane_velocity_axis(hc_lattice *L, int axis, int plane, const int *idx, 
 /* The pre-inlet's fluid coupling kept on the device (helper/preInlet.cpp, applyPreInletVelocityBoundary): the plane velocities
  * of the lattice `pre` on its plane coordinate[axis] == pre_plane at the in-plane indices pre_idx[0 .. n-1] (as for
  * hcl_plane_velocity_axis) become the velocities of the domain's open-boundary slots domain_first_slot .. + n - 1, node k
- * to slot domain_first_slot + k.  create uploads the index list once and checks: n_slabs = 1 on both lattices, plane and
- * indices in range, the slots exist on the domain and every one of them is a velocity slot (else HC_ERR_ARG).  The handle
+ * to slot domain_first_slot + k.  create uploads the index list once and checks: n_slabs = 1 on the pre-inlet lattice, and on
+ * the domain too unless axis == 0 (a slab domain: the inlet plane of an x direction lies on one rank, the slots are that
+ * rank's local slots and the handle lives in that rank's process beside its own pre-inlet lattice; a y or z plane would span
+ * the ranks), plane and indices in range, the slots exist on the domain and every one of them is a velocity slot (else HC_ERR_ARG).  The handle
  * holds plain pointers to both lattices and owns neither: destroy it BEFORE either lattice.
  * apply: one kernel on the library's stream, no staging, no copy and no host wait; it writes u_x, u_y, u_z of the slots and
  * leaves rho alone.  It reads the domain's slot storage and the pre-inlet's state at the time of the call, so slots
@@ -223,7 +230,9 @@ int hcl_plane_velocity_axis(hc_lattice *L, int axis, int plane, const int *idx, 
  * domain the coupled slots are gone: apply and iterate then return HC_ERR_STATE and launch nothing, also when nodes were
  * declared again since -- make a new handle.
  * iterate: n times (hcl_collide_stream(pre, 1), hcl_collide_stream(domain, 1), apply), the reference's per-iteration order,
- * all queued on the library's stream without a host wait: the domain lags the pre-inlet by one iteration. */
+ * all queued on the library's stream without a host wait: the domain lags the pre-inlet by one iteration.  With a slab
+ * domain the domain's step is COLLECTIVE: the other ranks call hcl_collide_stream(domain, ...) or hc_iterate for the same
+ * number of steps, or the face exchange inside waits for them until the transport's timeout. */
 typedef struct hc_preinlet hc_preinlet;
 int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, int axis, int pre_plane,
                         const int *pre_idx, int n, int domain_first_slot);
@@ -278,7 +287,9 @@ int hcl_halo_unpack_both(hc_lattice *L, const double *dev_lo, const double *dev_
 /* the message of a velocity update between slabs: node velocities u = j/rho + F/2 (Cell::computeVelocity for
  * ExternalForceDynamics, what core/hemoCellParticleField.cpp:833 blends) of this slab's face plane `side`, evaluated by
  * their owner on the post-stream state and packed as [3][ny*nz] doubles (device pointer) for the neighbour whose first halo
- * plane it is -- 3 planes instead of the 19 population planes of a width-2 halo.  hc_iterate exchanges them itself. */
+ * plane it is -- 3 planes instead of the 19 population planes of a width-2 halo.  hc_iterate exchanges them itself.
+ * On a lattice with open-boundary nodes a fluid open node of the plane sends the moments of its completed populations (a
+ * velocity node u_bc + F / 2), as every observer reports them; bounce-back nodes send 0. */
 int hcl_face_velocity_pack(hc_lattice *L, int side, double *dev_buf);
 int hcl_face_velocity_pack_both(hc_lattice *L, double *dev_lo, double *dev_hi);   /* both face planes in one launch; a null buffer = no neighbour there */
 int hcl_download_face_velocity(hc_lattice *L, int side, double *host_u /*[3][ny*nz]*/);   /* the same plane on the host, for inspection */
