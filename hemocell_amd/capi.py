@@ -179,6 +179,7 @@ SIGNATURES = {
     "hcp_remove_cells": (C.c_int, [VP, C.c_int, c_int_p, C.c_int]),
     "hcp_owned_vertices": (C.c_int, [VP, c_long_p]),
     "hcp_preinlet_create": (C.c_int, [C.POINTER(VP), VP, VP, C.c_int, C.c_int, C.c_double, C.c_double, c_double_p, C.c_long]),
+    "hcp_preinlet_create_slab": (C.c_int, [C.POINTER(VP), VP, VP, C.c_int, C.c_int, C.c_double, C.c_double, c_double_p, C.c_long]),
     "hcp_preinlet_set_sink": (C.c_int, [VP, C.c_int, C.c_double]),
     "hcp_preinlet_apply": (C.c_int, [VP, c_long_p, c_long_p]),
     "hcp_preinlet_counts": (C.c_int, [VP, c_long_p]),

@@ -7,7 +7,12 @@
 //
 // The reference copies single particles; this back end stores cells whole and unwrapped, so a cell is added only when its
 // id is absent and its whole vertex set lies in the window.
+//
+// A domain that is cut into x-slabs takes the same check as a collective (hcp_preinlet_create_slab): the pre-inlet lives whole
+// on the rank that holds the inlet plane, the ranks agree over the control plane (hcm::allgatherv) on the cells the sink takes
+// and on the candidates whose id some rank holds, and then every rank changes its own container.
 #include "cells.h"
+#include "comm.h"
 #include <memory>
 #include <set>
 #include <unordered_set>
@@ -20,10 +25,15 @@ constexpr int SEL = 8;   // doubles per cell slot of the select block: flag, lap
 // One workgroup per cell slot of one type: extents of the live vertices on the three axes, the lap of the cell along `axis`
 // (positions are unwrapped: a cell that went k times round the periodic pre-inlet sits at x + k Lp) and whether it lies
 // wholly in the window.  fmin / fmax are exact, so the result does not depend on the order of the reduction.
+// SLAB (the sink's select over one x-slab's container): flag and lap give way to the number of live vertices whose nearest node
+// lies in the slab [x0, x0 + nx) -- 0 for a pure envelope copy, as in cell_extent_kernel -- and the cell's deletion state.
+template <bool SLAB>
 __global__ __launch_bounds__(256) void preinlet_select_kernel(int nv, const double *px, const double *py, const double *pz, const int *tag,
                                                               const unsigned char *dead, int axis, double Lp, double window_lo, double window_hi,
-                                                              double *out) {
+                                                              int x0, int nx, double *out) {
   __shared__ double red[4][6];
+  __shared__ int red_own[4];
+  int own = 0;
   const int tid = threadIdx.x;
   const long base = (long)blockIdx.x * nv;
   const int state = tag[blockIdx.x];
@@ -35,13 +45,19 @@ __global__ __launch_bounds__(256) void preinlet_select_kernel(int nv, const doub
       lo[0] = fmin(lo[0], x); hi[0] = fmax(hi[0], x);
       lo[1] = fmin(lo[1], y); hi[1] = fmax(hi[1], y);
       lo[2] = fmin(lo[2], z); hi[2] = fmax(hi[2], z);
+      if (SLAB) { const long gx = nearest_node(x) - x0; own += (gx >= 0 && gx < nx) ? 1 : 0; }
     }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
 #pragma unroll
     for (int d = 0; d < 3; d++) { lo[d] = fmin(lo[d], __shfl_xor(lo[d], off)); hi[d] = fmax(hi[d], __shfl_xor(hi[d], off)); }
+  if (SLAB) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) own += __shfl_xor(own, off);
+  }
   if ((tid & 63) == 0) {
     const int w = tid >> 6;
+    if (SLAB) red_own[w] = own;
 #pragma unroll
     for (int d = 0; d < 3; d++) { red[w][2 * d] = lo[d]; red[w][2 * d + 1] = hi[d]; }
   }
@@ -60,7 +76,8 @@ __global__ __launch_bounds__(256) void preinlet_select_kernel(int nv, const doub
       flag = (cmin - (double)lap * Lp >= window_lo && cmax - (double)lap * Lp <= window_hi) ? 1 : 0;
     }
     double *r = out + SEL * (long)blockIdx.x;
-    r[0] = (double)flag; r[1] = (double)lap;
+    if (SLAB) { r[0] = (double)(red_own[0] + red_own[1] + red_own[2] + red_own[3]); r[1] = (double)state; }
+    else { r[0] = (double)flag; r[1] = (double)lap; }
     r[2] = lo[0]; r[3] = hi[0]; r[4] = lo[1]; r[5] = hi[1]; r[6] = lo[2]; r[7] = hi[2];
   }
 }
@@ -99,9 +116,11 @@ struct hc_preinlet_cells {
   std::set<std::pair<int, long>> offered;   // (type, id') already offered to the domain
   SelectBlock sel[2];
   Event done;
+  bool slab = false;          // hcp_preinlet_create_slab: dom is one x-slab, pre is null off the rank that holds the inlet plane
 };
 
 static int axis_nodes(const hc_lattice *L, int axis) { return axis == 0 ? L->nx : axis == 1 ? L->ny : L->nz; }
+static int global_nodes(const hc_lattice *L, int axis) { return axis == 0 ? L->nx_global : axis_nodes(L, axis); }
 
 // room for `total` cell slots in a select block; the old block is given up only once the last check has left it
 static int reserve_select(hc_preinlet_cells *X, SelectBlock &b, long total) {
@@ -111,7 +130,8 @@ static int reserve_select(hc_preinlet_cells *X, SelectBlock &b, long total) {
 }
 
 // the select kernel over every type of a container; block row of (type t, slot c) = first[t] + c
-static int launch_select(hc_preinlet_cells *X, int which, hc_cells *C, double Lp, double lo, double hi, std::vector<long> &first) {
+// (slab: the instantiation that counts the vertices this slab owns)
+static int launch_select(hc_preinlet_cells *X, int which, hc_cells *C, double Lp, double lo, double hi, std::vector<long> &first, bool slab = false) {
   first.assign((size_t)C->ntypes + 1, 0);
   for (int t = 0; t < C->ntypes; t++) first[(size_t)t + 1] = first[(size_t)t] + C->ncells[t];
   const long total = first[(size_t)C->ntypes];
@@ -121,10 +141,245 @@ static int launch_select(hc_preinlet_cells *X, int which, hc_cells *C, double Lp
     const long nc = C->ncells[t];
     if (nc == 0) continue;
     const TypeArrays a = vert_arrays(C, t);
-    hipLaunchKernelGGL(preinlet_select_kernel, dim3((unsigned)nc), dim3(256), 0, hc::stream(), C->types[t]->host.nv, a.p[0], a.p[1], a.p[2], a.tag, a.dead,
-                       X->axis, Lp, lo, hi, b.dev + SEL * first[(size_t)t]);
+    hipLaunchKernelGGL(slab ? preinlet_select_kernel<true> : preinlet_select_kernel<false>, dim3((unsigned)nc), dim3(256), 0, hc::stream(), C->types[t]->host.nv,
+                       a.p[0], a.p[1], a.p[2], a.tag, a.dead, X->axis, Lp, lo, hi, C->L->x0, C->L->nx, b.dev + SEL * first[(size_t)t]);
     HC_HIP(hipGetLastError());
   }
+  return HC_OK;
+}
+
+// what create and create_slab ask of the two containers and the window
+static int check_pair(const std::string &fn, const hc_cells *pre, const hc_cells *domain, int axis, double window_lo, double window_hi, long id_stride) {
+  HC_REQUIRE(pre->L->periodic[axis], fn + ": the pre-inlet must be periodic on the inlet axis");
+  HC_REQUIRE(pre->ntypes == domain->ntypes, fn + ": the containers hold different numbers of cell types");
+  for (int t = 0; t < pre->ntypes; t++) {
+    const CellTables &a = pre->types[t]->host, &b = domain->types[t]->host;
+    HC_REQUIRE(a.model == b.model && a.nv == b.nv, fn + ": the cell types differ in model or vertices");
+  }
+  HC_REQUIRE(pre->rep_on() == domain->rep_on(), fn + ": repulsion is enabled on one container only");
+  HC_REQUIRE(window_lo >= 0.0 && window_hi <= (double)axis_nodes(pre->L, axis) && window_hi > window_lo, fn + ": the window must satisfy 0 <= lo < hi <= Lp");
+  HC_REQUIRE(id_stride > 0, fn + ": id_stride must be positive");
+  return HC_OK;
+}
+
+// the blocks of the cells held now, so that a check allocates only when the cell set has outgrown them
+static int reserve_blocks(hc_preinlet_cells *X) {
+  hc_cells *both[2] = {X->pre, X->dom};
+  for (int w = 0; w < 2; w++) {
+    if (!both[w]) continue;
+    long total = 0;
+    for (int t = 0; t < both[w]->ntypes; t++) total += (long)both[w]->hids[t].size();
+    int rc = reserve_select(X, X->sel[w], total); if (rc != HC_OK) return rc;
+  }
+  return HC_OK;
+}
+
+struct Cand { int slot; long lap; double ext[6]; };
+
+// the candidates of the pre-inlet's select leave the mapped block before anything can grow it or move cells
+static void take_candidates(const hc_preinlet_cells *X, const std::vector<long> &pfirst, std::vector<Cand> cand[8]) {
+  const hc_cells *P = X->pre;
+  for (int t = 0; t < P->ntypes; t++)
+    for (long c = 0; c < P->ncells[t]; c++) {
+      const double *r = X->sel[0] + SEL * (pfirst[(size_t)t] + c);
+      if (r[0] == 0.0) continue;
+      Cand k; k.slot = (int)c; k.lap = (long)r[1];
+      for (int e = 0; e < 6; e++) k.ext[e] = r[2 + e];
+      cand[t].push_back(k);
+    }
+}
+
+// do the shifted extents of a candidate lie in the box [0, n - 1] of the whole domain on every axis?
+static bool arrives_inside(const hc_preinlet_cells *X, const Cand &k) {
+  for (int a = 0; a < 3; a++) {
+    const double s = a == X->axis ? X->shift[a] - (double)k.lap * X->Lp : X->shift[a];
+    if (k.ext[2 * a] + s < 0.0 || k.ext[2 * a + 1] + s > (double)((X->slab ? global_nodes(X->dom->L, a) : axis_nodes(X->dom->L, a)) - 1)) return false;
+  }
+  return true;
+}
+
+// n cells of type t of the pre-inlet (slots src, laps lap) join the end of the domain's region with the ids given and are
+// copied slot to slot
+static int copy_in(hc_preinlet_cells *X, int t, const std::vector<int> &src, const std::vector<int> &lap, const std::vector<long> &ids) {
+  hc_cells *P = X->pre, *D = X->dom;
+  const int n = (int)ids.size();
+  if (n == 0) return HC_OK;
+  int rc;
+  const long slot0 = D->ncells[t];
+  if ((rc = append_cells(D, t, ids.data(), nullptr, n, n)) != HC_OK) return rc;   // may move the domain's arrays: taken below
+  std::vector<int> lists((size_t)(3 * n));
+  for (int i = 0; i < n; i++) { lists[(size_t)i] = src[(size_t)i]; lists[(size_t)(n + i)] = (int)(slot0 + i); lists[(size_t)(2 * n + i)] = lap[(size_t)i]; }
+  int *d_lists = nullptr;
+  if ((rc = stage_ints(D, 0, &d_lists, lists.data(), 3 * n)) != HC_OK) return rc;
+  hipLaunchKernelGGL(preinlet_copy_kernel, dim3((unsigned)n), dim3(256), 0, hc::stream(), P->types[t]->host.nv, n, (const int *)d_lists, vert_arrays(P, t),
+                     vert_arrays(D, t), X->axis, X->Lp, X->shift[0], X->shift[1], X->shift[2]);
+  HC_HIP(hipGetLastError());
+  return HC_OK;
+}
+
+// ---------------------------------------------------------------------------- the check on x-slabs
+// One control-plane round of a collective call.  Every rank contributes its return code so far, its error text when that code
+// is not HC_OK, and a payload of longs, so a rank that failed locally still completes the round.  When any rank failed, every
+// rank returns the first failing rank's code (the others with that rank's message): nobody is left waiting in a collective.
+static int agree(const char *fn, int rc, const std::vector<long> &mine, std::vector<std::vector<long>> &all) {
+  const std::string why = rc != HC_OK ? std::string(hc_last_error()) : std::string();
+  std::vector<long> block{(long)rc, (long)mine.size(), (long)why.size()};
+  block.insert(block.end(), mine.begin(), mine.end());
+  block.resize(block.size() + (why.size() + sizeof(long) - 1) / sizeof(long), 0L);
+  if (!why.empty()) std::memcpy(block.data() + 3 + mine.size(), why.data(), why.size());
+  std::vector<std::vector<char>> raw;
+  { const int e = hcm::allgatherv(block.data(), block.size() * sizeof(long), raw); if (e != HC_OK) return e; }
+  all.assign(raw.size(), std::vector<long>());
+  int bad = -1, bad_rc = HC_OK; std::string bad_why;
+  for (size_t r = 0; r < raw.size(); r++) {
+    const size_t n = raw[r].size() / sizeof(long);
+    std::vector<long> b(n);
+    if (n) std::memcpy(b.data(), raw[r].data(), n * sizeof(long));
+    if (n < 3 || b[1] < 0 || b[2] < 0 || 3 + (size_t)b[1] + ((size_t)b[2] + sizeof(long) - 1) / sizeof(long) != n) { hc::set_error(std::string(fn) + ": corrupt block from rank " + std::to_string(r)); return HC_ERR_STATE; }
+    if (b[0] != HC_OK && bad < 0) { bad = (int)r; bad_rc = (int)b[0]; bad_why.assign(reinterpret_cast<const char *>(b.data() + 3 + b[1]), (size_t)b[2]); }
+    all[r].assign(b.begin() + 3, b.begin() + 3 + b[1]);
+  }
+  if (bad < 0) return HC_OK;
+  if (bad != hcm::rank()) hc::set_error(std::string(fn) + ": rank " + std::to_string(bad) + " failed: " + bad_why);
+  else hc::set_error(bad_why);
+  return bad_rc;
+}
+
+static long bits_of(double v) { long b; std::memcpy(&b, &v, sizeof(b)); return b; }
+
+using IdSet = std::set<std::pair<int, long>>;   // (type, cell id)
+
+// hcp_preinlet_apply on a slab handle.  Nothing of the domain changes before the last round is over, so an error on any rank
+// leaves every container as it was.
+static int apply_slab(hc_preinlet_cells *X, long *n_injected, long *n_removed) {
+  static const char *fn = "hcp_preinlet_apply";
+  hc_cells *P = X->pre, *D = X->dom;
+  const int ntypes = D->ntypes;
+  std::vector<long> pfirst, dfirst;
+  std::vector<Cand> cand[8];
+  std::vector<std::pair<int, int>> offer;   // (type, index into cand[type]) of the candidates announced, in ascending (type, slot) order
+  std::vector<std::vector<char>> past((size_t)ntypes);   // per held cell: it reaches past the sink plane
+  bool selected = false;
+  IdSet offers;   // what this check offers for the first time; remembered once the check is through
+
+  // round 1: [sink on, plane, rejected, n sink pairs, n candidate pairs | (type, id) of the cells this rank owns part of and sees
+  // past the plane | (type, id') of the candidates]
+  std::vector<long> mine{(long)X->sink_on, bits_of(X->sink_plane), 0, 0, 0};
+  auto first_part = [&]() -> int {
+    int rc;
+    if ((P && (rc = settle(P)) != HC_OK) || (rc = settle(D)) != HC_OK) return rc;
+    if ((P && (rc = sync_to_device(P)) != HC_OK) || (rc = sync_to_device(D)) != HC_OK) return rc;
+    HC_REQUIRE(!P || P->ntypes == ntypes, std::string(fn) + ": the containers no longer hold the same cell types");
+    if (P && (rc = launch_select(X, 0, P, X->Lp, X->lo, X->hi, pfirst)) != HC_OK) return rc;
+    selected = X->sink_on && D->nverts > 0;
+    if (selected && (rc = launch_select(X, 1, D, (double)D->L->nx_global, 0.0, 0.0, dfirst, true)) != HC_OK) return rc;
+    HC_HIP(hipEventRecord(X->done, hc::stream()));
+    HC_HIP(hipEventSynchronize(X->done));   // the one wait of a check
+    std::vector<long> sunk, offered;
+    if (selected)
+      for (int t = 0; t < ntypes; t++) {
+        past[(size_t)t].assign((size_t)D->ncells[t], 0);
+        for (long c = 0; c < D->ncells[t]; c++) {
+          const double *r = X->sel[1] + SEL * (dfirst[(size_t)t] + c);
+          const double cmin = r[2], cmax = r[3];
+          if (cmin > cmax) continue;   // no live vertex
+          if (!(X->orient < 0 ? cmax > X->sink_plane : cmin < X->sink_plane)) continue;
+          past[(size_t)t][(size_t)c] = 1;
+          if (r[0] > 0.0) { sunk.push_back(t); sunk.push_back(D->hids[t][(size_t)c]); }   // a pure copy is its owners' business
+        }
+      }
+    if (P) {
+      take_candidates(X, pfirst, cand);
+      for (int t = 0; t < ntypes; t++)
+        for (size_t i = 0; i < cand[t].size(); i++) {
+          const Cand &k = cand[t][i];
+          HC_REQUIRE(k.lap > -(1L << 30) && k.lap < (1L << 30), std::string(fn) + ": lap out of range");
+          const long id = P->hids[t][(size_t)k.slot] + (k.lap - X->orient) * X->stride;
+          if (X->offered.count(std::make_pair(t, id)) || !offers.insert(std::make_pair(t, id)).second) continue;
+          if (!arrives_inside(X, k)) { mine[2]++; continue; }
+          offer.push_back(std::make_pair(t, (int)i)); offered.push_back(t); offered.push_back(id);
+        }
+    }
+    mine[3] = (long)(sunk.size() / 2); mine[4] = (long)(offered.size() / 2);
+    mine.insert(mine.end(), sunk.begin(), sunk.end());
+    mine.insert(mine.end(), offered.begin(), offered.end());
+    return HC_OK;
+  };
+  std::vector<std::vector<long>> all;
+  int rc = agree(fn, first_part(), mine, all);
+  if (rc != HC_OK) return rc;
+
+  // what every rank reads out of round 1, in rank order
+  IdSet sunk;
+  std::vector<std::pair<int, long>> announced;
+  long rejected = 0;
+  for (const std::vector<long> &b : all) {
+    if (b.size() < 5 || b[3] < 0 || b[4] < 0 || (size_t)(5 + 2 * b[3] + 2 * b[4]) != b.size() || b[0] != all[0][0] || b[1] != all[0][1]) {
+      hc::set_error(std::string(fn) + ": the ranks disagree about the sink (hcp_preinlet_set_sink is called with the same arguments on every rank)");
+      return HC_ERR_STATE;   // read from the same blocks on every rank: they all return here
+    }
+    rejected += b[2];
+    for (long i = 0; i < b[3]; i++) sunk.insert(std::make_pair((int)b[5 + 2 * i], b[6 + 2 * i]));
+    for (long i = 0; i < b[4]; i++) announced.push_back(std::make_pair((int)b[5 + 2 * b[3] + 2 * i], b[6 + 2 * b[3] + 2 * i]));
+  }
+  // the handle's books change only once every rank is through the last round: a check that failed has offered nothing
+  auto through = [&]() { X->checks++; X->rejected += rejected; X->offered.insert(offers.begin(), offers.end()); };
+  if (!all[0][0] && announced.empty()) { through(); return HC_OK; }   // no sink and nothing offered: one round
+
+  // round 2: [(type, id') of the candidates this rank will still hold once the sink has run].  A holder checks the sink's list
+  // against its own select first: a cell some rank takes out and another keeps would be an orphan.
+  std::vector<long> held;
+  auto second_part = [&]() -> int {
+    for (int t = 0; t < ntypes && selected; t++)
+      for (long c = 0; c < D->ncells[t]; c++) {
+        const long id = D->hids[t][(size_t)c];
+        if ((past[(size_t)t][(size_t)c] != 0) != (sunk.count(std::make_pair(t, id)) != 0)) {
+          hc::set_error(std::string(fn) + ": this rank's copy of cell " + std::to_string(id) + " of type " + std::to_string(t) +
+                        " and its owners disagree on whether it lies past the sink plane");
+          return HC_ERR_STATE;
+        }
+      }
+    for (const std::pair<int, long> &a : announced) {
+      if (a.first < 0 || a.first >= ntypes || sunk.count(a)) continue;
+      const std::vector<long> &ids = D->hids[a.first];
+      if (std::find(ids.begin(), ids.end(), a.second) != ids.end()) { held.push_back(a.first); held.push_back(a.second); }
+    }
+    return HC_OK;
+  };
+  rc = agree(fn, second_part(), held, all);
+  if (rc != HC_OK) return rc;
+  through();
+  IdSet taken;
+  for (const std::vector<long> &b : all) for (size_t i = 0; i + 1 < b.size(); i += 2) taken.insert(std::make_pair((int)b[i], b[i + 1]));
+
+  // the sink: every holder, owners and pure copies alike
+  for (int t = 0; t < ntypes && !sunk.empty(); t++) {
+    std::vector<int> gone;
+    for (long c = 0; c < D->ncells[t]; c++) if (sunk.count(std::make_pair(t, D->hids[t][(size_t)c]))) gone.push_back((int)c);
+    if (gone.empty()) continue;
+    if ((rc = hcp_remove_cells(D, t, gone.data(), (int)gone.size())) != HC_OK) return rc;
+    D->ext_pending[t] = false;   // extents on their way to the next envelope synchronisation describe the old slots
+  }
+  X->removed += (long)sunk.size();
+  if (n_removed) *n_removed = (long)sunk.size();
+
+  // the injection: a candidate arrives when no rank holds its id and no earlier candidate of this check took it
+  long injected = 0;
+  std::vector<int> src[8], lap[8]; std::vector<long> ids[8];
+  for (size_t i = 0; i < announced.size(); i++) {
+    if (!taken.insert(announced[i]).second) continue;
+    injected++;
+    if (!P) continue;
+    const int t = offer[i].first; const Cand &k = cand[t][(size_t)offer[i].second];
+    src[t].push_back(k.slot); lap[t].push_back((int)k.lap); ids[t].push_back(announced[i].second);
+  }
+  for (int t = 0; t < ntypes && P; t++) {
+    if (ids[t].empty()) continue;
+    if ((rc = copy_in(X, t, src[t], lap[t], ids[t])) != HC_OK) return rc;
+    D->ext_pending[t] = false;
+  }
+  X->injected += injected;
+  if (n_injected) *n_injected = injected;
   return HC_OK;
 }
 
@@ -151,12 +406,49 @@ int hcp_preinlet_create(hc_preinlet_cells **out, hc_cells *pre, hc_cells *domain
   X->pre = pre; X->dom = domain; X->axis = axis; X->orient = orientation; X->lo = window_lo; X->hi = window_hi; X->Lp = Lp; X->stride = id_stride;
   for (int d = 0; d < 3; d++) X->shift[d] = shift[d];
   { const int rc = X->done.create(); if (rc != HC_OK) return rc; }
-  hc_cells *both[2] = {pre, domain};
-  for (int w = 0; w < 2; w++) {   // the blocks of the cells held now, so that a check allocates only when the cell set has outgrown them
-    long total = 0;
-    for (int t = 0; t < both[w]->ntypes; t++) total += (long)both[w]->hids[t].size();
-    int rc = reserve_select(X.get(), X->sel[w], total); if (rc != HC_OK) return rc;
-  }
+  { const int rc = reserve_blocks(X.get()); if (rc != HC_OK) return rc; }
+  *out = X.release();
+  return HC_OK;
+}
+
+int hcp_preinlet_create_slab(hc_preinlet_cells **out, hc_cells *pre, hc_cells *domain, int axis, int orientation, double window_lo, double window_hi,
+                             const double shift[3], long id_stride) {
+  static const std::string fn = "hcp_preinlet_create_slab";
+  HC_REQUIRE(out && domain && shift, fn + ": bad arguments");
+  const hc_lattice *L = domain->L;
+  HC_REQUIRE(L->n_slabs > 1 && hcm::active() && hcm::world() == L->n_slabs,
+             fn + ": the domain must be one x-slab of a connected world, one rank per slab (hcp_preinlet_create couples a whole domain)");
+  if (hc::stream() == nullptr) { hc::set_error(fn + ": hc_init() has not been called"); return HC_ERR_STATE; }
+  // from here on the call is collective: a rank that refuses its arguments says so in the round, and every rank returns
+  auto local = [&]() -> int {
+    HC_REQUIRE(axis == 0, fn + ": only axis 0 feeds a slab (Xneg on rank 0, Xpos on the last rank)");
+    HC_REQUIRE(orientation == -1 || orientation == 1, fn + ": orientation must be -1 (Xneg) or +1 (Xpos)");
+    HC_REQUIRE(!L->periodic[0], fn + ": a slab domain that is periodic along x has no inlet plane");
+    const bool inlet = orientation < 0 ? L->x0 == 0 : L->x0 + L->nx == L->nx_global;
+    HC_REQUIRE(inlet || !pre, fn + ": pre must be null on a rank that does not hold the inlet plane");
+    HC_REQUIRE(!inlet || pre, fn + ": the rank that holds the inlet plane needs the pre-inlet's container");
+    HC_REQUIRE(id_stride > 0, fn + ": id_stride must be positive");
+    if (!pre) return HC_OK;
+    HC_REQUIRE(pre != domain && pre->L->n_slabs == 1, fn + ": the pre-inlet needs n_slabs = 1 (it lives whole on the inlet rank)");
+    { const int rc = check_pair(fn, pre, domain, axis, window_lo, window_hi, id_stride); if (rc != HC_OK) return rc; }
+    // an arriving cell is held by this rank alone until the ordinary envelope synchronisation replicates it
+    const double a = window_lo + shift[0], b = window_hi + shift[0], x0 = (double)L->x0, x1 = (double)(L->x0 + L->nx), e = domain->e_share;
+    HC_REQUIRE(orientation < 0 ? (a >= x0 && b <= x1 - e) : (a >= x0 + e && b <= x1),
+               fn + ": the window's image [" + std::to_string(a) + ", " + std::to_string(b) + "] must lie in the inlet rank's slab [" + std::to_string(x0) + ", " +
+                   std::to_string(x1) + "] at least the particle envelope (" + std::to_string(e) + " lu) away from its inner face");
+    return HC_OK;
+  };
+  std::vector<long> mine{(long)axis, (long)orientation, bits_of(window_lo), bits_of(window_hi), bits_of(shift[0]), bits_of(shift[1]), bits_of(shift[2]), id_stride,
+                         (long)domain->ntypes};
+  std::vector<std::vector<long>> all;
+  { const int rc = agree(fn.c_str(), local(), mine, all); if (rc != HC_OK) return rc; }
+  for (const std::vector<long> &b : all) HC_REQUIRE(b == all[0], fn + ": the ranks passed different arguments");
+  std::unique_ptr<hc_preinlet_cells> X(new hc_preinlet_cells());
+  X->pre = pre; X->dom = domain; X->axis = axis; X->orient = orientation; X->lo = window_lo; X->hi = window_hi; X->stride = id_stride; X->slab = true;
+  X->Lp = pre ? (double)axis_nodes(pre->L, axis) : 0.0;
+  for (int d = 0; d < 3; d++) X->shift[d] = shift[d];
+  { const int rc = X->done.create(); if (rc != HC_OK) return rc; }
+  { const int rc = reserve_blocks(X.get()); if (rc != HC_OK) return rc; }
   *out = X.release();
   return HC_OK;
 }
@@ -185,6 +477,7 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
   hc_cells *P = X->pre, *D = X->dom;
   if (n_injected) *n_injected = 0;
   if (n_removed) *n_removed = 0;
+  if (X->slab) return apply_slab(X, n_injected, n_removed);
   int rc;
   if ((rc = settle(P)) != HC_OK || (rc = settle(D)) != HC_OK) return rc;
   if ((rc = sync_to_device(P)) != HC_OK || (rc = sync_to_device(D)) != HC_OK) return rc;
@@ -198,17 +491,8 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
   HC_HIP(hipEventSynchronize(X->done));   // the one wait of a check: for the select kernels, not for the device
   X->checks++;
 
-  // the candidates leave the mapped block before anything below can grow it or move cells
-  struct Cand { int slot; long lap; double ext[6]; };
   std::vector<Cand> cand[8];
-  for (int t = 0; t < ntypes; t++)
-    for (long c = 0; c < P->ncells[t]; c++) {
-      const double *r = X->sel[0] + SEL * (pfirst[(size_t)t] + c);
-      if (r[0] == 0.0) continue;
-      Cand k; k.slot = (int)c; k.lap = (long)r[1];
-      for (int e = 0; e < 6; e++) k.ext[e] = r[2 + e];
-      cand[t].push_back(k);
-    }
+  take_candidates(X, pfirst, cand);
 
   // the sink: cells of the domain that reach past the plane, downstream of it
   if (sink) {
@@ -233,34 +517,18 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
   long injected = 0;
   for (int t = 0; t < ntypes; t++) {
     if (cand[t].empty()) continue;
-    const int nv = P->types[t]->host.nv;
     std::unordered_set<long> held(D->hids[t].begin(), D->hids[t].end());
     std::vector<int> src, lap; std::vector<long> ids;
     for (const Cand &k : cand[t]) {
       HC_REQUIRE(k.lap > -(1L << 30) && k.lap < (1L << 30), "hcp_preinlet_apply: lap out of range");
       const long id = P->hids[t][(size_t)k.slot] + (k.lap - X->orient) * X->stride;   // getOffset: positive for *neg
       if (!X->offered.insert(std::make_pair(t, id)).second) continue;
-      bool inside = true;
-      for (int a = 0; a < 3; a++) {
-        const double s = a == X->axis ? X->shift[a] - (double)k.lap * X->Lp : X->shift[a];
-        if (k.ext[2 * a] + s < 0.0 || k.ext[2 * a + 1] + s > (double)(axis_nodes(D->L, a) - 1)) inside = false;
-      }
-      if (!inside) { X->rejected++; continue; }
+      if (!arrives_inside(X, k)) { X->rejected++; continue; }
       if (!held.insert(id).second) continue;
       src.push_back(k.slot); lap.push_back((int)k.lap); ids.push_back(id);
     }
-    const int n = (int)ids.size();
-    if (n == 0) continue;
-    const long slot0 = D->ncells[t];
-    if ((rc = append_cells(D, t, ids.data(), nullptr, n, n)) != HC_OK) return rc;   // may move the domain's arrays: taken below
-    std::vector<int> lists((size_t)(3 * n));
-    for (int i = 0; i < n; i++) { lists[(size_t)i] = src[(size_t)i]; lists[(size_t)(n + i)] = (int)(slot0 + i); lists[(size_t)(2 * n + i)] = lap[(size_t)i]; }
-    int *d_lists = nullptr;
-    if ((rc = stage_ints(D, 0, &d_lists, lists.data(), 3 * n)) != HC_OK) return rc;
-    hipLaunchKernelGGL(preinlet_copy_kernel, dim3((unsigned)n), dim3(256), 0, hc::stream(), nv, n, (const int *)d_lists, vert_arrays(P, t), vert_arrays(D, t),
-                       X->axis, X->Lp, X->shift[0], X->shift[1], X->shift[2]);
-    HC_HIP(hipGetLastError());
-    injected += n;
+    if ((rc = copy_in(X, t, src, lap, ids)) != HC_OK) return rc;
+    injected += (long)ids.size();
   }
   X->injected += injected;
   if (n_injected) *n_injected = injected;
@@ -269,17 +537,19 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
 
 int hc_preinlet_iterate(hc_preinlet *F, hc_preinlet_cells *X, long *iter, int n, int particle_timescale, int force_limit, int deletion_check_every,
                         int cells_every) {
-  HC_REQUIRE(F && X && iter && n >= 0, "hc_preinlet_iterate: bad arguments");
+  HC_REQUIRE(X && iter && n >= 0, "hc_preinlet_iterate: bad arguments");
+  // a slab handle on a rank without the inlet plane has neither a pre-inlet nor a fluid coupling: that rank steps its slab
+  HC_REQUIRE((F != nullptr) == (X->pre != nullptr), "hc_preinlet_iterate: bad arguments (the fluid handle is null exactly on the ranks of a slab handle that hold no pre-inlet)");
   HC_REQUIRE(cells_every >= 1, "hc_preinlet_iterate: cells_every must be >= 1");
   HC_REQUIRE(particle_timescale >= 1 && deletion_check_every >= 1, "hc_preinlet_iterate: timescales must be >= 1");
   for (int s = 0; s < n; s++) {
     int rc;
     long a = *iter, b = *iter;
-    if ((rc = hc_iterate(X->pre->L, X->pre, &a, 1, particle_timescale, force_limit, deletion_check_every)) != HC_OK) return rc;
+    if (X->pre && (rc = hc_iterate(X->pre->L, X->pre, &a, 1, particle_timescale, force_limit, deletion_check_every)) != HC_OK) return rc;
     if ((rc = hc_iterate(X->dom->L, X->dom, &b, 1, particle_timescale, force_limit, deletion_check_every)) != HC_OK) return rc;
-    if ((rc = hcl_preinlet_apply(F)) != HC_OK) return rc;
-    *iter = a;
-    if (a % cells_every == 0 && (rc = hcp_preinlet_apply(X, nullptr, nullptr)) != HC_OK) return rc;
+    if (F && (rc = hcl_preinlet_apply(F)) != HC_OK) return rc;
+    *iter = b;
+    if (b % cells_every == 0 && (rc = hcp_preinlet_apply(X, nullptr, nullptr)) != HC_OK) return rc;
   }
   return HC_OK;
 }

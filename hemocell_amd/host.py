@@ -449,7 +449,14 @@ class PreInlet:
     that holds the inlet plane -- rank 0 with plane 0 for Xneg, the last rank with plane nx - 1 for Xpos -- beside its own
     whole pre-inlet lattice; domain_x is that rank's local plane and the slots are its local slots.  The domain's step inside
     iterate(n) is then collective: every other rank steps its slab the same number of times (collideAndStream(n) or
-    HemoCell.iterate(n)).  Other directions, a pre-inlet on slabs and cells= with a slab are refused."""
+    HemoCell.iterate(n)).  With cells=(pre_cells, slab_cells) the cells cross into the slabs too (hcp_preinlet_create_slab):
+    constructing the object, iterate(n) and applyPreInletCells() are then collective, and every other rank holds a
+    PreInletPeer made with the same window, shift, id_stride, sink and cadences and makes the same calls.  shift and sink are
+    in GLOBAL domain coordinates; the window's image [lo + shift_x, hi + shift_x] must lie in the inlet rank's slab, at least the
+    particle envelope away from its inner face, so that an arriving cell is held by the inlet rank alone until the envelope
+    synchronisation replicates it.  The sink takes a cell from every rank that holds it in the same check, and cell_counts()
+    are totals over the whole domain, equal on every rank.  With hc_set_reproducible_spread(1) the slabs hold the bits of the
+    same run on one domain.  Other directions, a pre-inlet on slabs and partly arrived cells are refused."""
 
     def __init__(self, preinlet, domain, yz, pre_x, domain_x, direction="Xpos", pre_origin=(0, 0), domain_origin=(0, 0),
                  device=False, cells=None, window=None, shift=(0.0, 0.0, 0.0), id_stride=None, sink=None, cells_every=1,
@@ -497,9 +504,11 @@ class PreInlet:
             self.force_limit, self.deletion_check_every = bool(force_limit), int(deletion_check_every)
             sh = np.array(shift, dtype=np.float64).reshape(3)
             xp = C.c_void_p()
+            # a slab of a multi-rank run: the collective entry point, which the other ranks reach through PreInletPeer
+            create = capi.lib().hcp_preinlet_create if getattr(domain, "n_slabs", 1) == 1 else capi.lib().hcp_preinlet_create_slab
             try:
-                check(capi.lib().hcp_preinlet_create(C.byref(xp), self.cells[0].ptr, self.cells[1].ptr, axis, sign,
-                                                     float(window[0]), float(window[1]), dptr(sh), int(id_stride)))
+                check(create(C.byref(xp), self.cells[0].ptr, self.cells[1].ptr, axis, sign,
+                             float(window[0]), float(window[1]), dptr(sh), int(id_stride)))
                 self.cells_ptr = xp
                 if sink is not None:
                     check(capi.lib().hcp_preinlet_set_sink(xp, 1, float(sink)))
@@ -570,6 +579,49 @@ class PreInlet:
         if self.ptr is not None:
             check(capi.lib().hcl_preinlet_destroy(self.ptr))
             self.ptr = None
+
+
+class PreInletPeer:
+    """What a rank WITHOUT the inlet plane holds while the inlet rank holds PreInlet(..., cells=(pre_cells, slab_cells)) over a
+    domain cut into x-slabs: the same collective handle (hcp_preinlet_create_slab with no pre-inlet), made with the same
+    direction, window, shift, id_stride, sink and cadences, and the same calls -- iterate(n) steps this rank's slab and joins
+    the check every cells_every iterations, applyPreInletCells() is one check, cell_counts() the global totals.  Every rank
+    constructs its object, calls and destroys it in the same order as the inlet rank does."""
+
+    def __init__(self, domain_cells, direction="Xneg", window=None, shift=(0.0, 0.0, 0.0), id_stride=None, sink=None,
+                 cells_every=1, particle_timescale=1, force_limit=True, deletion_check_every=1):
+        axis, sign = _preinlet_direction(direction)
+        if window is None or id_stride is None:
+            raise HcError("PreInletPeer: needs window=(lo, hi) and id_stride=, as the inlet rank's PreInlet")
+        if int(cells_every) < 1:
+            raise HcError("PreInletPeer: cells_every must be >= 1")
+        self.cells, self.cells_ptr, self.iter = (None, domain_cells), None, 0
+        self.cells_every, self.particle_timescale = int(cells_every), int(particle_timescale)
+        self.force_limit, self.deletion_check_every = bool(force_limit), int(deletion_check_every)
+        sh = np.array(shift, dtype=np.float64).reshape(3)
+        xp = C.c_void_p()
+        check(capi.lib().hcp_preinlet_create_slab(C.byref(xp), None, domain_cells.ptr, axis, sign, float(window[0]),
+                                                  float(window[1]), dptr(sh), int(id_stride)))
+        self.cells_ptr = xp
+        if sink is not None:
+            check(capi.lib().hcp_preinlet_set_sink(xp, 1, float(sink)))
+
+    applyPreInletCells = PreInlet.applyPreInletCells
+    cell_counts = PreInlet.cell_counts
+    _cells_handle = PreInlet._cells_handle
+
+    def iterate(self, n=1):
+        it = C.c_long(self.iter)
+        try:
+            check(capi.lib().hc_preinlet_iterate(None, self._cells_handle(), C.byref(it), int(n), self.particle_timescale,
+                                                 int(self.force_limit), self.deletion_check_every, self.cells_every))
+        finally:
+            self.iter = it.value
+
+    def destroy(self):
+        if self.cells_ptr is not None:
+            check(capi.lib().hcp_preinlet_destroy(self.cells_ptr))
+            self.cells_ptr = None
 
 
 class CellType:

@@ -526,10 +526,37 @@ int hcp_owned_vertices(hc_cells *C, long *n_owned); /* vertices whose nearest no
  * kernel, slot to slot.
  * counts: out = {cells injected, rejected, removed by the sink, checks} since create.
  * hc_preinlet_iterate: n times (hc_iterate(pre, 1), hc_iterate(domain, 1), hcl_preinlet_apply(F), and hcp_preinlet_apply(X)
- * when the advanced iter is a multiple of cells_every >= 1), the reference driver's order; both systems share iter. */
+ * when the advanced iter is a multiple of cells_every >= 1), the reference driver's order; both systems share iter.
+ *
+ * A domain cut into x-slabs: hcp_preinlet_create_slab is COLLECTIVE -- every rank of the domain's world calls it with its own
+ * slab's container and the same axis (0 only), orientation, window, shift and id_stride; shift and the sink plane are in global
+ * domain coordinates.  The pre-inlet lives whole (n_slabs = 1) on the rank that holds the inlet plane (rank 0 for -1, the last
+ * rank for +1), which passes its container as `pre`; every other rank passes null.  Refused on every rank (HC_ERR_ARG, the
+ * refusing rank's message) when any rank refuses: an axis other than 0, a domain periodic along x, `pre` on the wrong rank or
+ * missing on the inlet rank, what create refuses about the pair, arguments that differ between ranks, and a window whose
+ * image [window_lo + shift[0], window_hi + shift[0]] does not lie in the inlet rank's slab at least the particle envelope
+ * (hcp_envelope) away from that slab's inner face -- an arriving cell is then held by the inlet rank alone, none of its
+ * vertices has a stencil node on the neighbour, and the ordinary envelope synchronisation replicates it later.
+ * set_sink (the same arguments on every rank), apply, counts and destroy take the slab handle; on it apply is collective:
+ * the one-domain rule on the global domain.  One host wait (the select kernels; the domain's counts the vertices each slab
+ * owns), then at most two rounds over the control plane, none of which is skipped by a rank that failed locally -- it
+ * says so in the round and every rank returns the error, with no container changed and the handle's counts and its memory
+ * of what was offered as they were.  Round 1: the ranks that own part of a
+ * cell past the sink plane name it, the inlet rank names its candidates (offered for the first time, shifted extents inside
+ * the global box; the others count as rejected).  Round 2 (skipped when there is no sink and no candidate): every rank
+ * names the candidates whose id it will still hold after the sink.  Then every holder, owner or pure copy, removes the
+ * sink's cells -- in this check, before the next spread -- and the inlet rank appends the candidates nobody holds.  A
+ * holder whose own select disagrees with the owners about a cell it holds returns HC_ERR_STATE through round 2.  After a
+ * change to a type the extents already taken for the next envelope synchronisation are discarded.  n_injected, n_removed and
+ * counts are totals of distinct cells over the whole domain, the same on every rank.
+ * hc_preinlet_iterate with a slab handle: F is the inlet rank's fluid coupling and null on every other rank (null F with any
+ * other handle is HC_ERR_ARG); the inlet rank steps the pre-inlet, its slab and applies F, the other ranks step their slabs,
+ * and every cells_every iterations all ranks run the check together. */
 typedef struct hc_preinlet_cells hc_preinlet_cells;
 int hcp_preinlet_create(hc_preinlet_cells **out, hc_cells *pre, hc_cells *domain, int axis, int orientation /* -1: *neg, +1: *pos */,
                         double window_lo, double window_hi, const double shift[3], long id_stride);
+int hcp_preinlet_create_slab(hc_preinlet_cells **out, hc_cells *pre /* null off the inlet rank */, hc_cells *domain, int axis, int orientation,
+                             double window_lo, double window_hi, const double shift[3], long id_stride);
 int hcp_preinlet_set_sink(hc_preinlet_cells *X, int on, double plane);
 int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed);
 int hcp_preinlet_counts(const hc_preinlet_cells *X, long out[4]);   /* injected, rejected, removed by the sink, checks */
