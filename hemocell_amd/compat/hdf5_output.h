@@ -35,10 +35,16 @@ inline void h5_write_2d_int(hid_t file, const string &name, const vector<int> &d
   H5Dclose(did); H5Pclose(pl); H5Sclose(sid);
 }
 
+// One more atomic block beside the domain's: the pre-inlet's hidden lattice and container (compat/preInlet.h), written under the
+// block id after the domain's and positioned at its box's corner through the attributes and coordinates every block carries
+struct OutputBlock { plb::MultiBlockLattice3D<T, DESCRIPTOR> *lattice; hc_cells *cells; int id; plint origin[3]; };
+
 // writeCellField3D_HDF5 (io/ParticleHdf5IO.cpp:36-176)
-inline void writeCellField3D_HDF5(HemoCell &h, HemoCellField &field, const string &dir) {
+inline void writeCellField3D_HDF5(HemoCell &h, HemoCellField &field, const string &dir, const OutputBlock *blk = nullptr) {
   if (field.desiredOutputVariables.empty()) return;
   hc_cells *c = h.cellfields->device();
+  if (blk) c = blk->cells;
+  auto *lat = blk ? blk->lattice : h.lattice;
   long fv = 0, nc = 0; hcp_type_range(c, (int)field.ctype, &fv, &nc);
   long nvt = 0, nct = 0; hcp_counts(c, &nvt, &nct, nullptr);
   // the cells this rank reports: all of them on one GPU, those whose centre lies in its slab otherwise (the other holder of
@@ -46,8 +52,8 @@ inline void writeCellField3D_HDF5(HemoCell &h, HemoCellField &field, const strin
   vector<long> sel;
   {
     vector<double> V((size_t)nc), A((size_t)nc), B(6 * (size_t)nc), P(3 * (size_t)nc);
-    if (nc && global.world > 1) hc_check(hcp_cell_info(c, (int)field.ctype, V.data(), A.data(), B.data(), P.data()), "hcp_cell_info");
-    for (long k = 0; k < nc; k++) if (global.world == 1 || CellInformationFunctionals::centre_local(&h, &P[3 * (size_t)k])) sel.push_back(k);
+    if (nc && global.world > 1 && !blk) hc_check(hcp_cell_info(c, (int)field.ctype, V.data(), A.data(), B.data(), P.data()), "hcp_cell_info");
+    for (long k = 0; k < nc; k++) if (global.world == 1 || blk || CellInformationFunctionals::centre_local(&h, &P[3 * (size_t)k])) sel.push_back(k);
   }
   const long full_nc = nc; (void)full_nc;
   nc = (long)sel.size();
@@ -61,17 +67,19 @@ inline void writeCellField3D_HDF5(HemoCell &h, HemoCellField &field, const strin
   // the reference writes each particle where its block holds it, i.e. inside the domain; positions here are not
   // re-wrapped when a cell crosses a periodic face, so they are wrapped vertex by vertex for the output
   {
-    const plint dims[3] = {h.lattice->getNx(), h.lattice->getNy(), h.lattice->getNz()};
+    const plint dims[3] = {lat->getNx(), lat->getNy(), lat->getNz()};
     for (int d = 0; d < 3; d++) {
-      if (!h.lattice->per.p[d]) continue;
+      if (!lat->per.p[d]) continue;
       for (long i = 0; i < nvt; i++) { double &x = pos[(size_t)(3 * i + d)]; x -= (double)dims[d] * std::floor((x + 0.5) / (double)dims[d]); }
     }
+    if (blk) for (long i = 0; i < nvt; i++) for (int d = 0; d < 3; d++) pos[(size_t)(3 * i + d)] += (double)blk->origin[d];   // global coordinates
   }
   vector<long> ids((size_t)nct); if (nct) hcp_download_cell_ids(c, ids.data());
   long first_cell = 0; for (unsigned int t = 0; t < field.ctype; t++) { long f2, n2; hcp_type_range(c, (int)t, &f2, &n2); first_cell += n2; }
-  const string fileName = dir + "/" + field.name + "." + zeroPadNumber(h.iter) + ".p." + std::to_string(global.rank) + ".h5";   // one file per block (io/ParticleHdf5IO.cpp:60)
+  const int block = blk ? blk->id : global.rank;
+  const string fileName = dir + "/" + field.name + "." + zeroPadNumber(h.iter) + ".p." + std::to_string(block) + ".h5";   // one file per block (io/ParticleHdf5IO.cpp:60)
   hid_t file = H5Fcreate(fileName.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT);
-  double dx = Parameters::dx, dt = Parameters::dt; long it = h.iter, np_ = global.world; int id = global.rank;
+  double dx = Parameters::dx, dt = Parameters::dt; long it = h.iter, np_ = global.world + (h.preInlet ? 1 : 0); int id = block;
   H5LTset_attribute_double(file, "/", "dx", &dx, 1); H5LTset_attribute_double(file, "/", "dt", &dt, 1);
   H5LTset_attribute_long(file, "/", "iteration", &it, 1); H5LTset_attribute_int(file, "/", "processorId", &id, 1);
   H5LTset_attribute_long(file, "/", "numberOfProcessors", &np_, 1);
@@ -132,9 +140,11 @@ inline void writeCellField3D_HDF5(HemoCell &h, HemoCellField &field, const strin
 }
 
 // writeFluidField_HDF5 (io/FluidHdf5IO.hh:60-210)
-inline void writeFluidField_HDF5(HemoCell &h, const string &dir) {
+inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlock *blk = nullptr) {
   if (h.fluidOutputs.empty()) return;
-  auto *L = h.lattice; hc_lattice *d = L->device();
+  hc_lattice *d = h.lattice->device();   // (queued iterations run first)
+  auto *L = blk ? blk->lattice : h.lattice;
+  if (blk) d = L->device_now();
   const plint nx = L->nxl, ny = L->ny, nz = L->nz, x0 = L->x0;   // this rank's block
   const size_t plane = (size_t)ny * nz, nn = (size_t)nx * plane, ne = (size_t)(nx + 2) * plane;
   // Every field lives on the block plus one x-plane on either side (index (x + 1) * plane + y * nz + z, x = -1 .. nx): the
@@ -148,7 +158,7 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir) {
   };
   auto fill_ends = [&](vector<double> &a, int C) {   // a: [(nx + 2) * plane][C], interior already in place
     const size_t pc = plane * (size_t)C;
-    if (global.world > 1) {
+    if (global.world > 1 && !blk) {
       vector<double> rlo(pc), rhi(pc);
       hc_check(hc_comm_exchange_host(L->per.p[0] ? 1 : 0, a.data() + pc, pc * sizeof(double), a.data() + (size_t)nx * pc, pc * sizeof(double), rlo.data(), pc * sizeof(double),
                                      rhi.data(), pc * sizeof(double)), "hc_comm_exchange_host");
@@ -184,14 +194,15 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir) {
     if (bbx[k]) { rho[k] = L->bb_rho; u[3 * k] = u[3 * k + 1] = u[3 * k + 2] = 0; continue; }
     for (int c = 0; c < 3; c++) u[3 * k + c] = m >= 3 ? (double)L->wall_u[(size_t)(m - 3)][(size_t)c] : 0.0;
   }
-  const string fileName = dir + "/Fluid." + zeroPadNumber(h.iter) + ".p." + std::to_string(global.rank) + ".h5";
+  const string fileName = dir + "/Fluid." + zeroPadNumber(h.iter) + ".p." + std::to_string(blk ? blk->id : global.rank) + ".h5";
   hid_t file = H5Fcreate(fileName.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT);
-  double dx = Parameters::dx, dt = Parameters::dt; long it = h.iter; int id = global.rank;
+  double dx = Parameters::dx, dt = Parameters::dt; long it = h.iter; int id = blk ? blk->id : global.rank;
   H5LTset_attribute_double(file, "/", "dx", &dx, 1); H5LTset_attribute_double(file, "/", "dt", &dt, 1);
   H5LTset_attribute_long(file, "/", "iteration", &it, 1); H5LTset_attribute_int(file, "/", "processorId", &id, 1);
   const hsize_t Nx = nx + 2, Ny = ny + 2, Nz = nz + 2;   // one-node envelope on each side for paraview
   int ncells = (int)(Nx * Ny * Nz); int sub[3] = {(int)Nz, (int)Ny, (int)Nx};
   float dxdydz[3] = {1.f, 1.f, 1.f}, rel[3] = {-1.5f, -1.5f, (float)x0 - 1.5f};   // {z, y, x} of the block's first node - 1.5 (io/FluidHdf5IO.hh:112-118)
+  if (blk) { rel[0] += (float)blk->origin[2]; rel[1] += (float)blk->origin[1]; rel[2] += (float)blk->origin[0]; }
   const bool si = h.outputInSiUnits;
   if (si) for (int k = 0; k < 3; k++) { rel[k] *= (float)Parameters::dx; dxdydz[k] = (float)Parameters::dx; }
   H5LTset_attribute_int(file, "/", "numberOfCells", &ncells, 1); H5LTset_attribute_int(file, "/", "subdomainSize", sub, 3);
@@ -229,7 +240,8 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir) {
   for (int var : h.fluidOutputs) {
     if (var == OUTPUT_VELOCITY) write4("Velocity", 3, [&](size_t k, int cidx) { return (float)(u[3 * k + cidx] * (si ? Parameters::dx / Parameters::dt : 1.0)); });
     else if (var == OUTPUT_FORCE) {   // the external field as the driver left it (io/FluidHdf5IO.hh:240-262)
-      const auto ext = L->external_now();
+      ExternalForce<T> ext = L->external_now();
+      if (blk) ext = L->active;   // the pre-inlet's lattice holds its driving force
       write4("Force", 3, [&](size_t k, int cidx) {
         const plint xe = (plint)(k / plane) - 1, g = gx(xe) >= 0 ? gx(xe) : gx(xe < 0 ? 0 : nx - 1);
         return (float)(ext.at(g, (plint)(k / (size_t)nz % (size_t)ny), (plint)(k % (size_t)nz))[cidx] * (si ? Parameters::df : 1.0));
@@ -255,6 +267,7 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir) {
       write_raw("ShearRate", 9, out);
     } else if (var == OUTPUT_CELL_DENSITY) {   // vertices per node, one dataset per cell type (io/FluidHdf5IO.hh:374-402)
       hc_cells *c = h.cellfields->device();
+      if (blk) c = blk->cells;
       long nvt = 0; hcp_counts(c, &nvt, nullptr, nullptr);
       vector<double> pos(3 * (size_t)nvt); if (nvt) hcp_download(c, 0, pos.data());
       vector<unsigned char> alive((size_t)nvt, 1); if (nvt) hc_check(hcp_download_alive(c, alive.data()), "hcp_download_alive");

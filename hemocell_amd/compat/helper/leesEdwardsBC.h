@@ -31,6 +31,7 @@ class LeesEdwardsBC {
 
   // all three axes periodic, and the pass on from the next step on (and in lattice->initialize())
   void initialize() {
+    if (!lattice.open_decls.empty()) lattice.refuse_open("a Lees-Edwards boundary on a lattice with open boundaries: the two do not combine");
     lattice.periodicity().toggleAll(true);
     if (lattice.before_access) lattice.before_access();
     lattice.le.on = true;

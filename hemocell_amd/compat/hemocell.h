@@ -233,6 +233,7 @@ class HemoCell;
 class HemoCellFields;
 class HemoCellField;
 class HemoCellParticleField;
+class PreInlet;   // compat/preInlet.h, included at the end of this header
 }  // namespace hemo
 namespace plb { template <class PF> struct MultiParticleField3D; }
 namespace hemo {
@@ -546,7 +547,7 @@ class HemoCell {
     hlog << "(HemoCell) (Config) reading " << configFileName << endl;
     if (global.world > 1) hlog << "(HemoCell) (GPU backend) " << global.world << " atomic-blocks: one x-slab per rank and GPU, " << (tr == HC_TRANSPORT_RCCL ? "RCCL point-to-point" : "host-staged (ranks share a GPU)") << " neighbour exchange" << endl;
   }
-  ~HemoCell() { flush(); hc_synchronize(); delete cellfields; delete lattice; delete cfg; hc_comm_finalize(); global.hemoCellInitialized = false; }   // core/hemoCell.cpp:97-127: the facade owns the driver's lattice
+  inline ~HemoCell();   // core/hemoCell.cpp:97-127: the facade owns the driver's lattice (and the pre-inlet, which goes first)
 
   // config/config.cpp:88-174 (loadDirectories): <parameters><outputDirectory> (default ./tmp) gets _0, _1, ... appended when it
   // exists already; the log goes to <logDirectory>/<logFile> below it (default log/logfile), with .0, .1, ... appended when
@@ -588,7 +589,10 @@ class HemoCell {
   }
 
   // (the equilibrium replaces whatever an earlier lattice->initialize() did to the populations: its Lees-Edwards pass too)
-  void latticeEquilibrium(T rho, hemo::Array<T, 3> vel) { lattice->eq_rho = rho; for (int d = 0; d < 3; d++) lattice->eq_u[d] = vel[d]; lattice->le.init_pass = false; lattice->dirty_layout = true; }
+  void latticeEquilibrium(T rho, hemo::Array<T, 3> vel) {
+    lattice->eq_rho = rho; for (int d = 0; d < 3; d++) lattice->eq_u[d] = vel[d]; lattice->le.init_pass = false; lattice->dirty_layout = true;
+    if (preInlet) preinlet_equilibrium(rho, vel);   // the reference's pre-inlet ranks run the same line on their lattice
+  }
   void initializeCellfield() {
     cellfields = new HemoCellFields(*this);
     int env = 25;   // core/hemoCell.cpp:139 reads it here; core/hemoCellFields.cpp:43 prints it.  Used by loadParticles() on slab runs
@@ -668,6 +672,13 @@ class HemoCell {
   double *LEcurrentDisplacement = nullptr;   // hemocell.h:147: LeesEdwardsBC's constructor points it at its displacement
   unsigned int lastOutputAt = 0;
   void loadParticles();
+  // a .pos cell outside the domain box whose centre lies in the pre-inlet's box goes into the pre-inlet's container (the domain
+  // wins a tie); returns 1 when it was placed.  preinlet_loaded: the initial forces there, and the cell hand-over's parameters
+  inline int preinlet_place(int type, int id, const double *p_lu, const double *angles, double min_dist_um);
+  inline void preinlet_loaded();
+  inline hc_cells *preinlet_cells();        // the pre-inlet's container, or null
+  inline const plb::Box3D *preinlet_box();  // PreInlet::location, or null
+  inline bool preinlet_output_block(struct OutputBlock &blk);   // the pre-inlet as an output block (compat/hdf5_output.h); false before it exists
   void loadCheckPoint();
   void saveCheckPoint();
   void writeOutput();
@@ -683,6 +694,7 @@ class HemoCell {
   void iterate() {
     if (!lattice->before_access) lattice->before_access = [this] { flush(); };
     lattice->sync_force();   // what the driver wrote since the last iteration zeroed the field; usually the same force again
+    if (preInlet) preinlet_before_iterate();
     if (lattice->le.on) {
       if (leesEdwardsBC) refuse("the Lees-Edwards x-shift of particle envelopes (leesEdwardsBC = true)");
       if (pending && !(*lattice->le.cur == le_scheduled_D())) flush();
@@ -710,12 +722,18 @@ class HemoCell {
     long it = (long)iter - (long)pending;
     const int n = (int)pending;
     pending = 0;
-    hc_check(hc_iterate(lattice->device_now(), cellfields->dev, &it, n, (int)queued_timescale, /*force_limit=*/1, /*compaction look-up cadence=*/1), "iterate");
+    if (preInlet) preinlet_run(it, n);   // both systems, the hand-over after each iteration the driver asked it for
+    else hc_check(hc_iterate(lattice->device_now(), cellfields->dev, &it, n, (int)queued_timescale, /*force_limit=*/1, /*compaction look-up cadence=*/1), "iterate");
     lattice->mark_stepped();
     cellfields->particleField.invalidate();
     flushing = false;
   }
   unsigned int pending = 0, queued_timescale = 1; bool flushing = false;
+  // ---- the pre-inlet's part of the above (defined in compat/preInlet.h): the hidden lattice and container step with the domain
+  unsigned int pending_applied = 0;   // how many of the queued iterations were followed by preInlet->applyPreInlet(): a prefix of the queue
+  inline void preinlet_equilibrium(T rho, hemo::Array<T, 3> vel);
+  inline void preinlet_before_iterate();
+  inline void preinlet_run(long it, int n);
   // what the library's schedule has made D after the queued steps (hcl_set_lees_edwards_displacement)
   double le_set_D = 0;
   double le_scheduled_D() const { return lattice->le.d != 0 ? std::fmod(lattice->le.d * (double)iter, (double)lattice->nx) : le_set_D; }
@@ -727,7 +745,7 @@ class HemoCell {
   Config *cfg = nullptr;
   HemoCellFields *cellfields = nullptr;
   unsigned int iter = 0;
-  void *preInlet = nullptr;
+  PreInlet *preInlet = nullptr;   // hemocell.h:226; deleted before the lattices and containers
   string outDir, configFile, configElement;
   vector<int> fluidOutputs;
 };
@@ -939,7 +957,7 @@ inline void HemoCell::loadParticles() {
       // Here they are not placed at all.
       bool local = true;
       for (int d = 0; d < 3; d++) if (!(e.p[d] > -0.5 && e.p[d] <= (double)dims[d] - 0.5)) local = false;
-      if (!local) continue;
+      if (!local) { if (preInlet) placed_n += preinlet_place((int)j, e.id, e.p, e.a, (double)field->minimumDistanceFromSolid); continue; }
       // storage order = bricks of 32 lattice units, x-major: cells that are neighbours in space become neighbours in
       // memory, and the per-cell IBM kernels hand contiguous ranges of cells to one L2 (the cell ids stay those of the
       // file; the reference's 33 % hematocrit harness, whose .pos is in random order, runs 7 % faster this way)
@@ -963,6 +981,7 @@ inline void HemoCell::loadParticles() {
     hlog << "(readPositionsBloodCells) " << placed_per_type[j] << " complete " << (*cellfields)[j]->name << " cells placed." << endl;
   long it = iter;   // forces of the initial configuration, as the first applyConstitutiveModel would give them
   hc_check(hcp_mechanics(c, it, 1), "hcp_mechanics");
+  if (preInlet) preinlet_loaded();
 }
 
 // ------------------------------------------------------------------ checkpoint / resume (core/hemoCellFields.cpp:240-319)
@@ -972,6 +991,12 @@ inline void HemoCell::loadParticles() {
 inline string checkpoint_file(const string &dir) { return dir + (global.world > 1 ? "/checkpoint." + std::to_string(global.rank) + ".bin" : string("/checkpoint.bin")); }
 
 inline void HemoCell::saveCheckPoint() {
+  if (preInlet) {   // the pre-inlet's lattice and cells are not part of the dump: nothing is written rather than half a state
+    static bool told = false;
+    if (!told) hlog << "(HemoCell) (saveCheckPoint) the pre-inlet's state is not checkpointed by this back end: no checkpoint is written" << endl;
+    told = true;
+    return;
+  }
   string dir = global.checkpointDirectory; while (dir.size() > 1 && dir[dir.size() - 1] == '/') dir.pop_back();
   if (global.rank == 0) {
     mkpath(dir);
@@ -1013,6 +1038,7 @@ inline void HemoCell::saveCheckPoint() {
 }
 
 inline void HemoCell::loadCheckPoint() {
+  if (preInlet) refuse("resuming from a checkpoint with a pre-inlet (loadCheckPoint)");
   if (cfg->checkpointed) {   // core/hemoCellFields.cpp:244-250: continue in the directory the checkpoint names (the constructor has
                              // opened a fresh one, as the reference's does)
     string d = cfg->checkpointGeneral("OutDirectory");
@@ -1080,7 +1106,12 @@ struct CellInformationFunctionals {
   // ("incomplete cell detected, removing from output"); the single-property functionals skip the removed particles instead
   // (CellPosition :82-100, CellStretch :101-118), and velocity follows them here
   static void fill(HemoCell *h, bool vol, bool area, bool pos, bool bbox, bool stretch, bool vel = false, bool complete_only = false) {
-    hc_cells *c = h->cellfields->device();
+    fill_from(h, h->cellfields->device(), nullptr, global.rank, vol, area, pos, bbox, stretch, vel, complete_only);
+    // the pre-inlet's cells, as the reference's gather over all ranks reports them: global coordinates, the block after the domain's
+    if (hc_cells *pc = h->preinlet_cells()) fill_from(h, pc, h->preinlet_box(), global.world, vol, area, pos, bbox, stretch, vel, complete_only);
+  }
+  static void fill_from(HemoCell *h, hc_cells *c, const plb::Box3D *origin, int block, bool vol, bool area, bool pos, bool bbox, bool stretch, bool vel, bool complete_only) {
+    const double off[3] = {origin ? (double)origin->x0 : 0.0, origin ? (double)origin->y0 : 0.0, origin ? (double)origin->z0 : 0.0};
     long nvt = 0, nct = 0; hcp_counts(c, &nvt, &nct, nullptr);
     vector<long> ids((size_t)nct); if (nct) hcp_download_cell_ids(c, ids.data());
     vector<double> allpos; if (stretch) { allpos.resize(3 * (size_t)nvt); if (nvt) hcp_download(c, 0, allpos.data()); }
@@ -1098,13 +1129,13 @@ struct CellInformationFunctionals {
         int left = 0; for (int i = 0; i < nv; i++) left += al[i] ? 1 : 0;
         if (complete_only && left < nv) continue;
         if (left == 0) continue;
-        if (!centre_local(h, &P[3 * (size_t)k])) continue;   // the other holder reports it
+        if (!origin && !centre_local(h, &P[3 * (size_t)k])) continue;   // the other holder reports it
         CellInformation &ci = info()[(int)ids[(size_t)(first_cell + k)]];
-        ci.cellType = t; ci.base_cell_id = ids[(size_t)(first_cell + k)]; ci.blockId = global.rank;
+        ci.cellType = t; ci.base_cell_id = ids[(size_t)(first_cell + k)]; ci.blockId = block;
         if (vol) ci.volume = V[(size_t)k];
         if (area) ci.area = A[(size_t)k];
-        if (pos) for (int d = 0; d < 3; d++) ci.position[d] = P[3 * (size_t)k + d];
-        if (bbox) for (int d = 0; d < 6; d++) ci.bbox[d] = B[6 * (size_t)k + d];
+        if (pos) for (int d = 0; d < 3; d++) ci.position[d] = origin ? P[3 * (size_t)k + d] + off[d] : P[3 * (size_t)k + d];
+        if (bbox) for (int d = 0; d < 6; d++) ci.bbox[d] = origin ? B[6 * (size_t)k + d] + off[d / 2] : B[6 * (size_t)k + d];
         if (vel) {
           const double *vv = allvel.data() + 3 * (size_t)(fv + k * nv);
           for (int d = 0; d < 3; d++) { T sum = 0; for (int i = 0; i < nv; i++) if (al[i]) sum += vv[3 * i + d]; ci.velocity[d] = sum / T(left); }
@@ -1127,7 +1158,10 @@ struct CellInformationFunctionals {
   }
   // the single-property functionals of the reference run syncEnvelopes and deleteIncompleteCells(false) first
   // (helper/cellInfo.cpp:263-319): a cell that lost particles at a wall is gone before they look
-  static void prepare(HemoCell *h) { h->cellfields->deleteIncompleteCells(false); }
+  static void prepare(HemoCell *h) {
+    h->cellfields->deleteIncompleteCells(false);
+    if (hc_cells *pc = h->preinlet_cells()) hc_check(hcp_delete_incomplete_cells(pc, nullptr), "hcp_delete_incomplete_cells");
+  }
   static void calculateCellVolume(HemoCell *h) { prepare(h); fill(h, true, false, false, false, false); }
   static void calculateCellArea(HemoCell *h) { prepare(h); fill(h, false, true, false, false, false); }
   static void calculateCellPosition(HemoCell *h) { prepare(h); fill(h, false, false, true, false, false); }
@@ -1154,6 +1188,8 @@ struct CellInformationFunctionals {
       for (long k = 0; k < nc; k++) n[t] += centre_local(h, &P[3 * (size_t)k]) ? 1.0 : 0.0;
     }
     if (global.world > 1 && !n.empty()) hc_check(hc_comm_allreduce(n.data(), (int)n.size(), 0), "hc_comm_allreduce");
+    if (hc_cells *pc = h->preinlet_cells())   // the reference's gather covers the pre-inlet's ranks
+      for (unsigned int t = 0; t < h->cellfields->size(); t++) { long fv = 0, nc = 0; hcp_type_range(pc, (int)t, &fv, &nc); n[t] += (double)nc; }
     return n;
   }
   static pluint getTotalNumberOfCells(HemoCell *h) { double s = 0; for (double v : counts_per_type(h)) s += v; return (pluint)(s + 0.5); }
@@ -1240,6 +1276,7 @@ inline void writeCellInfo_CSV(HemoCell &h) {
 }
 
 }  // namespace hemo
+#include "preInlet.h"
 #include "hdf5_output.h"
 namespace hemo {
 
@@ -1247,6 +1284,7 @@ namespace hemo {
 inline void HemoCell::writeOutput() {
   lastOutputAt = iter;
   cellfields->deleteIncompleteCells(global.cellsDeletedInfo);   // core/hemoCell.cpp:248-252: the writers expect whole cells
+  if (hc_cells *pc = preinlet_cells()) hc_check(hcp_delete_incomplete_cells(pc, nullptr), "hcp_delete_incomplete_cells");
 #ifdef HEMOCELL_WITH_HDF5
   const string dir = outDir + "/hdf5/" + zeroPadNumber(iter);
   if (global.rank == 0) { mkdir((outDir + "/hdf5").c_str(), 0755); mkdir(dir.c_str(), 0755); }
@@ -1254,6 +1292,13 @@ inline void HemoCell::writeOutput() {
   hlog << "(HemoCell) (Output) writing output at timestep " << iter << " (" << iter * Parameters::dt << " s)" << endl;
   for (unsigned int t = 0; t < cellfields->size(); t++) writeCellField3D_HDF5(*this, *(*cellfields)[t], dir);
   writeFluidField_HDF5(*this, dir);
+  if (preinlet_cells() || preinlet_box()) {   // the pre-inlet: one more atomic block of every field, at its box's corner
+    OutputBlock blk;
+    if (preinlet_output_block(blk)) {
+      if (blk.cells) for (unsigned int t = 0; t < cellfields->size(); t++) writeCellField3D_HDF5(*this, *(*cellfields)[t], dir, &blk);
+      writeFluidField_HDF5(*this, dir, &blk);
+    }
+  }
 #else
   hlog << "(HemoCell) (Output) built without HEMOCELL_WITH_HDF5: only the CSV cell summary is written at " << iter << endl;
 #endif

@@ -68,12 +68,19 @@ struct ForcedD3Q19Descriptor {
 
 // ---- dynamics objects: only their identity and omega matter
 template <typename U, template <typename> class D>
-struct Dynamics { virtual ~Dynamics() {} virtual bool isBoundary() const { return false; } virtual U getOmega() const { return U(1); } virtual U wallDensity() const { return U(1); } };
+struct Dynamics {
+  virtual ~Dynamics() {}
+  virtual bool isBoundary() const { return false; }
+  virtual U getOmega() const { return U(1); }
+  virtual U wallDensity() const { return U(1); }
+  virtual Dynamics *clone() const { return new Dynamics(*this); }
+};
 template <typename U, template <typename> class D>
 struct GuoExternalForceBGKdynamics : Dynamics<U, D> {
   U omega;
   explicit GuoExternalForceBGKdynamics(U omega_) : omega(omega_) {}
   U getOmega() const override { return omega; }
+  Dynamics<U, D> *clone() const override { return new GuoExternalForceBGKdynamics(*this); }
 };
 template <typename U, template <typename> class D>
 struct BounceBack : Dynamics<U, D> {
@@ -81,6 +88,7 @@ struct BounceBack : Dynamics<U, D> {
   explicit BounceBack(U rho_ = U(1)) : rho(rho_) {}
   bool isBoundary() const override { return true; }
   U wallDensity() const override { return rho; }
+  Dynamics<U, D> *clone() const override { return new BounceBack(*this); }
 };
 
 struct MultiBlockManagement3D { plint nx = 0, ny = 0, nz = 0, envelope = 1; };
@@ -172,7 +180,8 @@ template <typename U, template <typename> class D>
 class MultiBlockLattice3D {
  public:
   MultiBlockLattice3D(const MultiBlockManagement3D &m, BlockCommunicator3D *, CombinedStatistics *, MultiCellAccess3D<U, D> *, Dynamics<U, D> *background)
-      : nx(m.nx), ny(m.ny), nz(m.nz), omega(background ? background->getOmega() : U(1)), mask((size_t)m.nx * m.ny * m.nz, 0) { delete background; per.changed = &dirty_layout; }
+      : nx(m.nx), ny(m.ny), nz(m.nz), omega(background ? background->getOmega() : U(1)), mask((size_t)m.nx * m.ny * m.nz, 0), background_dynamics(omega) { delete background; per.changed = &dirty_layout; }
+  const Dynamics<U, D> &getBackgroundDynamics() const { return background_dynamics; }
   ~MultiBlockLattice3D() { if (dev) hcl_destroy(dev); }
   Box3D getBoundingBox() const { return Box3D(0, nx - 1, 0, ny - 1, 0, nz - 1); }
   plint getNx() const { return nx; }
@@ -221,7 +230,7 @@ class MultiBlockLattice3D {
     active = e; dirty_force = true;
   }
   hc_lattice *device_now() {
-    if (dev && !dirty_layout) { if (dirty_force) push_force(); return dev; }
+    if (dev && !dirty_layout) { if (dirty_force) push_force(); if (dirty_open) push_open(); return dev; }
     if (dev && (stepped || cells_bound)) {
       std::cerr << "(HemoCell) (GPU backend) the lattice layout (dynamics / periodicity) was changed after " << (stepped ? "the first time step" : "the particles were loaded") << std::endl;
       std::exit(1);
@@ -249,7 +258,86 @@ class MultiBlockLattice3D {
     }
     dirty_layout = false; dirty_force = true;
     push_force();
+    for (OpenDecl &d : open_decls) { d.first_slot = -1; d.dirty_values = true; }
+    dirty_open = !open_decls.empty();
+    if (dirty_open) push_open();
     return dev;
+  }
+
+  // ---- Zou-He open boundaries (OnLatticeBoundaryCondition3D::addVelocityBoundary0N ... addPressureBoundary2P, setBoundaryVelocity
+  // and setBoundaryDensity on such nodes): recorded here in global coordinates, replayed on the device lattice after hcl_create.
+  // Consecutive declarations of one kind, axis and side share a record, so a plane declared node by node (PreInlet) gets
+  // consecutive slots.  The library's rules surface as refusals: a node declared twice, and Lees-Edwards beside open boundaries.
+  struct OpenDecl {
+    int kind, axis, orientation;
+    std::vector<int> nodes;                 // [n][3] global coordinates, in declaration order
+    std::vector<std::array<U, 4>> values;   // [n] {u_x, u_y, u_z, rho} as the driver set them
+    int first_slot = -1, n_local = 0; bool dirty_values = true;   // this rank's slots (valid once pushed)
+  };
+  std::vector<OpenDecl> open_decls;
+  std::vector<int> open_index;   // per node: (record << 1 | 1) ... 0 = none; empty until the first declaration
+  bool dirty_open = false;
+  [[noreturn]] static void refuse_open(const std::string &what) {
+    std::cerr << "(HemoCell) (GPU backend) " << what << std::endl;
+    std::exit(1);
+  }
+  void declare_open(int kind, int axis, int orientation, const Box3D &b) {
+    if (le.on) refuse_open("open boundaries on a lattice with a Lees-Edwards boundary: the two do not combine");
+    if (before_access) before_access();
+    if (open_index.empty()) open_index.assign(mask.size(), 0);
+    if (open_decls.empty() || open_decls.back().kind != kind || open_decls.back().axis != axis || open_decls.back().orientation != orientation || open_decls.back().first_slot >= 0) {
+      OpenDecl d; d.kind = kind; d.axis = axis; d.orientation = orientation; open_decls.push_back(d);
+    }
+    OpenDecl &d = open_decls.back();
+    for (plint x = b.x0; x <= b.x1; x++) for (plint y = b.y0; y <= b.y1; y++) for (plint z = b.z0; z <= b.z1; z++) {
+      if (x < 0 || y < 0 || z < 0 || x >= nx || y >= ny || z >= nz) refuse_open("open boundary: node (" + std::to_string(x) + ", " + std::to_string(y) + ", " + std::to_string(z) + ") lies outside the lattice");
+      int &slot = open_index[((size_t)x * ny + y) * nz + z];
+      if (slot) refuse_open("open boundary: node (" + std::to_string(x) + ", " + std::to_string(y) + ", " + std::to_string(z) + ") declared twice (it is an open-boundary node already)");
+      slot = (int)open_decls.size();
+      d.nodes.push_back((int)x); d.nodes.push_back((int)y); d.nodes.push_back((int)z);
+      d.values.push_back(std::array<U, 4>{{U(0), U(0), U(0), U(1)}});
+    }
+    dirty_open = true;
+  }
+  // setBoundaryVelocity / setBoundaryDensity on the declared nodes of a box; returns how many it reached
+  size_t set_open_values(const Box3D &b, int kind, const U *v) {
+    if (open_index.empty()) return 0;
+    size_t hit = 0;
+    for (OpenDecl &d : open_decls) {
+      if (d.kind != kind) continue;
+      for (size_t i = 0; i < d.values.size(); i++) {
+        const int *c = &d.nodes[3 * i];
+        if (c[0] < b.x0 || c[0] > b.x1 || c[1] < b.y0 || c[1] > b.y1 || c[2] < b.z0 || c[2] > b.z1) continue;
+        if (kind == HC_OB_VELOCITY) { d.values[i][0] = v[0]; d.values[i][1] = v[1]; d.values[i][2] = v[2]; } else d.values[i][3] = v[0];
+        if (!hit && before_access) before_access();
+        d.dirty_values = true; hit++;
+      }
+    }
+    if (hit) dirty_open = true;
+    return hit;
+  }
+  // declare what is new on the device lattice and hand over the values that changed: every rank its own rows, in local coordinates
+  void push_open() {
+    if (le.on) refuse_open("open boundaries on a lattice with a Lees-Edwards boundary: the two do not combine");
+    for (OpenDecl &d : open_decls) {
+      std::vector<int> local; std::vector<double> u, rho;
+      for (size_t i = 0; i < d.values.size(); i++) {
+        const int *c = &d.nodes[3 * i];
+        if (c[0] < x0 || c[0] >= x0 + nxl) continue;
+        local.push_back(c[0] - (int)x0); local.push_back(c[1]); local.push_back(c[2]);
+        u.push_back(d.values[i][0]); u.push_back(d.values[i][1]); u.push_back(d.values[i][2]); rho.push_back(d.values[i][3]);
+      }
+      if (d.first_slot < 0) {
+        hc_check(hcl_open_boundary_add_axis(dev, d.kind, d.axis, d.orientation, local.data(), (int)(local.size() / 3), &d.first_slot), "hcl_open_boundary_add_axis");
+        d.n_local = (int)(local.size() / 3); d.dirty_values = true;
+      }
+      if (d.dirty_values && d.n_local) {
+        if (d.kind == HC_OB_VELOCITY) hc_check(hcl_open_boundary_set_velocity(dev, d.first_slot, d.n_local, u.data(), 0), "hcl_open_boundary_set_velocity");
+        else hc_check(hcl_open_boundary_set_density(dev, d.first_slot, d.n_local, rho.data(), 0), "hcl_open_boundary_set_density");
+      }
+      d.dirty_values = false;
+    }
+    dirty_open = false;
   }
   void push_force() {
     double f[3] = {active.base[0], active.base[1], active.base[2]};
@@ -293,6 +381,7 @@ class MultiBlockLattice3D {
   bool dirty_layout = true, dirty_force = true, stepped = false, cells_bound = false;
   hc_lattice *dev = nullptr;
   int rank = 0, world = 1; plint x0 = 0, nxl = 0;   // this rank's slab (valid once device() ran)
+  GuoExternalForceBGKdynamics<U, D> background_dynamics;   // what the lattice was constructed with (getBackgroundDynamics)
 };
 
 // defineDynamics(lattice, flagMatrix, bbox, new BounceBack(1.), flag)   (examples/pipeflow/pipeflow.cpp:73)
@@ -335,6 +424,17 @@ void defineDynamics(MultiBlockLattice3D<U, D> &lattice, Box3D box, Dynamics<U, D
   delete dyn;
 }
 
+// point form (helper/genericFunctions.cpp:138-159, helper/preInlet.cpp:940-986); a node outside the lattice is nobody's
+template <typename U, template <typename> class D>
+void defineDynamics(MultiBlockLattice3D<U, D> &lattice, plint x, plint y, plint z, Dynamics<U, D> *dyn) {
+  if (x >= 0 && y >= 0 && z >= 0 && x < lattice.nx && y < lattice.ny && z < lattice.nz) {
+    const bool wall = dyn->isBoundary();
+    const size_t k = ((size_t)x * lattice.ny + y) * lattice.nz + z;
+    lattice.mask[k] = wall ? 1 : 0; lattice.note_wall(k, wall, dyn); lattice.dirty_layout = true;
+  }
+  delete dyn;
+}
+
 // setExternalVector(lattice, bbox, forceBeginsAt, F)   (core/hemoCell.cpp:369-371, examples/pipeflow/pipeflow.cpp:144-146)
 template <typename U, template <typename> class D>
 void setExternalVector(MultiBlockLattice3D<U, D> &lattice, Box3D box, int, Array<U, 3> F) {
@@ -346,8 +446,25 @@ void setExternalVector(MultiBlockLattice3D<U, D> &lattice, Box3D box, int, Array
 // A "velocity condition" node becomes a no-slip wall node moving with the velocity given by
 // setBoundaryVelocity (full-way bounce-back + Ladd momentum term inside the library).  Palabos' regularised
 // velocity nodes are isBoundary() as well, so the IBM treats both alike.
+namespace boundary { enum BcType { dirichlet, neumann, freeslip, density, outflow, normalOutflow }; }   // boundaryCondition3D.h
+
 template <typename U, template <typename> class D>
 struct OnLatticeBoundaryCondition3D {
+  virtual ~OnLatticeBoundaryCondition3D() {}
+  // Zou-He nodes (boundaryCondition/boundaryCondition3D.h): <axis><N / P>; the library completes the unknown populations
+  // inside its collide (hcl_open_boundary_add_axis).  Only the Zou-He conditions exist: a velocity is dirichlet, a pressure
+  // dirichlet or density (the other BcType values are refused)
+  void add_open(int kind, int axis, int orientation, Box3D b, MultiBlockLattice3D<U, D> &l, boundary::BcType t, const char *name) {
+    if (t != boundary::dirichlet && !(kind == HC_OB_PRESSURE && t == boundary::density)) MultiBlockLattice3D<U, D>::refuse_open(std::string(name) + ": only boundary::dirichlet velocity and boundary::density pressure nodes are part of this back end");
+    l.declare_open(kind, axis, orientation, b);
+  }
+#define HEMOCELL_OPEN_BOUNDARY(AXIS, SIDE, ORIENTATION) \
+  void addVelocityBoundary##AXIS##SIDE(Box3D b, MultiBlockLattice3D<U, D> &l, boundary::BcType t = boundary::dirichlet) { add_open(HC_OB_VELOCITY, AXIS, ORIENTATION, b, l, t, "addVelocityBoundary" #AXIS #SIDE); } \
+  void addPressureBoundary##AXIS##SIDE(Box3D b, MultiBlockLattice3D<U, D> &l, boundary::BcType t = boundary::dirichlet) { add_open(HC_OB_PRESSURE, AXIS, ORIENTATION, b, l, t, "addPressureBoundary" #AXIS #SIDE); }
+  HEMOCELL_OPEN_BOUNDARY(0, N, -1) HEMOCELL_OPEN_BOUNDARY(0, P, 1)
+  HEMOCELL_OPEN_BOUNDARY(1, N, -1) HEMOCELL_OPEN_BOUNDARY(1, P, 1)
+  HEMOCELL_OPEN_BOUNDARY(2, N, -1) HEMOCELL_OPEN_BOUNDARY(2, P, 1)
+#undef HEMOCELL_OPEN_BOUNDARY
   void setVelocityConditionOnBlockBoundaries(MultiBlockLattice3D<U, D> &l) {
     for (plint x = 0; x < l.nx; x++) for (plint y = 0; y < l.ny; y++) for (plint z = 0; z < l.nz; z++)
       if (x == 0 || y == 0 || z == 0 || x == l.nx - 1 || y == l.ny - 1 || z == l.nz - 1) l.mask[((size_t)x * l.ny + y) * l.nz + z] = 1;
@@ -360,16 +477,24 @@ struct OnLatticeBoundaryCondition3D {
 };
 template <typename U, template <typename> class D>
 OnLatticeBoundaryCondition3D<U, D> *createLocalBoundaryCondition3D() { return new OnLatticeBoundaryCondition3D<U, D>(); }
+// boundaryCondition/boundaryInstantiator3D.h, zouHeBoundary3D.h: the names drivers build a Zou-He condition from
+template <typename U, template <typename> class D> struct WrappedZouHeBoundaryManager3D {};
+template <typename U, template <typename> class D, class Manager>
+struct BoundaryConditionInstantiator3D : OnLatticeBoundaryCondition3D<U, D> {};
+template <typename U, template <typename> class D>
+OnLatticeBoundaryCondition3D<U, D> *createZouHeBoundaryCondition3D() { return new BoundaryConditionInstantiator3D<U, D, WrappedZouHeBoundaryManager3D<U, D>>(); }
 template <typename U, template <typename> class D>
 void setBoundaryVelocity(MultiBlockLattice3D<U, D> &l, Box3D b, Array<U, 3> v) {
+  l.set_open_values(b, HC_OB_VELOCITY, &v[0]);   // declared open velocity nodes take it as their slot's velocity
   const bool still = (v[0] == 0 && v[1] == 0 && v[2] == 0);
   const int cls = still ? 1 : l.wall_class(v[0], v[1], v[2]);
   for (plint x = b.x0; x <= b.x1; x++) for (plint y = b.y0; y <= b.y1; y++) for (plint z = b.z0; z <= b.z1; z++) {
     uint8_t &m = l.mask[((size_t)x * l.ny + y) * l.nz + z];
-    if (m != 0) m = (uint8_t)cls;   // only nodes that carry a velocity condition
+    if (m != 0 && m != (uint8_t)cls) { m = (uint8_t)cls; l.dirty_layout = true; }   // only nodes that carry a velocity condition
   }
-  l.dirty_layout = true;
 }
+template <typename U, template <typename> class D>
+void setBoundaryDensity(MultiBlockLattice3D<U, D> &l, Box3D b, U rho) { l.set_open_values(b, HC_OB_PRESSURE, &rho); }
 
 template <typename U, template <typename> class D>
 std::string getMultiBlockInfo(MultiBlockLattice3D<U, D> &l) {
