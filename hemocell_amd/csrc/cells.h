@@ -8,6 +8,7 @@
 // doubles per component and a mechanics workgroup stages one whole cell in LDS with coalesced loads.
 #pragma once
 #include "common.h"
+#include "host_cells.h"
 #include "mesh.h"
 #include <algorithm>
 #include <cmath>
@@ -27,12 +28,7 @@ struct hc_cells {
   int ntypes = 0;
   hc_celltype *types[8];
   int timescale[8];
-  std::vector<double> hpos[8];   // host staging per type: [ncells*nv][3]
-  std::vector<double> hvel[8], hfrc[8];
-  std::vector<double> hrep[8];   // force_repulsion staging (filled only while a repulsion is enabled)
-  std::vector<long> hids[8];
-  std::vector<int> htag[8];              // per cell: 0 complete, 2 incomplete (a gone cell never reaches the host staging)
-  std::vector<unsigned char> hdead[8];   // per vertex: 1 = this particle was removed (reference deletion mode)
+  HostCells host[8];             // host staging per type: ids always current, the payload only while the host holds it (host_cells.h)
   bool host_dirty = false;       // host staging newer than device
   long nverts = 0, cap = 0;      // live vertices (all types); allocated vertex capacity
   long ncells[8] = {0};
@@ -210,7 +206,6 @@ int stage_ints(hc_cells *C, int which, int **d, const int *h, int n);
 // the transposing copies between a staging [n][3] and three device arrays, from element `first` on (blocking)
 int upload_xyz(DevBuf<double> dst[3], long first, const double *src, long n);
 int download_xyz(double *dst, const DevBuf<double> src[3], long first, long n);
-void host_append_state(hc_cells *C, int type, long cell_id);
 int append_cells(hc_cells *C, int type, const long *cell_ids, const int *is_new, int n, long n_new);   // exchange.hip: n_new cells join the end of a type's region (is_new null: all n)
 int interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n, int which);   // ibm.hip: hcp_interpolate_cells through staging slot `which`
 

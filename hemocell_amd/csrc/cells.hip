@@ -111,7 +111,7 @@ int sync_to_device(hc_cells *C) {
   long nverts = 0;
   int rc;
   for (int t = 0; t < C->ntypes; t++) {
-    C->ncells[t] = (long)C->hids[t].size();
+    C->ncells[t] = (long)C->host[t].cells();
     nverts += C->ncells[t] * C->types[t]->host.nv;
     if (C->ncells[t] > C->capc[t]) grow = true;
   }
@@ -140,8 +140,9 @@ int sync_to_device(hc_cells *C) {
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
-    if ((rc = upload_xyz(C->pos, C->first[t], C->hpos[t].data(), n)) != HC_OK || (rc = upload_xyz(C->vel, C->first[t], C->hvel[t].data(), n)) != HC_OK ||
-        (rc = upload_xyz(C->frc, C->first[t], C->hfrc[t].data(), n)) != HC_OK) return rc;
+    const HostCells &H = C->host[t];
+    if ((rc = upload_xyz(C->pos, C->first[t], H.pos.data(), n)) != HC_OK || (rc = upload_xyz(C->vel, C->first[t], H.vel.data(), n)) != HC_OK ||
+        (rc = upload_xyz(C->frc, C->first[t], H.frc.data(), n)) != HC_OK) return rc;
   }
   HC_HIP(hipMemsetAsync(C->d_tag, 0, C->tag_cap * sizeof(int), hc::stream()));
   HC_HIP(hipMemsetAsync(C->d_vdead, 0, (size_t)C->cap, hc::stream()));
@@ -149,10 +150,11 @@ int sync_to_device(hc_cells *C) {
   for (int t = 0; t < C->ntypes; t++) {
     const long nc = C->ncells[t], n = nc * C->types[t]->host.nv;
     if (nc == 0) continue;
-    // deletion state and force_repulsion travel with the cells (a staging written before they existed has none: all live, zero)
-    if ((long)C->htag[t].size() == nc) HC_HIP(hipMemcpy(C->d_tag + C->cell0[t], C->htag[t].data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice));
-    if ((long)C->hdead[t].size() == n) HC_HIP(hipMemcpy(C->d_vdead + C->first[t], C->hdead[t].data(), (size_t)n, hipMemcpyHostToDevice));
-    if (C->rep[0] && (long)C->hrep[t].size() == 3 * n && (rc = upload_xyz(C->rep, C->first[t], C->hrep[t].data(), n)) != HC_OK) return rc;
+    // deletion state and force_repulsion travel with the cells
+    const HostCells &H = C->host[t];
+    HC_HIP(hipMemcpy(C->d_tag + C->cell0[t], H.tag.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice));
+    HC_HIP(hipMemcpy(C->d_vdead + C->first[t], H.dead.data(), (size_t)n, hipMemcpyHostToDevice));
+    if (H.has_rep && C->rep[0] && (rc = upload_xyz(C->rep, C->first[t], H.rep.data(), n)) != HC_OK) return rc;
   }
   C->host_dirty = false;
   return HC_OK;
@@ -165,20 +167,16 @@ int sync_to_host(hc_cells *C) {
   int rc;
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
-    C->hpos[t].resize((size_t)(3 * n)); C->hvel[t].resize((size_t)(3 * n)); C->hfrc[t].resize((size_t)(3 * n));
-    C->htag[t].assign((size_t)C->ncells[t], 0); C->hdead[t].assign((size_t)n, 0);
-    C->hrep[t].clear();
+    HostCells &H = C->host[t];   // not dirty: H.cells() == C->ncells[t]
+    H.size_payload(C->rep[0] != nullptr);
     if (n == 0) continue;
-    if ((rc = download_xyz(C->hpos[t].data(), C->pos, C->first[t], n)) != HC_OK || (rc = download_xyz(C->hvel[t].data(), C->vel, C->first[t], n)) != HC_OK ||
-        (rc = download_xyz(C->hfrc[t].data(), C->frc, C->first[t], n)) != HC_OK) return rc;
+    if ((rc = download_xyz(H.pos.data(), C->pos, C->first[t], n)) != HC_OK || (rc = download_xyz(H.vel.data(), C->vel, C->first[t], n)) != HC_OK ||
+        (rc = download_xyz(H.frc.data(), C->frc, C->first[t], n)) != HC_OK) return rc;
     if (C->d_tag) {
-      HC_HIP(hipMemcpy(C->htag[t].data(), C->d_tag + C->cell0[t], (size_t)C->ncells[t] * sizeof(int), hipMemcpyDeviceToHost));
-      HC_HIP(hipMemcpy(C->hdead[t].data(), C->d_vdead + C->first[t], (size_t)n, hipMemcpyDeviceToHost));
+      HC_HIP(hipMemcpy(H.tag.data(), C->d_tag + C->cell0[t], (size_t)C->ncells[t] * sizeof(int), hipMemcpyDeviceToHost));
+      HC_HIP(hipMemcpy(H.dead.data(), C->d_vdead + C->first[t], (size_t)n, hipMemcpyDeviceToHost));
     }
-    if (C->rep[0]) {
-      C->hrep[t].resize((size_t)(3 * n));
-      if ((rc = download_xyz(C->hrep[t].data(), C->rep, C->first[t], n)) != HC_OK) return rc;
-    }
+    if (H.has_rep && (rc = download_xyz(H.rep.data(), C->rep, C->first[t], n)) != HC_OK) return rc;
   }
   return HC_OK;
 }
@@ -215,17 +213,6 @@ int stage_ints(hc_cells *C, int which, int **d, const int *h, int n) {
   }
   *d = s.d;
   return HC_OK;
-}
-
-// id, deletion state and force_repulsion of a cell whose vertices were just appended to the host staging of its type
-void host_append_state(hc_cells *C, int type, long cell_id) {
-  const size_t nv = (size_t)C->types[type]->host.nv, nc = C->hids[type].size();
-  C->htag[type].resize(nc, 0); C->hdead[type].resize(nc * nv, 0);
-  if (C->rep_on()) C->hrep[type].resize(3 * nc * nv, 0.0);
-  C->hids[type].push_back(cell_id);
-  C->htag[type].push_back(0); C->hdead[type].resize((nc + 1) * nv, 0);
-  if (C->rep_on()) C->hrep[type].resize(3 * (nc + 1) * nv, 0.0);
-  C->host_dirty = true;
 }
 
 // hcp_celltype_create / _create_wbc / _create_ex: mesh, tables and moduli on the host, then the tables to the device
@@ -361,7 +348,7 @@ int hcp_set_envelope(hc_cells *C, double particle_envelope_lu, double *share_in_
   HC_REQUIRE(C, "hcp_set_envelope: null pointer");
   HC_REQUIRE(particle_envelope_lu > 0.0 && particle_envelope_lu < 1e6, "hcp_set_envelope: the envelope must be a positive number of lattice units");
   HC_REQUIRE(C->ntypes > 0, "hcp_set_envelope: add the cell types first (the envelope is measured against the largest cell)");
-  for (int t = 0; t < C->ntypes; t++) HC_REQUIRE(C->hids[t].empty(), "hcp_set_envelope: set the envelope before the first cell is placed (placement already uses it)");
+  for (int t = 0; t < C->ntypes; t++) HC_REQUIRE(C->host[t].cells() == 0, "hcp_set_envelope: set the envelope before the first cell is placed (placement already uses it)");
   double dmax = 0.0;
   for (int t = 0; t < C->ntypes; t++) dmax = std::max(dmax, C->types[t]->host.diameter);
   double share = std::max(particle_envelope_lu - dmax, E_SHARE_MIN);
@@ -394,7 +381,7 @@ int hcp_add_type(hc_cells *C, hc_celltype *T, int material_timescale, int *type_
   HC_REQUIRE(C && T, "hcp_add_type: null pointer");
   HC_REQUIRE(C->ntypes < 8, "hcp_add_type: at most 8 cell types");
   HC_REQUIRE(material_timescale >= 1, "hcp_add_type: material timescale must be >= 1");
-  C->types[C->ntypes] = T; C->timescale[C->ntypes] = material_timescale;
+  C->types[C->ntypes] = T; C->timescale[C->ntypes] = material_timescale; C->host[C->ntypes].nv = T->host.nv;
   if (type_index) *type_index = C->ntypes;
   C->ntypes++;
   return HC_OK;
@@ -469,11 +456,9 @@ int hcp_add_cell(hc_cells *C, int type, long cell_id, const double centre_lu[3],
     if (L->n_slabs > 1) { C->slab_rejected.push_back(type); C->slab_rejected.push_back(cell_id); }   // the other holders must drop it too
     return HC_OK;
   }
-  for (int i = 0; i < nv; i++) {
-    C->hpos[type].push_back(cx + m[i][0]); C->hpos[type].push_back(centre_lu[1] + m[i][1]); C->hpos[type].push_back(centre_lu[2] + m[i][2]);
-    for (int d = 0; d < 3; d++) { C->hvel[type].push_back(0.0); C->hfrc[type].push_back(0.0); }
-  }
-  host_append_state(C, type, cell_id);
+  double *p = C->host[type].append(cell_id, C->rep_on());
+  for (int i = 0; i < nv; i++) { p[3 * i] = cx + m[i][0]; p[3 * i + 1] = centre_lu[1] + m[i][1]; p[3 * i + 2] = centre_lu[2] + m[i][2]; }
+  C->host_dirty = true;
   return HC_OK;
 }
 
@@ -484,9 +469,9 @@ int hcp_add_cell_unchecked(hc_cells *C, int type, long cell_id, const double cen
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   const CellTables &T = C->types[type]->host;
   (void)angles;
-  for (int i = 0; i < T.nv; i++)
-    for (int d = 0; d < 3; d++) { C->hpos[type].push_back(centre_lu[d] + T.vertices[i][d]); C->hvel[type].push_back(0.0); C->hfrc[type].push_back(0.0); }
-  host_append_state(C, type, cell_id);
+  double *p = C->host[type].append(cell_id, C->rep_on());
+  for (int i = 0; i < T.nv; i++) for (int d = 0; d < 3; d++) p[3 * i + d] = centre_lu[d] + T.vertices[i][d];
+  C->host_dirty = true;
   return HC_OK;
 }
 
@@ -494,7 +479,7 @@ int hcp_counts(hc_cells *C, long *n_vertices, long *n_cells, long *n_deleted) {
   HC_REQUIRE(C, "hcp_counts: null pointer");
   { int rc = settle(C); if (rc != HC_OK) return rc; }
   long nv = 0, nc = 0;
-  for (int t = 0; t < C->ntypes; t++) { nc += (long)C->hids[t].size(); nv += (long)C->hids[t].size() * C->types[t]->host.nv; }
+  for (int t = 0; t < C->ntypes; t++) { nc += (long)C->host[t].cells(); nv += (long)C->host[t].cells() * C->types[t]->host.nv; }
   if (n_vertices) *n_vertices = nv;
   if (n_cells) *n_cells = nc;
   if (n_deleted) *n_deleted = C->n_deleted;
@@ -505,9 +490,9 @@ int hcp_type_range(hc_cells *C, int type, long *first_vertex, long *n_cells) {
   HC_REQUIRE(C && type >= 0 && type < C->ntypes, "hcp_type_range: bad arguments");
   { int rc = settle(C); if (rc != HC_OK) return rc; }
   long f = 0;
-  for (int t = 0; t < type; t++) f += (long)C->hids[t].size() * C->types[t]->host.nv;
+  for (int t = 0; t < type; t++) f += (long)C->host[t].cells() * C->types[t]->host.nv;
   if (first_vertex) *first_vertex = f;
-  if (n_cells) *n_cells = (long)C->hids[type].size();
+  if (n_cells) *n_cells = (long)C->host[type].cells();
   return HC_OK;
 }
 
@@ -517,7 +502,8 @@ int hcp_download(hc_cells *C, int what, double *out) {
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   size_t o = 0;
   for (int t = 0; t < C->ntypes; t++) {
-    const std::vector<double> &src = what == 0 ? C->hpos[t] : what == 1 ? C->hvel[t] : C->hfrc[t];
+    const HostCells &H = C->host[t];
+    const std::vector<double> &src = what == 0 ? H.pos : what == 1 ? H.vel : H.frc;
     std::copy(src.begin(), src.end(), out + o);
     o += src.size();
   }
@@ -530,7 +516,8 @@ int hcp_upload(hc_cells *C, int what, const double *in) {
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   size_t o = 0;
   for (int t = 0; t < C->ntypes; t++) {
-    std::vector<double> &dst = what == 0 ? C->hpos[t] : what == 1 ? C->hvel[t] : C->hfrc[t];
+    HostCells &H = C->host[t];
+    std::vector<double> &dst = what == 0 ? H.pos : what == 1 ? H.vel : H.frc;
     std::copy(in + o, in + o + dst.size(), dst.begin());
     o += dst.size();
   }
@@ -557,21 +544,21 @@ int hcp_download_records(hc_cells *C, void *records, long n_records) {
   int rc = settle(C); if (rc != HC_OK) return rc;
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   long total = 0;
-  for (int t = 0; t < C->ntypes; t++) { total += (long)C->hids[t].size() * C->types[t]->host.nv; for (unsigned char dd : C->hdead[t]) total -= dd ? 1 : 0; }
+  for (int t = 0; t < C->ntypes; t++) { total += (long)C->host[t].cells() * C->types[t]->host.nv; for (unsigned char dd : C->host[t].dead) total -= dd ? 1 : 0; }
   HC_REQUIRE(n_records == total, "hcp_download_records: the buffer must hold exactly one record per particle (hcp_counts vertices minus hcp_deletion_counts removed-and-still-listed particles)");
   SvRecord *out = static_cast<SvRecord *>(records);
   long o = 0;
   for (int t = 0; t < C->ntypes; t++) {
     const int nv = C->types[t]->host.nv;
-    const bool has_rep = C->hrep[t].size() == C->hpos[t].size();
-    for (size_t c = 0; c < C->hids[t].size(); c++)
+    const HostCells &H = C->host[t];
+    for (size_t c = 0; c < H.cells(); c++)
       for (int i = 0; i < nv; i++) {
-        if (C->hdead[t][c * (size_t)nv + (size_t)i]) continue;   // a particle removeParticles(1) took out (core/hemoCellParticleField.cpp:304-321)
+        if (H.dead[c * (size_t)nv + (size_t)i]) continue;   // a particle removeParticles(1) took out (core/hemoCellParticleField.cpp:304-321)
         SvRecord &r = out[o++];
         std::memset(&r, 0, sizeof(r));
         const size_t k = 3 * (c * (size_t)nv + (size_t)i);
-        for (int d = 0; d < 3; d++) { r.v[d] = C->hvel[t][k + d]; r.position[d] = C->hpos[t][k + d]; r.force[d] = C->hfrc[t][k + d]; r.force_repulsion[d] = has_rep ? C->hrep[t][k + d] : 0.0; }
-        r.cellId = C->hids[t][c]; r.vertexId = (unsigned short)i; r.restime = 0; r.celltype = (unsigned char)t;
+        for (int d = 0; d < 3; d++) { r.v[d] = H.vel[k + d]; r.position[d] = H.pos[k + d]; r.force[d] = H.frc[k + d]; r.force_repulsion[d] = H.has_rep ? H.rep[k + d] : 0.0; }
+        r.cellId = H.ids[c]; r.vertexId = (unsigned short)i; r.restime = 0; r.celltype = (unsigned char)t;
       }
   }
   return HC_OK;
@@ -585,36 +572,34 @@ int hcp_upload_records(hc_cells *C, const void *records, long n_records) {
   int rc = settle(C); if (rc != HC_OK) return rc;
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   const SvRecord *in = static_cast<const SvRecord *>(records);
-  std::vector<long> ids[8]; std::vector<double> pos[8], vel[8], frc[8], rep[8]; std::vector<int> seen[8];
-  std::vector<std::pair<long, long>> index[8];   // (cellId, slot), sorted on demand
+  HostCells built[8];   // swapped in at the end: a bad record leaves the container as it was.  A new cell has every particle flagged as removed; its records clear the flags
+  for (int t = 0; t < C->ntypes; t++) { built[t].nv = C->types[t]->host.nv; built[t].has_rep = C->rep_on(); }
   for (long k = 0; k < n_records; k++) {
     const SvRecord &r = in[k];
     const int t = r.celltype;
     HC_REQUIRE(t < C->ntypes, "hcp_upload_records: record with an unknown celltype");
     const int nv = C->types[t]->host.nv;
     HC_REQUIRE(r.vertexId < nv, "hcp_upload_records: vertexId out of range for its cell type");
+    HostCells &H = built[t];
     long slot = -1;
-    for (size_t c = ids[t].size(); c-- > 0;) if (ids[t][c] == r.cellId) { slot = (long)c; break; }   // records of a cell usually arrive together
+    for (size_t c = H.cells(); c-- > 0;) if (H.ids[c] == r.cellId) { slot = (long)c; break; }   // records of a cell usually arrive together
     if (slot < 0) {
-      slot = (long)ids[t].size(); ids[t].push_back(r.cellId);
-      pos[t].resize(pos[t].size() + 3 * (size_t)nv, 0.0); vel[t].resize(pos[t].size(), 0.0); frc[t].resize(pos[t].size(), 0.0); rep[t].resize(pos[t].size(), 0.0);
-      seen[t].resize(seen[t].size() + (size_t)nv, 0);
+      slot = (long)H.cells(); H.append(r.cellId, H.has_rep);
+      std::fill(H.dead.end() - nv, H.dead.end(), (unsigned char)1);
     }
     const size_t v = (size_t)slot * nv + r.vertexId;
-    HC_REQUIRE(!seen[t][v], "hcp_upload_records: duplicate (cellId, vertexId)");
-    seen[t][v] = 1;
-    for (int d = 0; d < 3; d++) { pos[t][3 * v + d] = r.position[d]; vel[t][3 * v + d] = r.v[d]; frc[t][3 * v + d] = r.force[d]; rep[t][3 * v + d] = r.force_repulsion[d]; }
+    HC_REQUIRE(H.dead[v], "hcp_upload_records: duplicate (cellId, vertexId)");
+    H.dead[v] = 0;
+    for (int d = 0; d < 3; d++) { H.pos[3 * v + d] = r.position[d]; H.vel[3 * v + d] = r.v[d]; H.frc[3 * v + d] = r.force[d]; if (H.has_rep) H.rep[3 * v + d] = r.force_repulsion[d]; }   // force_repulsion travels through the staging
   }
   // A cell with a vertexId missing is what removeParticles(1) leaves behind (core/hemoCellParticleField.cpp:304-321) and what a
   // checkpoint written between two deleteIncompleteCells holds: it arrives as the incomplete cell it was (tag 2, the missing
   // particles flagged as removed), exactly the state hcp_download_records serialised; the reference's load path then runs
   // deleteIncompleteCells (core/hemoCellFields.cpp:272-274), which is the caller's next call.
   for (int t = 0; t < C->ntypes; t++) {
-    const size_t nv = (size_t)C->types[t]->host.nv;
-    C->hids[t].swap(ids[t]); C->hpos[t].swap(pos[t]); C->hvel[t].swap(vel[t]); C->hfrc[t].swap(frc[t]);
-    C->htag[t].assign(C->hids[t].size(), 0); C->hdead[t].assign(C->hids[t].size() * nv, 0);
-    for (size_t v = 0; v < seen[t].size(); v++) if (!seen[t][v]) { C->hdead[t][v] = 1; C->htag[t][v / nv] = 2; }
-    if (C->rep_on()) C->hrep[t].swap(rep[t]); else C->hrep[t].clear();   // force_repulsion travels through the staging
+    HostCells &H = built[t];
+    for (size_t v = 0; v < H.dead.size(); v++) if (H.dead[v]) H.tag[v / (size_t)H.nv] = 2;
+    std::swap(C->host[t], H);
   }
   C->host_dirty = true;
   return sync_to_device(C);
@@ -624,7 +609,7 @@ int hcp_download_cell_ids(hc_cells *C, long *ids) {
   HC_REQUIRE(C && ids, "hcp_download_cell_ids: null pointer");
   { int rc = settle(C); if (rc != HC_OK) return rc; }
   size_t o = 0;
-  for (int t = 0; t < C->ntypes; t++) { std::copy(C->hids[t].begin(), C->hids[t].end(), ids + o); o += C->hids[t].size(); }
+  for (int t = 0; t < C->ntypes; t++) { std::copy(C->host[t].ids.begin(), C->host[t].ids.end(), ids + o); o += C->host[t].cells(); }
   return HC_OK;
 }
 
@@ -701,24 +686,12 @@ int hcp_add_vertex_force(hc_cells *C, const long *vertex_index, int n, const dou
 static int compact_gone(hc_cells *C) {
   int rc = sync_to_host(C); if (rc != HC_OK) return rc;
   for (int t = 0; t < C->ntypes; t++) {
-    const size_t nc = C->hids[t].size(), nv = (size_t)C->types[t]->host.nv;
-    const bool has_rep = C->hrep[t].size() == 3 * nc * nv;
-    size_t w = 0;
-    for (size_t c = 0; c < nc; c++) {
-      if (C->htag[t][c] == 1) { C->n_deleted++; if (C->L && C->L->n_slabs > 1) C->slab_gone[t].push_back(C->hids[t][c]); continue; }
-      if (w != c) {
-        std::copy(C->hpos[t].begin() + 3 * c * nv, C->hpos[t].begin() + 3 * (c + 1) * nv, C->hpos[t].begin() + 3 * w * nv);
-        std::copy(C->hvel[t].begin() + 3 * c * nv, C->hvel[t].begin() + 3 * (c + 1) * nv, C->hvel[t].begin() + 3 * w * nv);
-        std::copy(C->hfrc[t].begin() + 3 * c * nv, C->hfrc[t].begin() + 3 * (c + 1) * nv, C->hfrc[t].begin() + 3 * w * nv);
-        if (has_rep) std::copy(C->hrep[t].begin() + 3 * c * nv, C->hrep[t].begin() + 3 * (c + 1) * nv, C->hrep[t].begin() + 3 * w * nv);
-        std::copy(C->hdead[t].begin() + c * nv, C->hdead[t].begin() + (c + 1) * nv, C->hdead[t].begin() + w * nv);
-        C->htag[t][w] = C->htag[t][c]; C->hids[t][w] = C->hids[t][c];
-      }
-      w++;
-    }
-    C->hpos[t].resize(3 * w * nv); C->hvel[t].resize(3 * w * nv); C->hfrc[t].resize(3 * w * nv);
-    if (has_rep) C->hrep[t].resize(3 * w * nv);
-    C->hdead[t].resize(w * nv); C->htag[t].resize(w); C->hids[t].resize(w);
+    HostCells &H = C->host[t];
+    H.compact([&](size_t c) {
+      if (H.tag[c] != 1) return true;
+      C->n_deleted++; if (C->L && C->L->n_slabs > 1) C->slab_gone[t].push_back(H.ids[c]);
+      return false;
+    });
   }
   C->host_dirty = true;
   return sync_to_device(C);
@@ -792,7 +765,7 @@ int hcp_deletion_counts(hc_cells *C, long *cells_removed, long *particles_remove
   int rc = settle(C); if (rc != HC_OK) return rc;
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   long inc = 0, miss = 0;
-  for (int t = 0; t < C->ntypes; t++) { for (int g : C->htag[t]) inc += g == 2; for (unsigned char d : C->hdead[t]) miss += d ? 1 : 0; }
+  for (int t = 0; t < C->ntypes; t++) { for (int g : C->host[t].tag) inc += g == 2; for (unsigned char d : C->host[t].dead) miss += d ? 1 : 0; }
   if (cells_removed) *cells_removed = C->n_deleted;
   if (particles_removed) *particles_removed = C->n_particles_deleted;
   if (incomplete_cells) *incomplete_cells = inc;
@@ -805,7 +778,7 @@ int hcp_download_alive(hc_cells *C, unsigned char *alive) {
   int rc = settle(C); if (rc != HC_OK) return rc;
   rc = sync_to_host(C); if (rc != HC_OK) return rc;
   size_t o = 0;
-  for (int t = 0; t < C->ntypes; t++) for (unsigned char d : C->hdead[t]) alive[o++] = d ? 0 : 1;
+  for (int t = 0; t < C->ntypes; t++) for (unsigned char d : C->host[t].dead) alive[o++] = d ? 0 : 1;
   return HC_OK;
 }
 

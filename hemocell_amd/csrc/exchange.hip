@@ -138,16 +138,11 @@ int append_cells(hc_cells *C, int type, const long *cell_ids, const int *is_new,
   if (C->ncells[type] + n_new > C->capc[type]) {
     // slow path: grow the device regions through the host staging
     rc = sync_to_host(C); if (rc != HC_OK) return rc;
-    const size_t add = (size_t)C->types[type]->host.nv * 3;
-    for (int i = 0; i < n; i++) {
-      if (is_new && !is_new[i]) continue;
-      C->hpos[type].resize(C->hpos[type].size() + add, 0.0); C->hvel[type].resize(C->hvel[type].size() + add, 0.0); C->hfrc[type].resize(C->hfrc[type].size() + add, 0.0);
-      host_append_state(C, type, cell_ids[i]);   // id, deletion state and force_repulsion grow with the vertices: the state of the cells already here survives
-    }
+    for (int i = 0; i < n; i++) if (!is_new || is_new[i]) C->host[type].append(cell_ids[i], C->rep_on());   // the state of the cells already here survives
     C->host_dirty = true;
     rc = sync_to_device(C); if (rc != HC_OK) return rc;
   } else {
-    for (int i = 0; i < n; i++) if (!is_new || is_new[i]) C->hids[type].push_back(cell_ids[i]);
+    for (int i = 0; i < n; i++) if (!is_new || is_new[i]) C->host[type].ids_push(cell_ids[i]);
     C->ncells[type] += n_new;
     C->nverts += n_new * C->types[type]->host.nv;
   }
@@ -252,10 +247,10 @@ int hcp_remove_cells(hc_cells *C, int type, const int *slots, int n) {
     if (!dead[(size_t)h]) continue;
     while (tail < nc && dead[(size_t)tail]) tail++;
     src.push_back((int)tail); dst.push_back((int)h);
-    C->hids[type][(size_t)h] = C->hids[type][(size_t)tail];
+    C->host[type].ids_move((size_t)h, (size_t)tail);
     tail++;
   }
-  C->hids[type].resize((size_t)new_nc);
+  C->host[type].ids_truncate((size_t)new_nc);
   if (!src.empty()) {
     int *d_src = nullptr, *d_dst = nullptr;
     rc = stage_ints(C, 0, &d_src, src.data(), (int)src.size()); if (rc != HC_OK) return rc;

@@ -671,7 +671,7 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
     obase[(size_t)t] = (long)o;
     order.resize(o + nc);
     std::iota(order.begin() + (long)o, order.end(), 0);
-    const std::vector<long> &ids = C->hids[t];
+    const std::vector<long> &ids = C->host[t].ids;
     std::stable_sort(order.begin() + (long)o, order.end(), [&](int a, int b) { return ids[(size_t)a] < ids[(size_t)b]; });
   }
   int *d_order = nullptr;

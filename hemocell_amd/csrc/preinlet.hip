@@ -168,7 +168,7 @@ static int reserve_blocks(hc_preinlet_cells *X) {
   for (int w = 0; w < 2; w++) {
     if (!both[w]) continue;
     long total = 0;
-    for (int t = 0; t < both[w]->ntypes; t++) total += (long)both[w]->hids[t].size();
+    for (int t = 0; t < both[w]->ntypes; t++) total += (long)both[w]->host[t].cells();
     int rc = reserve_select(X, X->sel[w], total); if (rc != HC_OK) return rc;
   }
   return HC_OK;
@@ -285,7 +285,7 @@ static int apply_slab(hc_preinlet_cells *X, long *n_injected, long *n_removed) {
           if (cmin > cmax) continue;   // no live vertex
           if (!(X->orient < 0 ? cmax > X->sink_plane : cmin < X->sink_plane)) continue;
           past[(size_t)t][(size_t)c] = 1;
-          if (r[0] > 0.0) { sunk.push_back(t); sunk.push_back(D->hids[t][(size_t)c]); }   // a pure copy is its owners' business
+          if (r[0] > 0.0) { sunk.push_back(t); sunk.push_back(D->host[t].ids[(size_t)c]); }   // a pure copy is its owners' business
         }
       }
     if (P) {
@@ -294,7 +294,7 @@ static int apply_slab(hc_preinlet_cells *X, long *n_injected, long *n_removed) {
         for (size_t i = 0; i < cand[t].size(); i++) {
           const Cand &k = cand[t][i];
           HC_REQUIRE(k.lap > -(1L << 30) && k.lap < (1L << 30), std::string(fn) + ": lap out of range");
-          const long id = P->hids[t][(size_t)k.slot] + (k.lap - X->orient) * X->stride;
+          const long id = P->host[t].ids[(size_t)k.slot] + (k.lap - X->orient) * X->stride;
           if (X->offered.count(std::make_pair(t, id)) || !offers.insert(std::make_pair(t, id)).second) continue;
           if (!arrives_inside(X, k)) { mine[2]++; continue; }
           offer.push_back(std::make_pair(t, (int)i)); offered.push_back(t); offered.push_back(id);
@@ -332,7 +332,7 @@ static int apply_slab(hc_preinlet_cells *X, long *n_injected, long *n_removed) {
   auto second_part = [&]() -> int {
     for (int t = 0; t < ntypes && selected; t++)
       for (long c = 0; c < D->ncells[t]; c++) {
-        const long id = D->hids[t][(size_t)c];
+        const long id = D->host[t].ids[(size_t)c];
         if ((past[(size_t)t][(size_t)c] != 0) != (sunk.count(std::make_pair(t, id)) != 0)) {
           hc::set_error(std::string(fn) + ": this rank's copy of cell " + std::to_string(id) + " of type " + std::to_string(t) +
                         " and its owners disagree on whether it lies past the sink plane");
@@ -341,7 +341,7 @@ static int apply_slab(hc_preinlet_cells *X, long *n_injected, long *n_removed) {
       }
     for (const std::pair<int, long> &a : announced) {
       if (a.first < 0 || a.first >= ntypes || sunk.count(a)) continue;
-      const std::vector<long> &ids = D->hids[a.first];
+      const std::vector<long> &ids = D->host[a.first].ids;
       if (std::find(ids.begin(), ids.end(), a.second) != ids.end()) { held.push_back(a.first); held.push_back(a.second); }
     }
     return HC_OK;
@@ -355,7 +355,7 @@ static int apply_slab(hc_preinlet_cells *X, long *n_injected, long *n_removed) {
   // the sink: every holder, owners and pure copies alike
   for (int t = 0; t < ntypes && !sunk.empty(); t++) {
     std::vector<int> gone;
-    for (long c = 0; c < D->ncells[t]; c++) if (sunk.count(std::make_pair(t, D->hids[t][(size_t)c]))) gone.push_back((int)c);
+    for (long c = 0; c < D->ncells[t]; c++) if (sunk.count(std::make_pair(t, D->host[t].ids[(size_t)c]))) gone.push_back((int)c);
     if (gone.empty()) continue;
     if ((rc = hcp_remove_cells(D, t, gone.data(), (int)gone.size())) != HC_OK) return rc;
     D->ext_pending[t] = false;   // extents on their way to the next envelope synchronisation describe the old slots
@@ -517,11 +517,11 @@ int hcp_preinlet_apply(hc_preinlet_cells *X, long *n_injected, long *n_removed) 
   long injected = 0;
   for (int t = 0; t < ntypes; t++) {
     if (cand[t].empty()) continue;
-    std::unordered_set<long> held(D->hids[t].begin(), D->hids[t].end());
+    std::unordered_set<long> held(D->host[t].ids.begin(), D->host[t].ids.end());
     std::vector<int> src, lap; std::vector<long> ids;
     for (const Cand &k : cand[t]) {
       HC_REQUIRE(k.lap > -(1L << 30) && k.lap < (1L << 30), "hcp_preinlet_apply: lap out of range");
-      const long id = P->hids[t][(size_t)k.slot] + (k.lap - X->orient) * X->stride;   // getOffset: positive for *neg
+      const long id = P->host[t].ids[(size_t)k.slot] + (k.lap - X->orient) * X->stride;   // getOffset: positive for *neg
       if (!X->offered.insert(std::make_pair(t, id)).second) continue;
       if (!arrives_inside(X, k)) { X->rejected++; continue; }
       if (!held.insert(id).second) continue;

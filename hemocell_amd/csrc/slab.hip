@@ -210,7 +210,7 @@ int sync_begin(Slab *S, std::vector<Plan> &plans) {
     P.n = C->ext_n[t];
     if (P.n) HC_HIP(hipEventSynchronize(C->ext_done[t]));
     P.ext.assign(C->h_ext[t].p, C->h_ext[t].p + 4 * P.n);
-    const std::vector<long> &ids = C->hids[t];
+    const std::vector<long> &ids = C->host[t].ids;
     for (long c = 0; c < P.n; c++) {
       const double *e = &P.ext[(size_t)(4 * c)];
       if (e[3] != 0.0) { P.gone.push_back((int)c); continue; }
@@ -320,7 +320,7 @@ int sync_merge(Slab *S, std::vector<Plan> &plans, hipStream_t comm_stream) {
     const long n = P.n;
     std::unordered_map<long, long> known;
     known.reserve((size_t)n * 2 + 16);
-    for (long c = 0; c < n; c++) known[C->hids[t][(size_t)c]] = c;
+    for (long c = 0; c < n; c++) known[C->host[t].ids[(size_t)c]] = c;
     std::vector<char> refreshed((size_t)n, 0);
     long next_new = n;
     // a neighbour that has not heard yet still sends its copy of a cell this rank compacted away: it lands in a new slot
@@ -349,7 +349,7 @@ int sync_merge(Slab *S, std::vector<Plan> &plans, hipStream_t comm_stream) {
     for (int side = 0; side < 2; side++) for (long id : P.tag_r[side]) dead_ids.insert(id);
     for (long c = 0; c < n; c++) {
       const double *e = &P.ext[(size_t)(4 * c)];
-      const bool gone = e[3] != 0.0, told = !dead_ids.empty() && dead_ids.count(C->hids[t][(size_t)c]) > 0;
+      const bool gone = e[3] != 0.0, told = !dead_ids.empty() && dead_ids.count(C->host[t].ids[(size_t)c]) > 0;
       if (gone || told) { drop.push_back((int)c); S->stats[3] += 1.0; C->n_deleted++; any_gone = any_gone || gone; }
       else if (e[2] <= 0.0 && !refreshed[(size_t)c]) { drop.push_back((int)c); S->stats[2] += 1.0; }
     }
@@ -551,26 +551,16 @@ int hcp_slab_sync_placement(hc_cells *C, long *global_cells_per_type) {
   const hc_lattice *L = C->L;
   std::vector<double> counts((size_t)C->ntypes, 0.0);
   for (int t = 0; t < C->ntypes; t++) {
-    const size_t nv = (size_t)C->types[t]->host.nv, nc = C->hids[t].size();
-    const bool has_rep = C->hrep[t].size() == 3 * nc * nv;
-    size_t w = 0;
-    for (size_t c = 0; c < nc; c++) {
-      if (rejected[t].count(C->hids[t][c])) continue;
-      if (w != c) {
-        std::copy(C->hpos[t].begin() + 3 * c * nv, C->hpos[t].begin() + 3 * (c + 1) * nv, C->hpos[t].begin() + 3 * w * nv);
-        std::copy(C->hvel[t].begin() + 3 * c * nv, C->hvel[t].begin() + 3 * (c + 1) * nv, C->hvel[t].begin() + 3 * w * nv);
-        std::copy(C->hfrc[t].begin() + 3 * c * nv, C->hfrc[t].begin() + 3 * (c + 1) * nv, C->hfrc[t].begin() + 3 * w * nv);
-        if (has_rep) std::copy(C->hrep[t].begin() + 3 * c * nv, C->hrep[t].begin() + 3 * (c + 1) * nv, C->hrep[t].begin() + 3 * w * nv);
-        C->hids[t][w] = C->hids[t][c];
-      }
-      const long gx = (long)std::floor(C->hpos[t][3 * w * nv] + 0.5) - L->x0;
+    HostCells &H = C->host[t];
+    const size_t nc = H.cells();
+    const size_t w = H.compact([&](size_t c) { return rejected[t].count(H.ids[c]) == 0; });
+    for (size_t c = 0; c < w; c++) {
+      const long gx = (long)std::floor(H.pos[3 * c * (size_t)H.nv] + 0.5) - L->x0;
       if (L->n_slabs == 1 || (gx >= 0 && gx < L->nx)) counts[(size_t)t] += 1.0;
-      w++;
     }
     if (w != nc) {
-      C->hpos[t].resize(3 * w * nv); C->hvel[t].resize(3 * w * nv); C->hfrc[t].resize(3 * w * nv);
-      if (has_rep) C->hrep[t].resize(3 * w * nv);
-      C->hids[t].resize(w); C->htag[t].assign(w, 0); C->hdead[t].assign(w * nv, 0);
+      // dropping a cell resets the deletion state of the cells that stay: every survivor becomes complete and whole
+      H.tag.assign(w, 0); H.dead.assign(w * (size_t)H.nv, 0);
       C->host_dirty = true;
     }
   }

@@ -1,5 +1,5 @@
 """The storage paths of the cell container (csrc/cells.hip and the scratch blocks of ibm.hip, mechanics.hip, exchange.hip):
-regrowth of the device regions, the staged slot lists, the information and extents scratch, and create / destroy.  Other
+regrowth of the device regions, compaction after a deletion, hole filling on the device, the staged slot lists, the information and extents scratch, and create / destroy.  Other
 suites reach them only through slab or pre-inlet runs.  32 x 32 x 32 all-fluid periodic lattice, the RBC and PLT types of
 host.CellType; every comparison is bit for bit."""
 import ctypes as C
@@ -35,9 +35,11 @@ def _same(a, b):
 class _Box:
     """lattice, the two cell types and one container; destroy() in the order a driver uses"""
 
-    def __init__(self, gpu, facade=False, u=(0.0, 0.0, 0.0)):
+    def __init__(self, gpu, facade=False, u=(0.0, 0.0, 0.0), periodic=PER, mask=None):
         self.P = gpu.base_parameters()
-        self.L = gpu.Lattice(N, N, N, PER, 1.0 / self.P.tau)
+        self.L = gpu.Lattice(N, N, N, periodic, 1.0 / self.P.tau)
+        if mask is not None:
+            self.L.defineBounceBack(mask)
         self.L.latticeEquilibrium(1.0, u)
         self.types = [gpu.CellType.rbc(self.P), gpu.CellType.plt(self.P)]
         self.h = gpu.HemoCell(self.L, self.P) if facade else None
@@ -56,8 +58,8 @@ class _Box:
 def box(gpu):
     made = []
 
-    def make(facade=False):
-        made.append(_Box(gpu, facade))
+    def make(facade=False, **kw):
+        made.append(_Box(gpu, facade, **kw))
         return made[-1]
     yield make
     for b in made:
@@ -130,6 +132,88 @@ def test_region_growth_carries_every_state(gpu, box):
     assert _same(rep1[n0:], np.zeros((70 * nv, 3)))
     h.iterate(2)
     assert np.isfinite(cells.positions).all()
+
+
+def _five_cells(b):
+    """One RBC and four platelets (P0..P3, at z = 12: lowest vertex at z = 9.5) whose records carry seeded force and
+    force_repulsion; v is zero except (0, 0, -8) on P1, and vertex 5 of P3 is left out, so P3 is incomplete.  Returns the five
+    cell ids, RBC first."""
+    cells = b.cells
+    assert cells.addCell(RBC, (16.0, 16.0, 18.0))
+    for x, y, _ in _grid(4):
+        assert cells.addCell(PLT, (x, y, 12.0))
+    cells.setRepulsion(K_REP, CUTOFF_UM, 1)   # the repulsion arrays exist from here on
+    ids = cells.cell_ids()
+    rec = cells.records()
+    assert rec["position"][rec["celltype"] == PLT][:, 2].min() > 9.0   # clear of a wall at z <= 5; P1's step of -8 puts it there
+    rng = np.random.default_rng(23)
+    rec["force"] = 1e-3 * rng.standard_normal((len(rec), 3))
+    rec["force_repulsion"] = 1e-3 * rng.standard_normal((len(rec), 3))
+    rec["v"] = 0.0
+    plt = rec["celltype"] == PLT
+    rec["v"][plt & (rec["cellId"] == ids[2])] = (0.0, 0.0, -8.0)
+    cells.set_records(rec[~(plt & (rec["cellId"] == ids[4]) & (rec["vertexId"] == 5))])
+    assert np.array_equal(cells.cell_ids(), ids)
+    assert cells.deletion_counts() == (0, 0, 1, 1)
+    return ids
+
+
+def test_compaction_carries_every_state(gpu, box):
+    """P1 moves into the wall below it in one advance and, in deletion mode "cell", is gone at once; the compaction that
+    follows closes the gap: every record field, the repulsion forces, the incomplete tag of P3 and its dead particle move one
+    slot down together, and the cells in front stay where they were.  The other cells have v = 0, and p + 0.0 keeps p's bits."""
+    mask = np.zeros((N, N, N), np.uint8)
+    mask[:, :, :6] = 1
+    mask[:, :, N - 1] = 1
+    b = box(periodic=(True, True, False), mask=mask)
+    cells = b.cells
+    ids = _five_cells(b)
+    nr, nv = b.types[RBC].nv, b.types[PLT].nv
+    rec0, rep0, alive0 = cells.records(), cells.repulsion_forces, cells.alive()
+    assert np.abs(rep0).max() > 0.0 and (~alive0).sum() == 1 and not alive0[nr + 3 * nv + 5]
+
+    cells.setDeletionMode("cell")
+    cells.advanceParticles(True)
+
+    stay = ~((rec0["celltype"] == PLT) & (rec0["cellId"] == ids[2]))
+    assert stay.sum() == len(rec0) - nv
+    assert _same(cells.records(), rec0[stay])
+    assert np.array_equal(cells.cell_ids(), ids[[0, 1, 3, 4]])
+    alive1 = cells.alive()
+    assert len(alive1) == nr + 3 * nv and np.array_equal(np.flatnonzero(~alive1), [nr + 2 * nv + 5])
+    assert cells.deletion_counts() == (1, 0, 1, 1)
+    stay_v = np.ones(len(alive0), bool)
+    stay_v[nr + nv:nr + 2 * nv] = False
+    assert _same(cells.repulsion_forces, rep0[stay_v])
+
+
+def test_remove_cells_fills_holes_from_the_tail(gpu, box):
+    """hcp_remove_cells takes P1 out on the device: the last cell, P3, moves into its slot with its whole state, only the
+    host's id list follows.  A platelet added afterwards arrives with zero v, force and force_repulsion."""
+    b = box()
+    cells = b.cells
+    ids = _five_cells(b)
+    nr, nv = b.types[RBC].nv, b.types[PLT].nv
+    rec0 = cells.records()
+    slots = np.array([1], dtype=np.int32)
+    gpu.check(gpu.capi.lib().hcp_remove_cells(cells.ptr, PLT, slots.ctypes.data_as(C.POINTER(C.c_int)), len(slots)))
+    assert np.array_equal(cells.cell_ids(), ids[[0, 1, 4, 3]])
+    rec1 = cells.records()
+    assert len(rec1) == len(rec0) - nv
+    assert _same(rec1[rec1["celltype"] == RBC], rec0[rec0["celltype"] == RBC])
+    for cid in ids[[1, 4, 3]]:
+        now, then = rec1[(rec1["celltype"] == PLT) & (rec1["cellId"] == cid)], rec0[(rec0["celltype"] == PLT) & (rec0["cellId"] == cid)]
+        assert len(then) == (nv - 1 if cid == ids[4] else nv) and _same(now, then)
+    assert rec1["cellId"][nr] == ids[1] and rec1["cellId"][nr + nv] == ids[4]   # P0, then P3 in the slot P1 left
+    assert np.array_equal(np.flatnonzero(~cells.alive()), [nr + nv + 5])        # with its dead particle
+
+    assert cells.addCell(PLT, (27.0, 3.0, 12.0))
+    rec2 = cells.records()
+    assert _same(rec2[:len(rec1)], rec1)
+    new = rec2[len(rec1):]
+    assert len(new) == nv and (new["celltype"] == PLT).all() and np.array_equal(new["vertexId"], np.arange(nv))
+    for f in ("v", "force", "force_repulsion"):
+        assert _same(new[f], np.zeros((nv, 3)))
 
 
 def test_slot_list_outgrows_its_staging_block(gpu, box):
