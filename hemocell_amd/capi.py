@@ -131,6 +131,16 @@ SIGNATURES = {
     "hcl_download_face_velocity": (C.c_int, [VP, C.c_int, c_double_p]),
     "hcl_dims": (C.c_int, [VP, c_int_p]),
     "hcl_mlups_bytes_per_node": (C.c_double, [VP]),
+    "hcl_interior_enable": (C.c_int, [VP, C.c_int, c_double_p]),
+    "hcl_interior_info": (C.c_int, [VP, c_int_p, c_double_p]),
+    "hcl_interior_upload_classes": (C.c_int, [VP, VP]),
+    "hcl_interior_download_classes": (C.c_int, [VP, VP]),
+    "hcp_type_set_interior_viscosity": (C.c_int, [VP, C.c_int, C.c_double]),
+    "hcp_set_interior_timescales": (C.c_int, [VP, C.c_int, C.c_int]),
+    "hcp_interior_find": (C.c_int, [VP]),
+    "hcp_interior_membrane": (C.c_int, [VP]),
+    "hcp_interior_normals": (C.c_int, [VP, C.c_int, c_double_p]),
+    "hc_debug_interior_block": (C.c_int, [C.c_int]),
     "hc_params_base": (C.c_int, [C.POINTER(Params)] + [C.c_double] * 5),
     "hcp_celltype_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Material)]),
     "hcp_celltype_create_wbc": (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(Params), C.POINTER(Material),

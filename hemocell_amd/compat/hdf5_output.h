@@ -229,6 +229,17 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
     }
     write_raw(name, C, out);
   };
+  // the node's own relaxation: omega and, for nodes inside a cell with interior viscosity, tau (0 elsewhere: the reference's
+  // interiorViscosityField, io/FluidHdf5IO.hh:335-350); without the feature every node has the lattice's omega
+  vector<double> omx(ne, (double)L->omega), taux(ne, 0.0);
+  int nclasses = 0; double class_omega[HC_MAX_VISC_CLASSES];
+  hc_check(hcl_interior_info(d, &nclasses, class_omega), "hcl_interior_info");
+  if (nclasses > 0) {
+    vector<uint8_t> cls(nn);
+    hc_check(hcl_interior_download_classes(d, cls.data()), "hcl_interior_download_classes");
+    for (size_t k = 0; k < nn; k++) if (cls[k]) { omx[plane + k] = class_omega[cls[k] - 1]; taux[plane + k] = 1.0 / class_omega[cls[k] - 1]; }
+    fill_ends(omx, 1); fill_ends(taux, 1);
+  }
   vector<double> pi;   // off-equilibrium momentum flux, fetched once if a stress or strain-rate field is asked for
   auto need_pi = [&]() {
     if (!pi.empty()) return;
@@ -250,14 +261,13 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
     else if (var == OUTPUT_DENSITY) write4("Density", 1, [&](size_t k, int) { return (float)(rho[k] * (si ? Parameters::df / (Parameters::dx * Parameters::dx) : 1.0)); });
     else if (var == OUTPUT_BOUNDARY) write4("Boundary", 1, [&](size_t k, int) { return maskx[k] ? 1.f : 0.f; });
     else if (var == OUTPUT_OMEGA)   // getDynamics().getOmega(), scaled like a stress in SI as the reference does (io/FluidHdf5IO.hh:352-372); a BounceBack node has none
-      write4("Omega", 1, [&](size_t k, int) { return (float)((bbx[k] ? 0.0 : (double)L->omega) * (si ? Parameters::df / (Parameters::dx * Parameters::dx) : 1.0)); });
+      write4("Omega", 1, [&](size_t k, int) { return (float)((bbx[k] ? 0.0 : omx[k]) * (si ? Parameters::df / (Parameters::dx * Parameters::dx) : 1.0)); });
     else if (var == OUTPUT_SHEAR_STRESS) {   // Cell::computeShearStress (io/FluidHdf5IO.hh:404-432): (omega/2 - 1) PiNeq in the bulk, zero on BounceBack nodes
       need_pi();
-      const double pre = 0.5 * (double)L->omega - 1.0;
-      write4("ShearStress", 6, [&](size_t k, int cidx) { return (float)(bbx[k] ? 0.0 : pre * pi[6 * k + cidx] * (si ? Parameters::df / (Parameters::dx * Parameters::dx) : 1.0)); });
+      write4("ShearStress", 6, [&](size_t k, int cidx) { return (float)(bbx[k] ? 0.0 : (0.5 * omx[k] - 1.0) * pi[6 * k + cidx] * (si ? Parameters::df / (Parameters::dx * Parameters::dx) : 1.0)); });
     } else if (var == OUTPUT_STRAIN_RATE) {   // computeStrainRateFromStress (io/FluidHdf5IO.hh:497-552): -omega / (2 cs2 rho) PiNeq
       need_pi();
-      write4("StrainRate", 6, [&](size_t k, int cidx) { return (float)(bbx[k] ? 0.0 : -1.5 * (double)L->omega / rho[k] * pi[6 * k + cidx] * (si ? 1.0 / Parameters::dt : 1.0)); });
+      write4("StrainRate", 6, [&](size_t k, int cidx) { return (float)(bbx[k] ? 0.0 : -1.5 * omx[k] / rho[k] * pi[6 * k + cidx] * (si ? 1.0 / Parameters::dt : 1.0)); });
     } else if (var == OUTPUT_SHEAR_RATE) {   // central differences of computeVelocity (io/FluidHdf5IO.hh:434-495); row a*3+b = d u_a / d x_b
       vector<float> out((size_t)(Nx * Ny * Nz) * 9); size_t o = 0;
       for (plint z = -1; z <= nz; z++) for (plint y = -1; y <= ny; y++) for (plint x = -1; x <= nx; x++) {
@@ -288,7 +298,9 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
         if (si) for (float &v : out) v *= (float)cf.volumeFractionOfLspPerNode;
         write_raw("CellDensity_" + cf.name, 1, out);
       }
-    } else if (var == OUTPUT_BINDING_SITES || var == OUTPUT_INTERIOR_POINTS) {   // neither feature exists here: what the reference writes without them (:306-350)
+    } else if (var == OUTPUT_INTERIOR_POINTS && nclasses > 0) {   // tau at the tagged nodes, 0 elsewhere (:335-350)
+      write4("InteriorPoints", 1, [&](size_t k, int) { return (float)taux[k]; });
+    } else if (var == OUTPUT_BINDING_SITES || var == OUTPUT_INTERIOR_POINTS) {   // the feature does not exist here / is not in use: what the reference writes then (:306-350)
       pcout << (var == OUTPUT_BINDING_SITES ? "(FluidHdf5) (Error) OUTPUT_BINDING_SITES requested, but binding sites not used, outputting a zero field"
                                             : "(FluidHdf5) (Error) OUTPUT_INTERIOR_POINTS requested, but interior viscosity not used, outputting a zero field") << endl;
       write_raw(var == OUTPUT_BINDING_SITES ? "BindingSites" : "InteriorPoints", 1, vector<float>((size_t)(Nx * Ny * Nz), 0.f));

@@ -514,8 +514,11 @@ class HemoCellFields {
   inline void solidifyCells() { refuse("solidify mechanics (solidifyCells)"); }
   inline void prepareSolidification() { refuse("solidify mechanics (prepareSolidification)"); }
   inline void populateBindingSites(plb::Box3D * = nullptr) { refuse("binding sites (populateBindingSites)"); }
-  inline void findInternalParticleGridPoints() { refuse("interior viscosity (findInternalParticleGridPoints)"); }
-  inline void internalGridPointsMembrane() { refuse("interior viscosity (internalGridPointsMembrane)"); }
+  // core/hemoCellParticleField.cpp:745-807 on the device (csrc/interior.hip); hc_iterate runs them at these cadences
+  unsigned int interiorViscosityTimescale = 1, interiorViscosityEntireGridTimescale = 1;
+  bool interiorViscosity = false;   // a bound type has enableInteriorViscosity (global.enableInteriorViscosity of the reference)
+  inline void findInternalParticleGridPoints() { hc_check(hcp_interior_find(device()), "hcp_interior_find"); }
+  inline void internalGridPointsMembrane() { hc_check(hcp_interior_membrane(device()), "hcp_interior_membrane"); }
   inline void createCEPACfield() { refuse("the CEPAC field (createCEPACfield)"); }
 };
 
@@ -660,7 +663,28 @@ class HemoCell {
   void refuse(const char *what) { hlog << "(HemoCell) (GPU backend) " << what << " is not part of this back end (DESIGN.md section 0), exiting ..." << endl; std::exit(1); }
   void enableSolidifyMechanics(string) { refuse("solidify mechanics (enableSolidifyMechanics)"); }
   void setSolidifyTimeScaleSeperation(unsigned int) { refuse("solidify mechanics (setSolidifyTimeScaleSeperation)"); }
-  void setInteriorViscosityTimeScaleSeperation(unsigned int, unsigned int) { refuse("interior viscosity (setInteriorViscosityTimeScaleSeperation)"); }
+  void setInteriorViscosityTimeScaleSeperation(unsigned int separation, unsigned int separation_entire_grid) {   // core/hemoCell.cpp:404-410
+    hlog << "(HemoCell) (Interior Viscosity Timescale Seperation) Setting seperation to " << separation << " timesteps" << endl;
+    hlog << "(HemoCell) (Interior Viscosity Timescale Seperation) Setting entire grid refresh to " << separation_entire_grid << " timesteps" << endl;
+    flush();
+    cellfields->interiorViscosityTimescale = separation; cellfields->interiorViscosityEntireGridTimescale = separation_entire_grid;
+  }
+  // core/hemoCell.cpp:614-620, 635-643, where the settings are used: before the first queued iteration
+  void interiorViscositySanity(hc_cells *c) {
+    if (!cellfields->interiorViscosity) return;
+    const unsigned int every = cellfields->interiorViscosityTimescale, grid = cellfields->interiorViscosityEntireGridTimescale, pv = cellfields->particleVelocityUpdateTimescale;
+    if (every == 0 || grid == 0 || grid % pv != 0 || every % pv != 0) {
+      hlog << "(HemoCell) Error, Velocity timescale separation cannot divide this interior viscosity timescale separation, exiting ..." << endl;
+      std::exit(1);
+    }
+    if (!interiorViscosityWarned) {
+      if (grid == 1) hlog << "(HemoCell) WARNING: Interior viscosity (entire grid) timescale is 1, did you forget to call hemocell->setInteriorViscosityTimescaleSeparation()?" << endl;
+      if (every == 1) hlog << "(HemoCell) WARNING: Interior viscosity timescale is 1, did you forget to call hemocell->setInteriorViscosityTimescaleSeparation()?" << endl;
+      interiorViscosityWarned = true;
+    }
+    hc_check(hcp_set_interior_timescales(c, (int)every, (int)grid), "hcp_set_interior_timescales");
+  }
+  bool interiorViscosityWarned = false;
   void setCEPACOutputs(vector<int>) { refuse("the CEPAC field (setCEPACOutputs)"); }
   void checkExitSignals() {}                                   // core/hemoCell.cpp:300: SIGINT / SIGTERM handling of the reference's run scripts
   void sanityCheck() { sanityCheckDone = true; }               // the facade's own checks run where a setting is used
@@ -705,6 +729,7 @@ class HemoCell {
       if (boundaryRepulsionEnabled && !boundaryRepulsionPushed) { hc_check(hcp_set_boundary_repulsion(c, boundaryRepulsionConstant_, boundaryRepulsionCutoff_, (int)boundaryRepulsionTimescale), "hcp_set_boundary_repulsion"); boundaryRepulsionPushed = true; }
       if (repulsionEnabled && !repulsionPushed) { hc_check(hcp_set_repulsion(c, repulsionConstant_, repulsionCutoff_, (int)repulsionTimescale), "hcp_set_repulsion"); repulsionPushed = true; }
       lattice->device();
+      interiorViscositySanity(c);
       queued_timescale = cellfields->particleVelocityUpdateTimescale;
     }
     const bool particle_step = iter % cellfields->particleVelocityUpdateTimescale == 0;
@@ -810,6 +835,11 @@ inline void HemoCellField::create_device_type(int model) {
     volume = m["MaterialModel"]["Volume"].read<T>();
     volumeFractionOfLspPerNode = (volume / numVertex) / std::pow(Parameters::dx * 1e6, 3);
   } catch (std::invalid_argument &) { hlog << "(HemoCell) (WARNING) (AddCellType) Volume of celltype " << name << " not present, volume set to zero" << endl; }
+  try { interiorViscosityTau = m["MaterialModel"]["viscosityRatio"].read<T>() * (param::tau - 0.5) + 0.5; } catch (std::invalid_argument &) {}   // :100-101
+  try {   // :102-116 (the library is always an INTERIOR_VISCOSITY build); the type is marked on the device when it is bound
+    doInteriorViscosity = m["MaterialModel"]["enableInteriorViscosity"].read<bool>();
+    if (doInteriorViscosity) hlog << "(HemoCell) (AddCellType) (" << name << ") Enabling interior viscosity" << endl;
+  } catch (std::invalid_argument &) {}
 }
 
 // mechanics/commonCellConstants.cpp:70-409: the tables are built by the library (csrc/mesh.cpp) together with the mesh;
@@ -857,7 +887,11 @@ inline hc_cells *HemoCellFields::device() {
         hlog << "(HemoCell) (GPU backend) cell type " << f->name << " installs its own IBM kernelMethod; only interpolationCoefficientsPhi2 (core/immersedBoundaryMethod.h:62-138) runs on the device. Exiting." << endl;
         std::exit(1);
       }
-      hc_check(hcp_add_type(dev, f->dev, (int)f->timescale, nullptr), "hcp_add_type");
+      int index = -1;
+      hc_check(hcp_add_type(dev, f->dev, (int)f->timescale, &index), "hcp_add_type");
+      // core/hemoCellField.cpp:102-116: the type's nodes relax with omega = 1 / interiorViscosityTau (the library refuses other
+      // models than RbcHighOrderModel, slabs, open boundaries, Lees-Edwards and a pre-inlet beside it, each with its message)
+      if (f->doInteriorViscosity) { hc_check(hcp_type_set_interior_viscosity(dev, index, f->interiorViscosityTau), "hcp_type_set_interior_viscosity"); interiorViscosity = true; }
     }
     types_bound = true;
   }
@@ -1022,6 +1056,16 @@ inline void HemoCell::saveCheckPoint() {
   if (nrec) hc_check(hcp_download_records(c, rec.data(), nrec), "hcp_download_records");
   o.write((const char *)&nrec, sizeof(long));
   o.write((const char *)rec.data(), (std::streamsize)(rec.size() * sizeof(rec[0])));
+  // interior viscosity: the class byte of every node (the reference saves its interiorViscosityField,
+  // helper/interiorViscosity.cpp:90-110); the block is absent from checkpoints of runs without the feature
+  int nclasses = 0; hc_check(hcl_interior_info(d, &nclasses, nullptr), "hcl_interior_info");
+  if (nclasses > 0) {
+    vector<uint8_t> cls(n);
+    hc_check(hcl_interior_download_classes(d, cls.data()), "hcl_interior_download_classes");
+    const long ncls = (long)n;
+    o.write((const char *)&ncls, sizeof(long));
+    o.write((const char *)cls.data(), (std::streamsize)cls.size());
+  }
   o.close();
   if (!o) { hlog << "(HemoCell) (saveCheckPoint) could not write " << tmp_name << endl; std::exit(1); }
   rename(final_name.c_str(), (final_name + ".old").c_str());
@@ -1079,6 +1123,18 @@ inline void HemoCell::loadCheckPoint() {
   // core/hemoCellFields.cpp:272-274: load, syncEnvelopes, deleteIncompleteCells -- a checkpoint written while a cell had lost
   // particles at a wall (removeParticles(1)) holds that cell incomplete
   hc_check(hcp_delete_incomplete_cells(c, nullptr), "hcp_delete_incomplete_cells");
+  {   // the class field of a run with interior viscosity (binding the types above has enabled it on the lattice)
+    int nclasses = 0; hc_check(hcl_interior_info(d, &nclasses, nullptr), "hcl_interior_info");
+    long ncls = 0; in.read((char *)&ncls, sizeof(long));
+    const bool present = in.good() && ncls == (long)n;
+    if (nclasses > 0 && !present) { hlog << "(HemoCell) (loadCheckPoint) the checkpoint holds no interior-viscosity field for this case" << endl; std::exit(1); }
+    if (present) {
+      vector<uint8_t> cls(n);
+      in.read((char *)cls.data(), (std::streamsize)cls.size());
+      if (!in.good()) truncated();
+      if (nclasses > 0) hc_check(hcl_interior_upload_classes(d, cls.data()), "hcl_interior_upload_classes");
+    }
+  }
   long nct = 0; hcp_counts(c, nullptr, &nct, nullptr);
   cellfields->number_of_cells = (int)nct;
   iter = (unsigned int)hdr[1];
@@ -1306,7 +1362,11 @@ inline void HemoCell::writeOutput() {
 }
 
 // ------------------------------------------------------------------ helper/hemoCellStretch.h
-class HemoCellStretch {
+// scale is a static member in the reference (helper/hemoCellStretch.h:55; cases/stretchCell_interior_viscosity assigns
+// HemoCellStretch::scale): a static of a class template, so that this header alone defines it
+template <class Tag> struct HemoCellStretchStatics { static T scale; };
+template <class Tag> T HemoCellStretchStatics<Tag>::scale = 1.0;
+class HemoCellStretch : public HemoCellStretchStatics<void> {
  public:
   HemoCellStretch(HemoCellField &cellfield_, unsigned int n_forced_lsps_, T external_force_) : cellfield(cellfield_) {
     HemoCellFields &cf = *cellfield.cellFields;
@@ -1330,7 +1390,7 @@ class HemoCellStretch {
   }
   HemoCellField &cellfield;
   vector<plint> lower_lsps, upper_lsps;
-  unsigned int n_forced_lsps = 0; T external_force = 0; T scale = 1.0;
+  unsigned int n_forced_lsps = 0; T external_force = 0;
 };
 
 // ------------------------------------------------------------------ helper/voxelizeDomain.cpp:76-152 replacement for synthetic pipes

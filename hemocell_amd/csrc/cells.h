@@ -82,6 +82,13 @@ struct hc_cells {
   double e_share = 4.0;
   MappedBuf<int> h_env_viol;
   std::vector<long> slab_rejected;   // (type, cell id) pairs hcp_add_cell rejected at a wall on this slab, until hcp_slab_sync_placement
+  // interior viscosity (interior.hip): the lattice class of each type (0: the type is not marked), the cadences of the two
+  // passes inside hc_iterate, and the rank of every cell of the marked types in ascending (cell id, type) order -- [type's
+  // offset + slot], formed and staged again only when the ids changed
+  int visc_class[8] = {0};
+  int visc_every = 1, visc_grid_every = 1;
+  Staged<int> visc_rank; std::vector<long> visc_ids_seen;   // the ids (per marked type, behind a separator) the staged ranks were formed from
+  bool visc_on() const { for (int t = 0; t < ntypes; t++) if (visc_class[t]) return true; return false; }
   long n_deleted = 0;              // cells removed entirely
   long n_particles_deleted = 0;    // single particles removed (reference mode), including those of cells removed later
 };
@@ -203,6 +210,7 @@ TypeArrays vert_arrays(hc_cells *C, int t);
 int ensure_rep(hc_cells *C);       // the three force_repulsion arrays, zeroed, once a repulsion is enabled and the vertex arrays exist
 // stage a small host int array on the device in a persistent scratch slot (through a pinned block; stream ordered)
 int stage_ints(hc_cells *C, int which, int **d, const int *h, int n);
+int stage_ints(Staged<int> &s, int **d, const int *h, int n);   // the same through a staging block of the caller's
 // the transposing copies between a staging [n][3] and three device arrays, from element `first` on (blocking)
 int upload_xyz(DevBuf<double> dst[3], long first, const double *src, long n);
 int download_xyz(double *dst, const DevBuf<double> src[3], long first, long n);

@@ -198,8 +198,8 @@ TypeArrays vert_arrays(hc_cells *C, int t) {
 // stage a small host int array on the device in a persistent scratch slot.  The source is copied into a pinned block
 // first, so the caller's array may be a temporary and the copy really is asynchronous; the copy and every later use are
 // ordered on the stream in use.  The slot's event tells when the pinned block may be rewritten.
-int stage_ints(hc_cells *C, int which, int **d, const int *h, int n) {
-  Staged<int> &s = C->iscratch[which];
+int stage_ints(hc_cells *C, int which, int **d, const int *h, int n) { return stage_ints(C->iscratch[which], d, h, n); }
+int stage_ints(Staged<int> &s, int **d, const int *h, int n) {
   if (!s.ev) { const int rc = s.ev.create(); if (rc != HC_OK) return rc; }
   else HC_HIP(hipEventSynchronize(s.ev));   // the previous copy has left the pinned block (normally long ago)
   if ((size_t)n > s.cap()) {
@@ -819,6 +819,13 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
   // Deletions (core/hemoCellParticleField.cpp:566-588) happen on the device inside the advance kernel at EVERY iteration,
   // whatever deletion_check_every says; that argument is only the cadence at which the host looks (without waiting) whether
   // gone cells can be compacted away.
+  // Interior viscosity (core/hemoCell.cpp:347-357): the two passes follow the mechanics of their iterations and write the
+  // lattice's class field, which every collide reads.  Their cadences are multiples of particle_timescale
+  // (core/hemoCell.cpp:614-620), so such an iteration is a particle step and runs on the main timeline alone; the fork
+  // below checks that itself instead of relying on it.
+  const bool visc = C->visc_on();
+  if (visc) HC_REQUIRE(C->visc_every % particle_timescale == 0 && C->visc_grid_every % particle_timescale == 0,
+                       "hc_iterate: the velocity-update timescale must divide both interior-viscosity timescales (hcp_set_interior_timescales)");
   struct ForkGuard { ~ForkGuard() { if (hc::forked()) hc::join(); else hc::route(0); } } guard;   // error paths leave one timeline behind
   const bool may_overlap = g_overlap && !C->rep_enabled && !C->brep_enabled;
   bool spread_done = false;
@@ -834,7 +841,8 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     }
     spread_done = false;
     const bool particle_step = it % particle_timescale == 0;
-    const bool overlap = may_overlap && !particle_step && s + 1 < n;
+    const bool visc_grid = visc && it % C->visc_grid_every == 0, visc_membrane = visc && it % C->visc_every == 0;
+    const bool overlap = may_overlap && !particle_step && !visc_grid && !visc_membrane && s + 1 < n;
     if (overlap && (rc = hc::fork()) != HC_OK) return rc;
     if ((rc = hcl_collide_stream_part(L, 0)) != HC_OK) return rc;               // :317
     hcl_step_end(L);
@@ -850,6 +858,11 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
       if (g_spread_beside) { if ((rc = hcp_spread(C, force_limit)) != HC_OK) return rc; spread_done = true; }   // :313 of iteration it + 1
       if ((rc = hc::join()) != HC_OK) return rc;
     }
+    if (visc_grid) {                                                            // :347-352; never forked (see above)
+      if ((rc = hcp_delete_incomplete_cells(C, nullptr)) != HC_OK) return rc;   // the one host wait of an entire-grid pass
+      if ((rc = hcp_interior_find(C)) != HC_OK) return rc;
+    }
+    if (visc_membrane) { if ((rc = hcp_interior_membrane(C)) != HC_OK) return rc; }   // :353-357
     *iter = it + 1;                                                             // :374 (force zeroing is fused into the collide kernel)
     if (!overlap && (it + 1) % deletion_check_every == 0 && s + 1 < n) { if ((rc = poll_deletions(C, true)) != HC_OK) return rc; }   // on the main timeline only
   }

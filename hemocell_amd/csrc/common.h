@@ -102,7 +102,8 @@ template <class T> struct Staged {
 };
 
 // per-kernel hipEvent timing (hc_profile_*)
-enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them
+enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
+void prof_count(int kernel);   // one more launch of `kernel`, without a time (while profiling is on)
 struct ProfScope {
   int k; bool on;
   hipEvent_t a, b;
@@ -288,6 +289,11 @@ struct hc_lattice {
   hc::DevBuf<double> ob_val;        // [ob_cap][4], device
   int ob_n = 0, ob_cap = 0;
   long ob_epoch = 0;                // counts hcl_open_boundary_clear: a pre-inlet coupling (hc_preinlet) made before one is stale
+  // Interior viscosity (hcl_interior_enable): one class byte per node, 0 = omega, k >= 1 = visc_omega[k - 1].  Allocated only
+  // once enabled; the collide runs its interior-viscosity instantiation while visc_n > 0.  The passes of interior.hip write it.
+  hc::DevBuf<uint8_t> visc_class;   // [npad], device
+  int visc_n = 0; double visc_omega[HC_MAX_VISC_CLASSES];
+  hc::DevBuf<unsigned long long> visc_vote;   // [npad] scratch of the interior passes: 0 between passes
   hc::DevBuf<int> ob_list;      // staging of hcl_plane_velocity's node list
   hc::DevBuf<double> ob_out;    // ... and of its output when the caller's buffer is on the host
 };

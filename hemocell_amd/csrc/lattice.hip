@@ -21,6 +21,7 @@
 #include "common.h"
 #include "comm.h"
 #include <algorithm>
+#include <cstring>
 #include <memory>
 #include <type_traits>
 
@@ -59,6 +60,14 @@ struct OpenArgs : LatArgs {
   const double *ob_val;  // [slot][4] {u_x, u_y, u_z, rho}
 };
 template <bool OPEN> using Args = std::conditional_t<OPEN, OpenArgs, LatArgs>;
+
+// the arguments of the interior-viscosity instantiation of the collide (launch_collide picks it while visc_n > 0), by the same
+// rule: the class byte of every node and the omegas of the classes 1 .. HC_MAX_VISC_CLASSES
+struct ViscArgs : LatArgs {
+  const uint8_t *visc_class;               // [npad]: 0 = the lattice's omega, k = omega_class[k - 1]
+  double omega_class[HC_MAX_VISC_CLASSES];
+};
+template <bool OPEN, bool VISC> using CollideArgs = std::conditional_t<VISC, ViscArgs, Args<OPEN>>;
 
 // uniform body force, or that of the last region holding the node
 __device__ __forceinline__ void body_at(const LatArgs &a, int x, int y, int z, double &bx, double &by, double &bz) {
@@ -124,9 +133,12 @@ __device__ __forceinline__ void collide_guo(double f[HC_Q], double Fx, double Fy
 }
 
 // OPEN: the instantiation for lattices with Zou-He nodes (launch_collide picks it while ob_n > 0); the other instantiations
-// compile to the same code as before it existed
-template <bool REGIONS, bool OPEN = false>
-__global__ __launch_bounds__(256) void collide_stream_kernel(Args<OPEN> a) {
+// compile to the same code as before it existed.  VISC: the instantiation for lattices with interior viscosity
+// (hcl_interior_enable), under the same rule; it differs in the omega a fluid node relaxes with and in nothing else.  The two
+// never combine (hcl_interior_enable and the open-boundary calls refuse each other).
+template <bool REGIONS, bool OPEN = false, bool VISC = false>
+__global__ __launch_bounds__(256) void collide_stream_kernel(CollideArgs<OPEN, VISC> a) {
+  static_assert(!(OPEN && VISC), "open boundaries and interior viscosity do not share a lattice");
   // thread -> (y,z) through the active-span map of this plane: consecutive threads walk the spans of
   // consecutive rows, so every lane of every wave (except the last of a plane) has a live node
   const int x = a.x_begin + (int)blockIdx.y + ((int)blockIdx.y >= a.x_split ? a.x_jump : 0);
@@ -140,6 +152,8 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(Args<OPEN> a) {
   const int p = y * a.nz + z;
   const long node = (long)(x + HALO) * a.xs + p;
   const uint8_t m = a.mask[node];
+  uint8_t vclass = 0;   // the class byte travels with the mask byte
+  if constexpr (VISC) vclass = a.visc_class[node];
   if (m == 2) return;   // solid node with no fluid neighbour: inert under full-way bounce-back
   const Nbr n = neighbours(a, x, y, z);
   // the node's IBM force record (24 B) is loaded together with the populations, in one round trip.  This also keeps the
@@ -179,7 +193,12 @@ __global__ __launch_bounds__(256) void collide_stream_kernel(Args<OPEN> a) {
       const int code = a.ob_code[node];
       if (code >= 0) zou_he_node(f, code, a.ob_val);
     }
-    collide_guo(f, Fx, Fy, Fz, a.omega);
+    double omega = a.omega;
+    if constexpr (VISC) {   // a chain of selects over the kernel arguments: no indexed access, no scratch
+#pragma unroll
+      for (int k = 0; k < HC_MAX_VISC_CLASSES; k++) omega = vclass == k + 1 ? a.omega_class[k] : omega;
+    }
+    collide_guo(f, Fx, Fy, Fz, omega);
   }
 #pragma unroll
   // streamed once and read again only after 5 GB of other traffic: non-temporal stores keep the lines out of the way
@@ -520,6 +539,15 @@ OpenArgs open_of(const hc_lattice *L, const LatArgs &a) {
   return o;
 }
 
+// the arguments of the interior-viscosity instantiation of the collide
+ViscArgs visc_of(const hc_lattice *L, const LatArgs &a) {
+  ViscArgs v;
+  static_cast<LatArgs &>(v) = a;
+  v.visc_class = L->visc_class;
+  for (int k = 0; k < HC_MAX_VISC_CLASSES; k++) v.omega_class[k] = k < L->visc_n ? L->visc_omega[k] : L->omega;
+  return v;
+}
+
 dim3 plane_grid(const hc_lattice *L, int nplanes) { return dim3((unsigned)((L->plane + 255) / 256), (unsigned)nplanes, 1); }
 
 int ensure_scratch(hc_lattice *L, size_t doubles) { return L->scratch.reserve(doubles); }
@@ -597,6 +625,14 @@ int launch_collide(hc_lattice *L, int x_begin, int nplanes, int x2 = 0, int n2 =
   if (n2 > 0) { a.x_split = nplanes; a.x_jump = x2 - (x_begin + nplanes); }
   const unsigned ny = (unsigned)(nplanes + n2);
   const dim3 grid((unsigned)((L->max_active + 255) / 256), ny, 1);
+  if (L->visc_n > 0) {   // never together with open-boundary nodes (hcl_interior_enable, ob_add)
+    hc::prof_count(hc::PK_COLLIDE_VISC);   // which instantiation ran: a count, no events of its own inside the caller's collide_stream bracket
+    const ViscArgs v = visc_of(L, a);
+    if (L->regions.n) hipLaunchKernelGGL((collide_stream_kernel<true, false, true>), grid, dim3(256), 0, hc::stream(), v);
+    else hipLaunchKernelGGL((collide_stream_kernel<false, false, true>), grid, dim3(256), 0, hc::stream(), v);
+    HC_HIP(hipGetLastError());
+    return HC_OK;
+  }
   launch_open(L, a, [&](auto open, const auto &args) {
     constexpr bool OPEN = decltype(open)::value;
     if (L->regions.n) hipLaunchKernelGGL((collide_stream_kernel<true, OPEN>), grid, dim3(256), 0, hc::stream(), args);
@@ -889,6 +925,7 @@ int hcl_set_lees_edwards(hc_lattice *L, double v_top, double v_bottom) {
   HC_REQUIRE(L->periodic[0] && L->periodic[1] && L->periodic[2], "hcl_set_lees_edwards: the lattice must be periodic on all three axes");
   HC_REQUIRE(L->nz >= 4, "hcl_set_lees_edwards: nz must be at least 4");
   HC_REQUIRE(L->ob_n == 0, "hcl_set_lees_edwards: the lattice has open-boundary nodes; open boundaries and Lees-Edwards do not combine");
+  HC_REQUIRE(L->visc_n == 0, "hcl_set_lees_edwards: the lattice has interior viscosity enabled; interior viscosity and Lees-Edwards do not combine");
   if (!le_layers_fluid(L, L->hmask.data(), L->xs)) {
     hc::set_error("hcl_set_lees_edwards: the layers z = 0, 1, nz-2 and nz-1 must hold fluid nodes only");
     return HC_ERR_STATE;
@@ -976,6 +1013,8 @@ static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int
   // The Lees-Edwards pass rewrites the post-stream populations of its z layers from plain moments of gathered populations; what
   // it should read and leave on a node whose populations the collide completes is not defined, so the two do not share a lattice
   HC_REQUIRE(!L->le_on, who + ": the lattice has a Lees-Edwards boundary; open boundaries and Lees-Edwards do not combine");
+  // the open-boundary and the interior-viscosity collide are two instantiations; no kernel does both
+  HC_REQUIRE(L->visc_n == 0, who + ": the lattice has interior viscosity enabled; interior viscosity and open boundaries do not combine");
   // a node holds one slot: declaring it again (in this call or an earlier one) would orphan the first slot and let the second
   // declaration win silently, so it is refused and nothing is changed
   {
@@ -1158,6 +1197,7 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
   HC_REQUIRE(out && pre && domain && n >= 0 && (n == 0 || pre_idx), "hcl_preinlet_create: bad arguments");
   HC_REQUIRE(axis >= 0 && axis <= 2, "hcl_preinlet_create: axis must be 0, 1 or 2");
   HC_REQUIRE(pre->n_slabs == 1, "hcl_preinlet_create: needs n_slabs = 1 on the pre-inlet lattice");
+  HC_REQUIRE(pre->visc_n == 0 && domain->visc_n == 0, "hcl_preinlet_create: a lattice has interior viscosity enabled; interior viscosity and a pre-inlet do not combine");
   // a slab domain: the inlet plane of an x direction lies on one rank, whose local slots these are; a y or z plane would span the ranks
   HC_REQUIRE(domain->n_slabs == 1 || axis == 0, "hcl_preinlet_create: axis 1 and 2 need n_slabs = 1 on the domain; a slab domain is coupled along x only (axis 0)");
   HC_REQUIRE(pre_plane >= 0 && pre_plane < axis_extent(pre, axis), "hcl_preinlet_create: plane outside the pre-inlet lattice");
@@ -1205,6 +1245,56 @@ int hcl_preinlet_destroy(hc_preinlet *P) {
   if (!P) return HC_OK;
   hipStreamSynchronize(hc::stream());
   delete P;
+  return HC_OK;
+}
+
+// ---- interior viscosity: the per-node class field of the collide's VISC instantiation
+int hcl_interior_enable(hc_lattice *L, int n_classes, const double *omega) {
+  HC_REQUIRE(L && omega, "hcl_interior_enable: null pointer");
+  HC_REQUIRE(n_classes >= 1 && n_classes <= HC_MAX_VISC_CLASSES, "hcl_interior_enable: the number of classes must be 1 .. HC_MAX_VISC_CLASSES");
+  for (int k = 0; k < n_classes; k++) HC_REQUIRE(omega[k] > 0.0 && omega[k] < 2.0, "hcl_interior_enable: every omega must be in (0,2)");
+  HC_REQUIRE(L->n_slabs == 1, "hcl_interior_enable: interior viscosity needs the whole domain on one GPU (n_slabs = 1)");
+  HC_REQUIRE(L->ob_n == 0, "hcl_interior_enable: the lattice has open-boundary nodes; interior viscosity and open boundaries do not combine");
+  HC_REQUIRE(!L->le_on, "hcl_interior_enable: the lattice has a Lees-Edwards boundary; interior viscosity and Lees-Edwards do not combine");
+  if (!L->visc_class) {   // a second call changes the omegas and keeps the field
+    const int rc = L->visc_class.reserve(L->npad); if (rc != HC_OK) return rc;
+    HC_HIP(hipMemsetAsync(L->visc_class, 0, L->npad, hc::stream()));
+    HC_HIP(hipStreamSynchronize(hc::stream()));
+  }
+  for (int k = 0; k < n_classes; k++) L->visc_omega[k] = omega[k];
+  L->visc_n = n_classes;
+  return HC_OK;
+}
+
+int hcl_interior_info(const hc_lattice *L, int *n_classes, double *omega) {
+  HC_REQUIRE(L && n_classes, "hcl_interior_info: null pointer");
+  *n_classes = L->visc_n;
+  if (omega) for (int k = 0; k < L->visc_n; k++) omega[k] = L->visc_omega[k];
+  return HC_OK;
+}
+
+int hcl_interior_upload_classes(hc_lattice *L, const uint8_t *classes) {
+  HC_REQUIRE(L && classes, "hcl_interior_upload_classes: null pointer");
+  if (L->visc_n == 0) { hc::set_error("hcl_interior_upload_classes: interior viscosity is not enabled (hcl_interior_enable)"); return HC_ERR_STATE; }
+  std::vector<uint8_t> h(L->npad, 0);   // device numbering; halo planes and padding stay class 0
+  for (int x = 0; x < L->nx; x++)
+    for (size_t p = 0; p < L->plane; p++) {
+      const uint8_t c = classes[(size_t)x * L->plane + p];
+      HC_REQUIRE(c <= L->visc_n, "hcl_interior_upload_classes: a class exceeds the number of enabled classes");
+      h[(size_t)(x + HALO) * L->xs + p] = c;
+    }
+  HC_HIP(hipMemcpyAsync(L->visc_class, h.data(), L->npad, hipMemcpyHostToDevice, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  return HC_OK;
+}
+
+int hcl_interior_download_classes(hc_lattice *L, uint8_t *classes) {
+  HC_REQUIRE(L && classes, "hcl_interior_download_classes: null pointer");
+  if (L->visc_n == 0) { hc::set_error("hcl_interior_download_classes: interior viscosity is not enabled (hcl_interior_enable)"); return HC_ERR_STATE; }
+  std::vector<uint8_t> h(L->npad);
+  HC_HIP(hipMemcpyAsync(h.data(), L->visc_class, L->npad, hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  for (int x = 0; x < L->nx; x++) std::memcpy(classes + (size_t)x * L->plane, h.data() + (size_t)(x + HALO) * L->xs, L->plane);
   return HC_OK;
 }
 
@@ -1345,7 +1435,7 @@ int hcl_halo_unpack(hc_lattice *L, int side, int width, const double *dev_buf) {
 double hcl_mlups_bytes_per_node(const hc_lattice *L) {
   // 19 reads + 19 writes of fp64 populations and 1 mask byte; with membrane cells bound to the lattice also
   // 3 reads of the IBM force and 3 zeroing writes (304 B fluid only, 353 B coupled)
-  return 19 * 8 * 2 + 1 + ((L && L->ibm) ? 3 * 8 * 2 : 0);
+  return 19 * 8 * 2 + 1 + ((L && L->ibm) ? 3 * 8 * 2 : 0) + ((L && L->visc_n) ? 1 : 0);   // and the class byte with interior viscosity
 }
 
 }  // extern "C"

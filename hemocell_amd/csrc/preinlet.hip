@@ -542,6 +542,8 @@ int hc_preinlet_iterate(hc_preinlet *F, hc_preinlet_cells *X, long *iter, int n,
   HC_REQUIRE((F != nullptr) == (X->pre != nullptr), "hc_preinlet_iterate: bad arguments (the fluid handle is null exactly on the ranks of a slab handle that hold no pre-inlet)");
   HC_REQUIRE(cells_every >= 1, "hc_preinlet_iterate: cells_every must be >= 1");
   HC_REQUIRE(particle_timescale >= 1 && deletion_check_every >= 1, "hc_preinlet_iterate: timescales must be >= 1");
+  // an injected cell would arrive with untagged nodes inside it, and the pre-inlet's own field is not built
+  HC_REQUIRE(X->dom->L->visc_n == 0 && !(X->pre && X->pre->L->visc_n), "hc_preinlet_iterate: a lattice has interior viscosity enabled; interior viscosity and a pre-inlet do not combine");
   for (int s = 0; s < n; s++) {
     int rc;
     long a = *iter, b = *iter;

@@ -349,6 +349,31 @@ class Lattice:
     def bytes_per_node(self):
         return float(self.lib.hcl_mlups_bytes_per_node(self.ptr))
 
+    # interior viscosity (INTERIOR_VISCOSITY builds of the reference): a class byte per node picks the omega a fluid node
+    # relaxes with -- 0 the lattice's, k >= 1 omegas[k - 1]
+    def enableInteriorViscosity(self, omegas):
+        oo = np.ascontiguousarray(omegas, dtype=np.float64).reshape(-1)
+        check(self.lib.hcl_interior_enable(self.ptr, len(oo), dptr(oo)))
+
+    def interiorViscosityOmegas(self):
+        """the omegas of the classes 1 .. n; empty while the feature is off"""
+        n = C.c_int()
+        oo = np.zeros(7)
+        check(self.lib.hcl_interior_info(self.ptr, C.byref(n), dptr(oo)))
+        return oo[:n.value].copy()
+
+    def setInteriorClasses(self, classes):
+        cc = np.ascontiguousarray(classes, dtype=np.uint8)
+        if cc.size != self.n:
+            raise HcError("classes must have %d entries, got %d" % (self.n, cc.size))
+        check(self.lib.hcl_interior_upload_classes(self.ptr, cc.ctypes.data))
+
+    def interiorClasses(self):
+        """uint8 [nx][ny][nz]: the class of every node"""
+        out = np.empty((self.nx, self.ny, self.nz), dtype=np.uint8)
+        check(self.lib.hcl_interior_download_classes(self.ptr, out.ctypes.data))
+        return out
+
     def destroy(self):
         if self.ptr:
             check(self.lib.hcl_destroy(self.ptr))
@@ -628,8 +653,11 @@ class CellType:
     """hemocell.addCellType<Mechanics>(name, constructType) for one type."""
 
     def __init__(self, P, model, shape, radius, min_triangles, kLink, kArea, kVolume, kBend, eta_m=0.0,
-                 aspect_ratio=0.3, inner_edges=None, wbc=None, kInnerLink=None, stl=None, ex=False):
-        """wbc: (kInnerRigid, kCytoskeleton, coreRadius, radius) in SI units, for MODEL_WBC_HO only;
+                 aspect_ratio=0.3, inner_edges=None, wbc=None, kInnerLink=None, stl=None, ex=False,
+                 interior_viscosity=False, viscosity_ratio=None):
+        """interior_viscosity, viscosity_ratio: <enableInteriorViscosity> and <viscosityRatio> of the cell XML
+        (core/hemoCellField.cpp:100-112): Cells.addCellType then marks the type with tau_int = ratio (tau - 0.5) + 0.5.
+        wbc: (kInnerRigid, kCytoskeleton, coreRadius, radius) in SI units, for MODEL_WBC_HO only;
         kInnerLink: for MODEL_RBC_MALARIA only; stl: the STL file of shape MESH_FROM_STL (any model).
         The malaria model, STL meshes and ex=True go through hcp_celltype_create_ex, the rest through the entry point
         of their model"""
@@ -673,6 +701,10 @@ class CellType:
         check(self.lib.hcp_celltype_sizes(self.ptr, sz))
         self.nv, self.nt, self.ne, self.nie = [int(x) for x in sz]
         self.model = model
+        if interior_viscosity and viscosity_ratio is None:
+            raise HcError("interior_viscosity=True needs viscosity_ratio=")
+        self.interior_viscosity = bool(interior_viscosity)
+        self.interiorViscosityTau = None if viscosity_ratio is None else float(viscosity_ratio) * (P.tau - 0.5) + 0.5
 
     @classmethod
     def rbc(cls, P, **kw):
@@ -774,7 +806,35 @@ class Cells:
         idx = C.c_int()
         check(self.lib.hcp_add_type(self.ptr, celltype.ptr, int(material_timescale), C.byref(idx)))
         self.types.append(celltype)
+        if getattr(celltype, "interior_viscosity", False):
+            check(self.lib.hcp_type_set_interior_viscosity(self.ptr, idx.value, celltype.interiorViscosityTau))
         return idx.value
+
+    # interior viscosity (core/hemoCell.cpp:347-357, 404-410; core/hemoCellParticleField.cpp:745-807)
+    def setInteriorViscosityTimeScaleSeparation(self, separation, separation_entire_grid):
+        """iterate() then runs internalGridPointsMembrane every `separation` and deleteIncompleteCells +
+        findInternalParticleGridPoints every `separation_entire_grid` iterations, after the constitutive model; both must be
+        multiples of the velocity-update timescale"""
+        check(self.lib.hcp_set_interior_timescales(self.ptr, int(separation), int(separation_entire_grid)))
+
+    def findInternalParticleGridPoints(self):
+        check(self.lib.hcp_interior_find(self.ptr))
+
+    def internalGridPointsMembrane(self):
+        check(self.lib.hcp_interior_membrane(self.ptr))
+
+    def interiorPoints(self):
+        """tau at the tagged nodes and 0 elsewhere, [nx][ny][nz] -- the reference's interiorViscosityField"""
+        cls = self.lattice.interiorClasses()
+        tau = np.r_[0.0, 1.0 / self.lattice.interiorViscosityOmegas()]
+        return tau[cls]
+
+    def interiorNormals(self, t):
+        """the outward vertex normals the membrane pass would use now, [cells * nv][3] of type t"""
+        f, n = self.type_range(t)
+        out = np.empty((n * self.types[t].nv, 3), dtype=np.float64)
+        check(self.lib.hcp_interior_normals(self.ptr, int(t), dptr(out)))
+        return out
 
     def addCell(self, type_index, centre_lu, angles_deg=(0.0, 0.0, 0.0), min_dist_um=0.0, cell_id=None):
         """one line of a .pos file, already in lattice units; angles in degrees as in the file

@@ -58,7 +58,7 @@ int hc_side_stream(void **hip_stream);  /* the side stream's hipStream_t, for a 
 int hc_set_overlap(int on);
 /* per-launch hipEvent timing of the dominant kernel (helper/profiler.h:46-77 "collideAndStream" timer) */
 int hc_profile_enable(int on);
-int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics", "lees_edwards" (both kernels of the pass) */
+int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics", "lees_edwards" (both kernels of the pass), "collide_stream_interior" (how many of the "collide_stream" launches ran the interior-viscosity instantiation: a count, its time is 0), "interior_find", "interior_membrane" (one entry per pass) */
 int hc_profile_reset(void);
 /* identifies the build of the dominant kernel: first 16 hex digits of the SHA-256 of csrc/lattice.hip and csrc/d3q19.h (a committed PMC
  * traffic figure is only quoted next to a timing when it was measured on the same kernel) */
@@ -298,6 +298,22 @@ int hcl_dims(const hc_lattice *L, int dims[3]);
  * loads and stores (everything but solid nodes without a fluid neighbour, which full-way bounce-back leaves inert) */
 int hcl_node_counts(const hc_lattice *L, long counts[3]);
 double hcl_mlups_bytes_per_node(const hc_lattice *L); /* algorithmic bytes per node update of the collide kernel */
+/* Interior viscosity (INTERIOR_VISCOSITY builds of the reference: core/hemoCellField.cpp:100-112 clones the background
+ * dynamics with omega = 1 / tau_int for nodes inside a cell, attributeDynamics in core/hemoCellParticleField.cpp:745-807).
+ * Here a node carries one class byte: 0 relaxes with the lattice's omega, k >= 1 with omega[k - 1]; the dynamics are the
+ * same Guo-forced BGK otherwise.  The field is allocated by the first hcl_interior_enable (all 0) and from then on the collide
+ * runs an instantiation of its own that loads the byte next to the mask byte; a lattice that never enables it runs the
+ * kernels it always ran.  A second call replaces the omegas and keeps the field.  Refused (HC_ERR_ARG, with a message):
+ * n_slabs > 1, a lattice with open-boundary nodes or a Lees-Edwards boundary -- and the open-boundary, Lees-Edwards and
+ * pre-inlet calls refuse a lattice that has it enabled, so the order of the calls does not matter.
+ * classes: uint8 [nx][ny][nz] in the bulk numbering z + nz * (y + ny * x); upload refuses a class above n_classes.  This pair
+ * is also how a checkpoint carries the field.  The passes that maintain it from the cells are hcp_interior_find and
+ * hcp_interior_membrane. */
+#define HC_MAX_VISC_CLASSES 7
+int hcl_interior_enable(hc_lattice *L, int n_classes, const double *omega /*[n_classes]*/);
+int hcl_interior_info(const hc_lattice *L, int *n_classes /* 0: not enabled */, double *omega /*[HC_MAX_VISC_CLASSES] or NULL*/);
+int hcl_interior_upload_classes(hc_lattice *L, const uint8_t *classes);
+int hcl_interior_download_classes(hc_lattice *L, uint8_t *classes);
 
 /* --------------------------------------------------------------- cell types */
 #define HC_MODEL_RBC_HO 0     /* mechanics/rbcHighOrderModel.cpp */
@@ -471,6 +487,37 @@ int hcp_mechanics(hc_cells *C, long iter, int forced);
 /* separate_force_vectors output mode (core/hemoCellParticleField.cpp:590-614): comp = [6][n][3]
  * (volume, area, bending, link, visc, inner link) for the vertices of one type */
 int hcp_mechanics_components(hc_cells *C, int type, double *comp);
+/* ---- interior viscosity: which nodes lie inside a cell (core/hemoCellParticleField.cpp:745-807, helper/octree.h:107-147,
+ * helper/mollerTrumbore.h).  hcp_type_set_interior_viscosity marks a type (<enableInteriorViscosity>, tau_int =
+ * viscosityRatio (tau - 0.5) + 0.5): omega = 1 / tau_int becomes a class of the lattice (an equal omega shares a class;
+ * hcl_interior_enable is called as needed); a type is marked once -- the same tau_int again changes nothing, another one is HC_ERR_ARG.  Only HC_MODEL_RBC_HO carries a normal in the reference; any other model,
+ * more than HC_MAX_VISC_CLASSES distinct omegas and everything hcl_interior_enable refuses are HC_ERR_ARG.
+ * hcp_interior_find (findInternalParticleGridPoints): clears the class field, then for every complete cell of a marked
+ * type tests every integer node of the truncated bounding box of its (unwrapped) vertices: the node is interior when the
+ * number of triangles the ray from the node along (-40, -40, -40) hits is odd, helper/mollerTrumbore.h operation for
+ * operation.  The node is wrapped onto the lattice as the IBM stencil wraps (periodic axes) or dropped (outside a
+ * non-periodic axis), and tagged with the type's class when it is a fluid node.  Where cells of several classes overlap,
+ * the cell with the highest id wins.  The caller removes incomplete cells first (hcp_delete_incomplete_cells), as
+ * core/hemoCell.cpp:348 does; cells that still are incomplete are skipped.
+ * hcp_interior_membrane (internalGridPointsMembrane): for every live vertex of a marked type, every admitted node of its
+ * phi2 stencil (non-zero weight, fluid) no farther than edge_mean_eq from the vertex is tagged when (node - position) . n < 0
+ * and cleared otherwise; n is the vertex's outward normal, the sum over its triangles in ascending order of unit normal *
+ * area / area_mean_eq (mechanics/rbcHighOrderModel.cpp:115-121), formed from the CURRENT positions; an incomplete cell's
+ * vertices have n = 0 and so clear their nodes, as in the reference.  The result is that of visiting the vertices one after
+ * the other in ascending (cell id, vertex index) order, the later one overruling the earlier, whatever the launch geometry.
+ * Both passes are stream ordered, wait for nothing and write the class field: never beside a collide.
+ * hcp_set_interior_timescales (setInteriorViscosityTimeScaleSeperation): hc_iterate then runs, after hcp_mechanics of an
+ * iteration `it`, hcp_delete_incomplete_cells + hcp_interior_find when it % entire_grid_every == 0 and
+ * hcp_interior_membrane when it % membrane_every == 0 (core/hemoCell.cpp:347-357); both must be multiples of hc_iterate's
+ * particle_timescale (HC_ERR_ARG otherwise, core/hemoCell.cpp:614-620), which keeps such an iteration off the side stream.
+ * Defaults 1, 1.  hcp_interior_normals: the normals the membrane pass would use now, [cells * nv][3] of one type. */
+int hcp_type_set_interior_viscosity(hc_cells *C, int type, double tau_int);
+int hcp_set_interior_timescales(hc_cells *C, int membrane_every, int entire_grid_every);
+int hcp_interior_find(hc_cells *C);
+int hcp_interior_membrane(hc_cells *C);
+int hcp_interior_normals(hc_cells *C, int type, double *out);
+/* tests: the workgroup size of the two passes (64, 128, 256 or 512; default 256) -- the class field does not depend on it */
+int hc_debug_interior_block(int threads);
 /* HemoCell::iterate() (core/hemoCell.cpp:299-376) n times, followed each time by the driver's body-force
  * re-application (examples/pipeflow/pipeflow.cpp:144-146).  particle_timescale =
  * setParticleVelocityUpdateTimeScaleSeparation. iter is read and advanced.  Particles that reach a wall are deleted on
