@@ -289,7 +289,7 @@ __device__ __forceinline__ void block_bbox(int lo[3], int hi[3], int *s_red, Til
   for (int a = 0; a < 3; a++) {
     int l = s_red[a], h = s_red[3 + a];
     for (int w = 1; w < nw; w++) { l = min(l, s_red[w * 6 + a]); h = max(h, s_red[w * 6 + 3 + a]); }
-    t.o[a] = l; t.e[a] = h - l + 1;
+    t.o[a] = l; t.e[a] = h >= l ? h - l + 1 : 0;   // no live vertex at all (every particle of the cell removed): an empty tile
   }
   const long vol = (long)t.e[0] * t.e[1] * t.e[2];
   t.vol = vol > 0x7fffffff ? 0x7fffffff : (int)vol;
@@ -501,13 +501,14 @@ __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv,
 #pragma unroll
       for (int j = 0; j < NVPT; j++) {
         const int i = tid + j * nth;
-        if (i < nv) {
+        if (i < nv && !(dead && dead[base + i])) {   // a removed particle is not in the list: its force stays
           const double mag = sqrt((f[j][0] * f[j][0] + f[j][1] * f[j][1]) + f[j][2] * f[j][2]);
           if (mag > f_limit) { const double sc = f_limit / mag; f[j][0] *= sc; f[j][1] *= sc; f[j][2] *= sc; fx[base + i] = f[j][0]; fy[base + i] = f[j][1]; fz[base + i] = f[j][2]; }
         }
       }
     } else {
       for (int i = tid; i < nv; i += nth) {
+        if (dead && dead[base + i]) continue;
         const double f0 = fx[base + i], f1 = fy[base + i], f2 = fz[base + i];
         const double mag = sqrt((f0 * f0 + f1 * f1) + f2 * f2);
         if (mag > f_limit) { const double sc = f_limit / mag; fx[base + i] = f0 * sc; fy[base + i] = f1 * sc; fz[base + i] = f2 * sc; }
@@ -588,7 +589,7 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
 #pragma unroll
     for (int j = 0; j < NVPT; j++) {
       const int i = tid + j * nth;
-      if (i >= nv) continue;
+      if (i >= nv || (dead && dead[base + i])) continue;   // a removed particle keeps its velocity, as in the per-vertex forms
       double a0 = 0.0, a1 = 0.0, a2 = 0.0;
 #pragma unroll
       for (int k = 0; k < 8; k++) {
