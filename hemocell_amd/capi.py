@@ -135,6 +135,18 @@ SIGNATURES = {
     "hcl_interior_info": (C.c_int, [VP, c_int_p, c_double_p]),
     "hcl_interior_upload_classes": (C.c_int, [VP, VP]),
     "hcl_interior_download_classes": (C.c_int, [VP, VP]),
+    "hcl_scalar_create": (C.c_int, [VP, C.c_double, C.POINTER(VP)]),
+    "hcl_scalar_destroy": (C.c_int, [VP]),
+    "hcl_scalar_init_equilibrium": (C.c_int, [VP, c_int_p, C.c_double]),
+    "hcl_scalar_set_source_box": (C.c_int, [VP, c_int_p, C.c_double]),
+    "hcl_scalar_clear_sources": (C.c_int, [VP]),
+    "hcl_scalar_step": (C.c_int, [VP]),
+    "hcl_scalar_download": (C.c_int, [VP, c_double_p]),
+    "hcl_scalar_download_populations": (C.c_int, [VP, c_double_p]),
+    "hcl_scalar_upload_populations": (C.c_int, [VP, c_double_p]),
+    "hcl_scalar_download_velocity": (C.c_int, [VP, c_double_p]),
+    "hcl_scalar_stats": (C.c_int, [VP, c_double_p]),
+    "hcp_sample_scalar": (C.c_int, [VP, VP, c_double_p]),
     "hcp_type_set_interior_viscosity": (C.c_int, [VP, C.c_int, C.c_double]),
     "hcp_set_interior_timescales": (C.c_int, [VP, C.c_int, C.c_int]),
     "hcp_interior_find": (C.c_int, [VP]),

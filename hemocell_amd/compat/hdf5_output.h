@@ -140,8 +140,12 @@ inline void writeCellField3D_HDF5(HemoCell &h, HemoCellField &field, const strin
 }
 
 // writeFluidField_HDF5 (io/FluidHdf5IO.hh:60-210)
-inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlock *blk = nullptr) {
-  if (h.fluidOutputs.empty()) return;
+// cepac: write the CEPAC field instead (writeCEPACField_HDF5, io/FluidHdf5IO.cpp:32-42: the same writer on the second lattice) --
+// CEPAC.<iter>.p.<block>.h5 with the same envelope layout and attributes; Density holds the concentration C as the lattice holds
+// it, Velocity the velocity the field is advected with; any other variable is skipped with one log line
+inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlock *blk = nullptr, hc_scalar *cepac = nullptr) {
+  const vector<int> &variables = cepac ? h.cellfields->desiredCEPACfieldOutputVariables : h.fluidOutputs;
+  if (variables.empty()) return;
   hc_lattice *d = h.lattice->device();   // (queued iterations run first)
   auto *L = blk ? blk->lattice : h.lattice;
   if (blk) d = L->device_now();
@@ -181,20 +185,21 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
   vector<double> rho(ne), u(3 * ne);
   {
     vector<double> r0(nn), u0(3 * nn);
-    hc_check(hcl_download_rho_u(d, r0.data(), u0.data()), "hcl_download_rho_u");
+    if (cepac) { hc_check(hcl_scalar_download(cepac, r0.data()), "hcl_scalar_download"); hc_check(hcl_scalar_download_velocity(cepac, u0.data()), "hcl_scalar_download_velocity"); }
+    else hc_check(hcl_download_rho_u(d, r0.data(), u0.data()), "hcl_download_rho_u");
     std::copy(r0.begin(), r0.end(), rho.begin() + plane); std::copy(u0.begin(), u0.end(), u.begin() + 3 * plane);
   }
   fill_ends(rho, 1); fill_ends(u, 3);
   // cell.computeVelocity / computeDensity go through the node's dynamics (io/FluidHdf5IO.hh:223,273): a BounceBack node answers
   // zero velocity and the density it was constructed with, whatever its populations hold; a velocity-condition node the
   // velocity it imposes (setBoundaryVelocity; zero until one is given)
-  for (size_t k = 0; k < ne; k++) {
+  for (size_t k = 0; k < ne && !cepac; k++) {
     const uint8_t m = maskx[k];
     if (m == 0) continue;
     if (bbx[k]) { rho[k] = L->bb_rho; u[3 * k] = u[3 * k + 1] = u[3 * k + 2] = 0; continue; }
     for (int c = 0; c < 3; c++) u[3 * k + c] = m >= 3 ? (double)L->wall_u[(size_t)(m - 3)][(size_t)c] : 0.0;
   }
-  const string fileName = dir + "/Fluid." + zeroPadNumber(h.iter) + ".p." + std::to_string(blk ? blk->id : global.rank) + ".h5";
+  const string fileName = dir + (cepac ? "/CEPAC." : "/Fluid.") + zeroPadNumber(h.iter) + ".p." + std::to_string(blk ? blk->id : global.rank) + ".h5";
   hid_t file = H5Fcreate(fileName.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT);
   double dx = Parameters::dx, dt = Parameters::dt; long it = h.iter; int id = blk ? blk->id : global.rank;
   H5LTset_attribute_double(file, "/", "dx", &dx, 1); H5LTset_attribute_double(file, "/", "dt", &dt, 1);
@@ -248,8 +253,10 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
     pi.assign(6 * ne, 0.0); std::copy(p0.begin(), p0.end(), pi.begin() + 6 * plane);
     fill_ends(pi, 6);
   };
-  for (int var : h.fluidOutputs) {
-    if (var == OUTPUT_VELOCITY) write4("Velocity", 3, [&](size_t k, int cidx) { return (float)(u[3 * k + cidx] * (si ? Parameters::dx / Parameters::dt : 1.0)); });
+  for (int var : variables) {
+    if (cepac && var == OUTPUT_DENSITY) write4("Density", 1, [&](size_t k, int) { return (float)rho[k]; });
+    else if (cepac && var != OUTPUT_VELOCITY) hlog << "(HemoCell) (Output) the CEPAC field writes Density and Velocity; output variable " << var << " is skipped" << endl;
+    else if (var == OUTPUT_VELOCITY) write4("Velocity", 3, [&](size_t k, int cidx) { return (float)(u[3 * k + cidx] * (si ? Parameters::dx / Parameters::dt : 1.0)); });
     else if (var == OUTPUT_FORCE) {   // the external field as the driver left it (io/FluidHdf5IO.hh:240-262)
       ExternalForce<T> ext = L->external_now();
       if (blk) ext = L->active;   // the pre-inlet's lattice holds its driving force

@@ -158,6 +158,10 @@ class Config {
 // ------------------------------------------------------------------ mechanics/constantConversion.h
 struct Parameters {
   static T dt, dx, dm, df, nu_p, rho_p, tau, re, nu_lbm, u_lbm_max, shearrate_lbm, kBT_lbm, kBT_p, ef_lbm, f_limit, pipe_radius, LE_force;
+  // The CEPAC field relaxes with omega = 1 / tau_CEPAC, diffusivity (tau_CEPAC - 0.5) / 3.  The reference leaves it 0 and hands
+  // it over where an omega belongs (mechanics/constantConversion.cpp:137, core/hemoCellFields.cpp:126); a driver sets it before
+  // initializeCellfield(), as the commented lines cases/CEPAC/CEPAC.cpp:54-57 intend: tau = 3 D dt / dx^2 + 0.5
+  static T tau_CEPAC;
   static hc_params &raw() { static hc_params p; return p; }
   static void lbm_base_parameters(Config &cfg) {
     hc_params &P = raw();
@@ -208,7 +212,7 @@ struct Parameters {
 #ifdef HEMOCELL_COMPAT_MAIN
 T Parameters::dt = 0, Parameters::dx = 0, Parameters::dm = 0, Parameters::df = 0, Parameters::nu_p = 0, Parameters::rho_p = 0, Parameters::tau = 0,
   Parameters::re = 0, Parameters::nu_lbm = 0, Parameters::u_lbm_max = 0, Parameters::shearrate_lbm = 0, Parameters::kBT_lbm = 0, Parameters::kBT_p = 0,
-  Parameters::ef_lbm = 0, Parameters::f_limit = 0, Parameters::pipe_radius = 0, Parameters::LE_force = 0;
+  Parameters::ef_lbm = 0, Parameters::f_limit = 0, Parameters::pipe_radius = 0, Parameters::LE_force = 0, Parameters::tau_CEPAC = 0;
 #endif
 
 // helper/profiler.h:46-77 / config/config.h:80-96: hemo::global.statistics; backed by the library's hipEvent timers
@@ -225,6 +229,7 @@ struct ProfilerView {
 struct Global {   // config/config.h:80-96 (ConfigValues) plus this rank's place in the run
   ProfilerView statistics; bool cellsDeletedInfo = false; bool hemoCellInitialized = false;
   int rank = 0, world = 1;
+  int enableCEPACfield = 0;     // <parameters><enableCEPACfield> (config/config.cpp:183)
   string checkpointDirectory;   // config/config.h:84, set by loadDirectories
 };
 static Global global;
@@ -470,10 +475,51 @@ struct MultiParticleField3D {   // particles/multiParticleField3D.h: one atomic 
 }  // namespace plb
 namespace hemo {
 
+// HemoCellFields::CEPACfield (core/hemoCellFields.cpp:113-140): the driver-facing side of the library's hc_scalar, a recorder
+// like the lattice it belongs to.  The device lattice is created late and may be created again while the driver still
+// describes it, and a scalar goes with its lattice: what the driver asked for (equilibrium over a box, source boxes) is kept
+// and applied, in order, to the scalar of the device lattice in hand.
+class CEPACField {
+ public:
+  struct Op { int kind; plb::Box3D box; double C; };   // kind 0: initializeAtEquilibrium, 1: the box holds C (a source)
+  CEPACField(HemoCellFields &f, double omega_) : omega(omega_), fields(f) {}
+  inline plb::Box3D getBoundingBox() const;
+  void initialize() {}                      // no data processors of its own: sources act inside the step
+  void toggleInternalStatistics(bool) {}
+  plb::Periodicity3D &periodicity() { return per; }   // the flow lattice's periodicity is what the step uses
+  void add(int kind, const plb::Box3D &box, double C) { ops.push_back(Op{kind, box, C}); if (S) device(); }
+  inline hc_scalar *device();               // (queued iterations run first)
+  vector<Op> ops; size_t applied = 0;
+  vector<plb::Box3D> boundaries;            // boxes named by addTemperatureBoundary*: recorded; setBoundaryDensity makes a source
+  plb::Periodicity3D per;
+  hc_scalar *S = nullptr; long generation = -1;
+  double omega;
+  HemoCellFields &fields;
+};
+}  // namespace hemo
+namespace plb {
+// the Palabos names cases/CEPAC/CEPAC.cpp drives the field with.  The flow carries the field, so the velocity of
+// initializeAtEquilibrium is ignored; a temperature boundary is recorded, and setBoundaryDensity on a box makes it a source
+inline void initializeAtEquilibrium(hemo::CEPACField &field, Box3D box, double C, Array<double, 3>) { field.add(0, box, C); }
+inline void setBoundaryDensity(hemo::CEPACField &field, Box3D box, double C) { field.add(1, box, C); }
+template <typename U, template <typename> class D>
+struct OnLatticeAdvectionDiffusionBoundaryCondition3D {
+  void addTemperatureBoundary0N(Box3D b, hemo::CEPACField &field) { field.boundaries.push_back(b); }
+  void addTemperatureBoundary0P(Box3D b, hemo::CEPACField &field) { field.boundaries.push_back(b); }
+  void addTemperatureBoundary1N(Box3D b, hemo::CEPACField &field) { field.boundaries.push_back(b); }
+  void addTemperatureBoundary1P(Box3D b, hemo::CEPACField &field) { field.boundaries.push_back(b); }
+  void addTemperatureBoundary2N(Box3D b, hemo::CEPACField &field) { field.boundaries.push_back(b); }
+  void addTemperatureBoundary2P(Box3D b, hemo::CEPACField &field) { field.boundaries.push_back(b); }
+};
+template <typename U, template <typename> class D>
+OnLatticeAdvectionDiffusionBoundaryCondition3D<U, D> *createLocalAdvectionDiffusionBoundaryCondition3D() { return new OnLatticeAdvectionDiffusionBoundaryCondition3D<U, D>(); }
+}  // namespace plb
+namespace hemo {
+
 class HemoCellFields {
  public:
   explicit HemoCellFields(HemoCell &h) : hemocell(h), particleField(*this), immersedParticles(new plb::MultiParticleField3D<HemoCellParticleField>(&particleField)) { HemoCellParticleField::cellFieldsRef() = this; }
-  ~HemoCellFields() { for (auto *f : cellFields) delete f; if (dev) hcp_destroy(dev); delete immersedParticles; }
+  ~HemoCellFields() { for (auto *f : cellFields) delete f; if (dev) hcp_destroy(dev); delete immersedParticles; delete CEPACfield; }   // (the device scalar goes with its lattice)
   HemoCellField *operator[](unsigned int i) { return cellFields[i]; }
   HemoCellField *operator[](const string &name) {
     for (auto *f : cellFields) if (f->name == name) return f;
@@ -519,7 +565,14 @@ class HemoCellFields {
   bool interiorViscosity = false;   // a bound type has enableInteriorViscosity (global.enableInteriorViscosity of the reference)
   inline void findInternalParticleGridPoints() { hc_check(hcp_interior_find(device()), "hcp_interior_find"); }
   inline void internalGridPointsMembrane() { hc_check(hcp_interior_membrane(device()), "hcp_interior_membrane"); }
-  inline void createCEPACfield() { refuse("the CEPAC field (createCEPACfield)"); }
+  // core/hemoCellFields.cpp:113-140.  The library's scalar lives on one whole domain and beside none of open boundaries,
+  // Lees-Edwards, interior viscosity and a pre-inlet (hcl_scalar_create): such a run is refused, here and again when the scalar
+  // is bound to the device lattice, by which time the driver has declared all of them.
+  inline bool CEPACcombines();
+  void checkCEPAC() { if (!CEPACcombines()) refuse("the CEPAC field (createCEPACfield)"); }
+  inline void createCEPACfield();
+  CEPACField *CEPACfield = nullptr;
+  vector<int> desiredCEPACfieldOutputVariables;   // core/hemoCellFields.h, setCEPACOutputs
 };
 
 // ------------------------------------------------------------------ hemocell.h:68-253
@@ -545,6 +598,7 @@ class HemoCell {
       if (a != string::npos && b != string::npos && b > a) configElement = text.substr(a, b - a) + "</hemocell>\n";
     }
     try { global.cellsDeletedInfo = (*cfg)["verbose"]["cellsDeletedInfo"].read<int>() != 0; } catch (std::invalid_argument &) {}   // config/config.cpp:180
+    try { global.enableCEPACfield = (*cfg)["parameters"]["enableCEPACfield"].read<int>(); } catch (std::invalid_argument &) {}   // :183
     if (global.rank != 0) hlog_instance().to_stdout = false;   // the log is rank 0's (config/logfile.h)
     loadDirectories(true);
     hlog << "(HemoCell) (Config) reading " << configFileName << endl;
@@ -598,6 +652,7 @@ class HemoCell {
   }
   void initializeCellfield() {
     cellfields = new HemoCellFields(*this);
+    if (global.enableCEPACfield) cellfields->createCEPACfield();   // core/hemoCellFields.cpp:49-51
     int env = 25;   // core/hemoCell.cpp:139 reads it here; core/hemoCellFields.cpp:43 prints it.  Used by loadParticles() on slab runs
     try { env = (*cfg)["domain"]["particleEnvelope"].read<int>(); } catch (const std::invalid_argument &) {}
     hlog << "(Hemocell) (HemoCellFields) (Init) particle envelope: " << env << " [lu]" << std::endl;
@@ -685,7 +740,10 @@ class HemoCell {
     hc_check(hcp_set_interior_timescales(c, (int)every, (int)grid), "hcp_set_interior_timescales");
   }
   bool interiorViscosityWarned = false;
-  void setCEPACOutputs(vector<int>) { refuse("the CEPAC field (setCEPACOutputs)"); }
+  void setCEPACOutputs(vector<int> outputs) {   // core/hemoCell.cpp:161-165
+    hlog << "(HemoCell) (Fluid) Setting CEPAC output variables for fluid field" << endl;
+    cellfields->desiredCEPACfieldOutputVariables = outputs;
+  }
   void checkExitSignals() {}                                   // core/hemoCell.cpp:300: SIGINT / SIGTERM handling of the reference's run scripts
   void sanityCheck() { sanityCheckDone = true; }               // the facade's own checks run where a setting is used
   // one x-slab per rank and GPU is the only layout: nothing to measure against, nothing to move
@@ -729,6 +787,7 @@ class HemoCell {
       if (boundaryRepulsionEnabled && !boundaryRepulsionPushed) { hc_check(hcp_set_boundary_repulsion(c, boundaryRepulsionConstant_, boundaryRepulsionCutoff_, (int)boundaryRepulsionTimescale), "hcp_set_boundary_repulsion"); boundaryRepulsionPushed = true; }
       if (repulsionEnabled && !repulsionPushed) { hc_check(hcp_set_repulsion(c, repulsionConstant_, repulsionCutoff_, (int)repulsionTimescale), "hcp_set_repulsion"); repulsionPushed = true; }
       lattice->device();
+      if (cellfields->CEPACfield) cellfields->CEPACfield->device();   // hc_iterate steps the scalar its lattice has
       interiorViscositySanity(c);
       queued_timescale = cellfields->particleVelocityUpdateTimescale;
     }
@@ -950,6 +1009,38 @@ inline void HemoCellFields::applyBoundaryRepulsionForce() {
   hc_check(hcp_boundary_repulsion(c), "hcp_boundary_repulsion"); particleField.invalidate();
 }
 inline void HemoCellFields::refuse(const char *what) { hemocell.refuse(what); }
+inline bool HemoCellFields::CEPACcombines() {
+  auto *L = hemocell.lattice;
+  bool visc = interiorViscosity;
+  for (auto *f : cellFields) visc = visc || f->doInteriorViscosity;
+  return global.world == 1 && !hemocell.preInlet && !visc && !(L && (L->le.on || !L->open_decls.empty()));
+}
+inline void HemoCellFields::createCEPACfield() {
+  if (!(param::tau_CEPAC > 0.5)) {
+    hlog << "(HemoCell) (CEPAC) param::tau_CEPAC is " << param::tau_CEPAC << ": the CEPAC field relaxes with omega = 1 / tau_CEPAC and needs tau_CEPAC > 0.5 "
+         << "(tau_CEPAC = 3 D dt / dx^2 + 0.5); set param::tau_CEPAC before initializeCellfield(). Exiting ..." << endl;
+    std::exit(1);
+  }
+  checkCEPAC();
+  if (!CEPACfield) CEPACfield = new CEPACField(*this, 1.0 / param::tau_CEPAC);
+}
+inline plb::Box3D CEPACField::getBoundingBox() const { return fields.hemocell.lattice->getBoundingBox(); }
+inline hc_scalar *CEPACField::device() {
+  auto *L = fields.hemocell.lattice;
+  hc_lattice *d = L->device();
+  if (!S || generation != L->dev_generation) {
+    fields.checkCEPAC();
+    hc_check(hcl_scalar_create(d, omega, &S), "hcl_scalar_create");
+    generation = L->dev_generation; applied = 0;
+  }
+  for (; applied < ops.size(); applied++) {
+    const Op &o = ops[applied];
+    const int b[6] = {(int)o.box.x0, (int)o.box.x1, (int)o.box.y0, (int)o.box.y1, (int)o.box.z0, (int)o.box.z1};
+    if (o.kind == 0) hc_check(hcl_scalar_init_equilibrium(S, b, o.C), "hcl_scalar_init_equilibrium");
+    else hc_check(hcl_scalar_set_source_box(S, b, o.C), "hcl_scalar_set_source_box");
+  }
+  return S;
+}
 inline plb::MultiParticleField3D<HemoCellParticleField> *HemoCellField::getParticleField3D() { return cellFields->immersedParticles; }
 inline plb::MultiParticleField3D<HemoCellParticleField> *HemoCellField::getParticleArg() { return cellFields->immersedParticles; }
 inline plb::MultiBlockLattice3D<T, DESCRIPTOR> *HemoCellField::getFluidField3D() { return cellFields->hemocell.lattice; }
@@ -1022,6 +1113,7 @@ inline void HemoCell::loadParticles() {
 // The reference writes Palabos' own parallelIO dumps plus checkpoint.xml (a copy of the config under a <Checkpoint>
 // root with the iteration); the binary format here is this back end's own: populations in the reference node
 // order, then per type the cell ids and the vertex position / velocity / force arrays.
+constexpr long CEPAC_CHECKPOINT_MARK = -0x43455041L;   // "CEPA", negated
 inline string checkpoint_file(const string &dir) { return dir + (global.world > 1 ? "/checkpoint." + std::to_string(global.rank) + ".bin" : string("/checkpoint.bin")); }
 
 inline void HemoCell::saveCheckPoint() {
@@ -1065,6 +1157,23 @@ inline void HemoCell::saveCheckPoint() {
     const long ncls = (long)n;
     o.write((const char *)&ncls, sizeof(long));
     o.write((const char *)cls.data(), (std::streamsize)cls.size());
+  }
+  // the CEPAC field: a marker no node count can equal, the scalar's populations and the source boxes with their values; the block
+  // is absent from checkpoints of runs without the field
+  if (cellfields->CEPACfield) {
+    hc_scalar *S = cellfields->CEPACfield->device();
+    vector<double> g(n * HC_Q);
+    hc_check(hcl_scalar_download_populations(S, g.data()), "hcl_scalar_download_populations");
+    long nsrc = 0;
+    for (const CEPACField::Op &op : cellfields->CEPACfield->ops) nsrc += op.kind == 1;
+    const long mark[3] = {CEPAC_CHECKPOINT_MARK, (long)n, nsrc};
+    o.write((const char *)mark, sizeof(mark));
+    o.write((const char *)g.data(), (std::streamsize)(g.size() * sizeof(double)));
+    for (const CEPACField::Op &op : cellfields->CEPACfield->ops) {
+      if (op.kind != 1) continue;
+      const long b[6] = {(long)op.box.x0, (long)op.box.x1, (long)op.box.y0, (long)op.box.y1, (long)op.box.z0, (long)op.box.z1};
+      o.write((const char *)b, sizeof(b)); o.write((const char *)&op.C, sizeof(double));
+    }
   }
   o.close();
   if (!o) { hlog << "(HemoCell) (saveCheckPoint) could not write " << tmp_name << endl; std::exit(1); }
@@ -1125,14 +1234,41 @@ inline void HemoCell::loadCheckPoint() {
   hc_check(hcp_delete_incomplete_cells(c, nullptr), "hcp_delete_incomplete_cells");
   {   // the class field of a run with interior viscosity (binding the types above has enabled it on the lattice)
     int nclasses = 0; hc_check(hcl_interior_info(d, &nclasses, nullptr), "hcl_interior_info");
+    const std::streampos at = in.tellg();
     long ncls = 0; in.read((char *)&ncls, sizeof(long));
     const bool present = in.good() && ncls == (long)n;
+    if (!present) { in.clear(); in.seekg(at); }   // the end of the file, or the block of another feature
     if (nclasses > 0 && !present) { hlog << "(HemoCell) (loadCheckPoint) the checkpoint holds no interior-viscosity field for this case" << endl; std::exit(1); }
     if (present) {
       vector<uint8_t> cls(n);
       in.read((char *)cls.data(), (std::streamsize)cls.size());
       if (!in.good()) truncated();
       if (nclasses > 0) hc_check(hcl_interior_upload_classes(d, cls.data()), "hcl_interior_upload_classes");
+    }
+  }
+  {   // the CEPAC field: populations and sources replace what the driver's set-up gave the scalar
+    long mark[3] = {0, 0, 0}; in.read((char *)mark, sizeof(mark));
+    const bool present = in.good() && mark[0] == CEPAC_CHECKPOINT_MARK && mark[1] == (long)n && mark[2] >= 0;
+    CEPACField *cf = cellfields->CEPACfield;
+    if (cf && !present) { hlog << "(HemoCell) (loadCheckPoint) the checkpoint holds no CEPAC field, and this run has one (enableCEPACfield)" << endl; std::exit(1); }
+    if (present) {
+      vector<double> g(n * HC_Q);
+      in.read((char *)g.data(), (std::streamsize)(g.size() * sizeof(double)));
+      if (!in.good()) truncated();
+      vector<CEPACField::Op> sources;
+      for (long k = 0; k < mark[2]; k++) {
+        long b[6]; double Cs = 0;
+        in.read((char *)b, sizeof(b)); in.read((char *)&Cs, sizeof(double));
+        if (!in.good()) truncated();
+        sources.push_back(CEPACField::Op{1, plb::Box3D(b[0], b[1], b[2], b[3], b[4], b[5]), Cs});
+      }
+      if (cf) {
+        hc_scalar *S = cf->device();
+        hc_check(hcl_scalar_clear_sources(S), "hcl_scalar_clear_sources");
+        hc_check(hcl_scalar_upload_populations(S, g.data()), "hcl_scalar_upload_populations");
+        cf->ops.clear(); cf->applied = 0;
+        for (const CEPACField::Op &op : sources) cf->add(1, op.box, op.C);
+      }
     }
   }
   long nct = 0; hcp_counts(c, nullptr, &nct, nullptr);
@@ -1348,6 +1484,7 @@ inline void HemoCell::writeOutput() {
   hlog << "(HemoCell) (Output) writing output at timestep " << iter << " (" << iter * Parameters::dt << " s)" << endl;
   for (unsigned int t = 0; t < cellfields->size(); t++) writeCellField3D_HDF5(*this, *(*cellfields)[t], dir);
   writeFluidField_HDF5(*this, dir);
+  if (cellfields->CEPACfield) writeFluidField_HDF5(*this, dir, nullptr, cellfields->CEPACfield->device());   // core/hemoCell.cpp:276-278
   if (preinlet_cells() || preinlet_box()) {   // the pre-inlet: one more atomic block of every field, at its box's corner
     OutputBlock blk;
     if (preinlet_output_block(blk)) {

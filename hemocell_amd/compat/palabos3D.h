@@ -242,6 +242,7 @@ class MultiBlockLattice3D {
     if (world == 1) hc_check(hc_init(0), "hc_init");
     x0 = (plint)rank * nx / world; nxl = (plint)(rank + 1) * nx / world - x0;
     hc_check(hcl_create(&dev, (int)nxl, (int)ny, (int)nz, pr, omega, (int)x0, (int)nx, world), "hcl_create");
+    dev_generation++;   // what was bound to the previous device lattice (the CEPAC field, hemo::CEPACField) went with it
     std::vector<uint8_t> padded((size_t)(nxl + 4) * ny * nz, 1);   // beyond a non-periodic end: wall
     for (plint x = -2; x < nxl + 2; x++) {
       plint sx = x0 + x;
@@ -379,6 +380,7 @@ class MultiBlockLattice3D {
   bool force_cleared = false;         // an iterate() has zeroed the field and nothing was written since
   std::function<void()> before_access;
   bool dirty_layout = true, dirty_force = true, stepped = false, cells_bound = false;
+  long dev_generation = 0;   // counts the device lattices created so far
   hc_lattice *dev = nullptr;
   int rank = 0, world = 1; plint x0 = 0, nxl = 0;   // this rank's slab (valid once device() ran)
   GuoExternalForceBGKdynamics<U, D> background_dynamics;   // what the lattice was constructed with (getBackgroundDynamics)

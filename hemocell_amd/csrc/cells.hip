@@ -850,6 +850,9 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
       if ((rc = hc::lees_edwards_step(L)) != HC_OK) return rc;
       if (L->le_d != 0.0) L->le_D = fmod(L->le_d * (double)(it + 1), (double)L->nx);   // LeesEdwardsBC::updateLECurDisplacement(iter)
     }
+    // the CEPAC field's collideAndStream (:320-325), on the main stream: it reads the populations just written and the force the
+    // collide consumed, which nothing on the side stream writes
+    if (L->scalar && (rc = hcl_scalar_step(L->scalar)) != HC_OK) return rc;
     if (particle_step) { if ((rc = hcp_interpolate(C)) != HC_OK) return rc; }   // :327-332
     if (overlap) hc::route(1);
     if ((rc = hcp_advance(C, 0)) != HC_OK) return rc;                           // :342

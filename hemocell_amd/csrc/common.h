@@ -102,7 +102,7 @@ template <class T> struct Staged {
 };
 
 // per-kernel hipEvent timing (hc_profile_*)
-enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
+enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_SCALAR, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
 void prof_count(int kernel);   // one more launch of `kernel`, without a time (while profiling is on)
 struct ProfScope {
   int k; bool on;
@@ -294,6 +294,10 @@ struct hc_lattice {
   hc::DevBuf<uint8_t> visc_class;   // [npad], device
   int visc_n = 0; double visc_omega[HC_MAX_VISC_CLASSES];
   hc::DevBuf<unsigned long long> visc_vote;   // [npad] scratch of the interior passes: 0 between passes
+  // The CEPAC scalar field bound to this lattice (scalar.hip; hcl_scalar_create), or null.  hc_iterate steps it once per
+  // iteration.  It does not combine with open boundaries, Lees-Edwards, interior viscosity or a pre-inlet: each of those calls
+  // refuses a lattice that has one, and hcl_scalar_create a lattice that has any of them.
+  hc_scalar *scalar = nullptr;
   hc::DevBuf<int> ob_list;      // staging of hcl_plane_velocity's node list
   hc::DevBuf<double> ob_out;    // ... and of its output when the caller's buffer is on the host
 };
@@ -312,6 +316,14 @@ inline void launch_open(const hc_lattice *L, const Plain &plain, Launch launch) 
 
 namespace hc {
 int lees_edwards_step(hc_lattice *L);   // lattice.hip: the pass after a step, when enabled
+void scalar_lattice_destroyed(hc_lattice *L);   // scalar.hip: hcl_destroy takes the lattice's scalar field with it
+// The lattices that live pre-inlet handles (hcl_preinlet_* / hcp_preinlet_*) name, for hcl_scalar_create's refusal.  Kept by
+// address in a list of the library's (lattice.hip), not in the lattices: a handle may outlive its lattices, so taking its
+// entries out again must not touch them.  `owner` is the handle.
+void preinlet_pair_add(const void *owner, const hc_lattice *L);
+void preinlet_pair_remove(const void *owner);
+void preinlet_pair_forget(const hc_lattice *L);   // hcl_destroy: the address may be handed out again
+bool in_preinlet_pair(const hc_lattice *L);
 }
 
 // slab.hip: HemoCell::iterate / collideAndStream on one x-slab of a multi-GPU run (halo and envelope exchange inside)

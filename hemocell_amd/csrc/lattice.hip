@@ -659,6 +659,21 @@ int launch_lees_edwards(hc_lattice *L) {
 
 int hc::lees_edwards_step(hc_lattice *L) { return L->le_on ? launch_lees_edwards(L) : HC_OK; }
 
+// the (handle, lattice) pairs of the live pre-inlet handles (common.h).  Not locked: like the error string and the stream
+// selection of runtime.hip, the library's entry points are called from one thread.  A counter in hc_lattice would need the
+// handles to go before their lattices, and callers release them in either order.
+static std::vector<std::pair<const void *, const hc_lattice *>> g_preinlet_pairs;
+void hc::preinlet_pair_add(const void *owner, const hc_lattice *L) { g_preinlet_pairs.emplace_back(owner, L); }
+void hc::preinlet_pair_remove(const void *owner) {
+  g_preinlet_pairs.erase(std::remove_if(g_preinlet_pairs.begin(), g_preinlet_pairs.end(), [&](const auto &e) { return e.first == owner; }), g_preinlet_pairs.end());
+}
+void hc::preinlet_pair_forget(const hc_lattice *L) {
+  g_preinlet_pairs.erase(std::remove_if(g_preinlet_pairs.begin(), g_preinlet_pairs.end(), [&](const auto &e) { return e.second == L; }), g_preinlet_pairs.end());
+}
+bool hc::in_preinlet_pair(const hc_lattice *L) {
+  return std::any_of(g_preinlet_pairs.begin(), g_preinlet_pairs.end(), [&](const auto &e) { return e.second == L; });
+}
+
 // the four z-layers a Lees-Edwards pass reads or writes populations of (z = 0, 1, nz-2, nz-1): every bulk node there must
 // be fluid, so that each stored slot the pass writes has the one reader the pass means (mask: device numbering)
 static bool le_layers_fluid(const hc_lattice *L, const uint8_t *mask, size_t xs) {
@@ -758,6 +773,8 @@ int hcl_create(hc_lattice **out, int nx, int ny, int nz, const int periodic[3], 
 int hcl_destroy(hc_lattice *L) {
   if (!L) return HC_OK;
   hcs::lattice_destroyed(L);
+  hc::scalar_lattice_destroyed(L);
+  hc::preinlet_pair_forget(L);
   hipStreamSynchronize(hc::stream());
   delete L;
   return HC_OK;
@@ -926,6 +943,7 @@ int hcl_set_lees_edwards(hc_lattice *L, double v_top, double v_bottom) {
   HC_REQUIRE(L->nz >= 4, "hcl_set_lees_edwards: nz must be at least 4");
   HC_REQUIRE(L->ob_n == 0, "hcl_set_lees_edwards: the lattice has open-boundary nodes; open boundaries and Lees-Edwards do not combine");
   HC_REQUIRE(L->visc_n == 0, "hcl_set_lees_edwards: the lattice has interior viscosity enabled; interior viscosity and Lees-Edwards do not combine");
+  HC_REQUIRE(!L->scalar, "hcl_set_lees_edwards: the lattice has a scalar field; the scalar field and Lees-Edwards do not combine");
   if (!le_layers_fluid(L, L->hmask.data(), L->xs)) {
     hc::set_error("hcl_set_lees_edwards: the layers z = 0, 1, nz-2 and nz-1 must hold fluid nodes only");
     return HC_ERR_STATE;
@@ -1015,6 +1033,8 @@ static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int
   HC_REQUIRE(!L->le_on, who + ": the lattice has a Lees-Edwards boundary; open boundaries and Lees-Edwards do not combine");
   // the open-boundary and the interior-viscosity collide are two instantiations; no kernel does both
   HC_REQUIRE(L->visc_n == 0, who + ": the lattice has interior viscosity enabled; interior viscosity and open boundaries do not combine");
+  // the scalar step takes plain moments of the flow's populations and knows no open faces of its own
+  HC_REQUIRE(!L->scalar, who + ": the lattice has a scalar field; the scalar field and open boundaries do not combine");
   // a node holds one slot: declaring it again (in this call or an earlier one) would orphan the first slot and let the second
   // declaration win silently, so it is refused and nothing is changed
   {
@@ -1198,6 +1218,7 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
   HC_REQUIRE(axis >= 0 && axis <= 2, "hcl_preinlet_create: axis must be 0, 1 or 2");
   HC_REQUIRE(pre->n_slabs == 1, "hcl_preinlet_create: needs n_slabs = 1 on the pre-inlet lattice");
   HC_REQUIRE(pre->visc_n == 0 && domain->visc_n == 0, "hcl_preinlet_create: a lattice has interior viscosity enabled; interior viscosity and a pre-inlet do not combine");
+  HC_REQUIRE(!pre->scalar && !domain->scalar, "hcl_preinlet_create: a lattice has a scalar field; the scalar field and a pre-inlet do not combine");
   // a slab domain: the inlet plane of an x direction lies on one rank, whose local slots these are; a y or z plane would span the ranks
   HC_REQUIRE(domain->n_slabs == 1 || axis == 0, "hcl_preinlet_create: axis 1 and 2 need n_slabs = 1 on the domain; a slab domain is coupled along x only (axis 0)");
   HC_REQUIRE(pre_plane >= 0 && pre_plane < axis_extent(pre, axis), "hcl_preinlet_create: plane outside the pre-inlet lattice");
@@ -1221,6 +1242,7 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
     HC_HIP(hipMemcpyAsync(P->idx, pre_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, hc::stream()));
     HC_HIP(hipStreamSynchronize(hc::stream()));   // the caller's list may go away after the call
   }
+  hc::preinlet_pair_add(P.get(), pre); hc::preinlet_pair_add(P.get(), domain);
   *out = P.release();
   return HC_OK;
 }
@@ -1244,6 +1266,7 @@ int hcl_preinlet_iterate(hc_preinlet *P, int n) {
 int hcl_preinlet_destroy(hc_preinlet *P) {
   if (!P) return HC_OK;
   hipStreamSynchronize(hc::stream());
+  hc::preinlet_pair_remove(P);
   delete P;
   return HC_OK;
 }
@@ -1256,6 +1279,7 @@ int hcl_interior_enable(hc_lattice *L, int n_classes, const double *omega) {
   HC_REQUIRE(L->n_slabs == 1, "hcl_interior_enable: interior viscosity needs the whole domain on one GPU (n_slabs = 1)");
   HC_REQUIRE(L->ob_n == 0, "hcl_interior_enable: the lattice has open-boundary nodes; interior viscosity and open boundaries do not combine");
   HC_REQUIRE(!L->le_on, "hcl_interior_enable: the lattice has a Lees-Edwards boundary; interior viscosity and Lees-Edwards do not combine");
+  HC_REQUIRE(!L->scalar, "hcl_interior_enable: the lattice has a scalar field; the scalar field and interior viscosity do not combine");
   if (!L->visc_class) {   // a second call changes the omegas and keeps the field
     const int rc = L->visc_class.reserve(L->npad); if (rc != HC_OK) return rc;
     HC_HIP(hipMemsetAsync(L->visc_class, 0, L->npad, hc::stream()));

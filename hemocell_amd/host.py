@@ -374,10 +374,91 @@ class Lattice:
         check(self.lib.hcl_interior_download_classes(self.ptr, out.ctypes.data))
         return out
 
+    def createCEPACfield(self, tau):
+        """the CEPAC scalar field of this lattice (core/hemoCellFields.cpp:120-133), relaxing with omega = 1 / tau:
+        diffusivity (tau - 0.5) / 3 in lattice units"""
+        if not tau > 0.0:
+            raise HcError("createCEPACfield: tau must be positive, got %r" % (tau,))
+        self.scalar = Scalar(self, 1.0 / float(tau))
+        return self.scalar
+
     def destroy(self):
         if self.ptr:
-            check(self.lib.hcl_destroy(self.ptr))
+            check(self.lib.hcl_destroy(self.ptr))   # takes the lattice's scalar field with it
+            if getattr(self, "scalar", None) is not None:
+                self.scalar.ptr = C.c_void_p()
             self.ptr = C.c_void_p()
+
+
+class Scalar:
+    """The CEPAC field: a passive scalar (a dissolved agonist concentration C) that the lattice's flow carries and that
+    diffuses.  Arrays are in the lattice's node order z + nz*(y + ny*x)."""
+
+    def __init__(self, lattice, omega):
+        self.lib = capi.lib()
+        self.lattice = lattice
+        self.omega = float(omega)
+        self.ptr = C.c_void_p()
+        check(self.lib.hcl_scalar_create(lattice.ptr, self.omega, C.byref(self.ptr)))
+        self.n = lattice.n
+
+    @staticmethod
+    def _box(box):
+        b = [int(v) for v in box]
+        if len(b) != 6:
+            raise HcError("a box is (x0, x1, y0, y1, z0, z1), got %r" % (box,))
+        return (C.c_int * 6)(*b)
+
+    def initializeAtEquilibrium(self, C_value, box=None):
+        """plb::initializeAtEquilibrium(field, box, C, u) at u = 0; box: inclusive node ranges, None = every node"""
+        check(self.lib.hcl_scalar_init_equilibrium(self.ptr, self._box(box) if box is not None else None, float(C_value)))
+
+    def addSource(self, box, C_value):
+        """the nodes of the box hold C from now on (setBoundaryDensity on the temperature boundary of the reference's case)"""
+        check(self.lib.hcl_scalar_set_source_box(self.ptr, self._box(box), float(C_value)))
+
+    def clearSources(self):
+        check(self.lib.hcl_scalar_clear_sources(self.ptr))
+
+    def collideAndStream(self):
+        """one step with the velocity of the lattice's present state (after Lattice.step_end or collideAndStream)"""
+        check(self.lib.hcl_scalar_step(self.ptr))
+
+    def concentration(self):
+        out = np.empty(self.n, dtype=np.float64)
+        check(self.lib.hcl_scalar_download(self.ptr, dptr(out)))
+        return out
+
+    def velocity(self):
+        """[n][3]: the velocity the next step advects with; 0 on nodes that are not fluid"""
+        out = np.empty((self.n, 3), dtype=np.float64)
+        check(self.lib.hcl_scalar_download_velocity(self.ptr, dptr(out)))
+        return out
+
+    def populations(self):
+        """[n][19] post-stream populations (g - t_i)"""
+        out = np.empty((self.n, 19), dtype=np.float64)
+        check(self.lib.hcl_scalar_download_populations(self.ptr, dptr(out)))
+        return out
+
+    def set_populations(self, g):
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        if g.shape != (self.n, 19):
+            raise HcError("populations must have shape (%d, 19), got %s" % (self.n, g.shape))
+        check(self.lib.hcl_scalar_upload_populations(self.ptr, dptr(g)))
+
+    def stats(self):
+        """(sum, minimum, maximum) of C over the fluid nodes, reduced on the device"""
+        o = np.zeros(3)
+        check(self.lib.hcl_scalar_stats(self.ptr, dptr(o)))
+        return o[0], o[1], o[2]
+
+    def destroy(self):
+        if self.ptr:
+            check(self.lib.hcl_scalar_destroy(self.ptr))
+            self.ptr = C.c_void_p()
+            if getattr(self.lattice, "scalar", None) is self:
+                self.lattice.scalar = None
 
 
 class LeesEdwardsBC:
@@ -958,6 +1039,12 @@ class Cells:
         out = np.empty(self.counts()[0], dtype=np.uint8)
         check(self.lib.hcp_download_alive(self.ptr, out.ctypes.data))
         return out.astype(bool)
+
+    def sampleScalar(self, scalar):
+        """the scalar field's C at every vertex, through the interpolation stencil of interpolateFluidVelocity"""
+        out = np.empty(self.counts()[0], dtype=np.float64)
+        check(self.lib.hcp_sample_scalar(self.ptr, scalar.ptr, dptr(out)))
+        return out
 
     def applyConstitutiveModel(self, iter_=0, forced=False):
         check(self.lib.hcp_mechanics(self.ptr, int(iter_), int(forced)))

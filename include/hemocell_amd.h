@@ -315,6 +315,42 @@ int hcl_interior_info(const hc_lattice *L, int *n_classes /* 0: not enabled */, 
 int hcl_interior_upload_classes(hc_lattice *L, const uint8_t *classes);
 int hcl_interior_download_classes(hc_lattice *L, uint8_t *classes);
 
+/* The CEPAC field (core/hemoCellFields.cpp:120-133): a passive scalar, a dissolved agonist concentration C, on a D3Q19
+ * advection-diffusion lattice bound to one hc_lattice, which carries it.  The reference leaves the field half finished and its
+ * fluid library is not part of its tree, so this back end defines the step itself (csrc/scalar.hip states it operation by
+ * operation, tests/scalar_ref.py restates it; DESIGN.md section 6 lists the deviations):
+ *   fluid node   g_i <- g_i (1 - omega) + omega t_i (Cbar + 3 C c_i.u), Cbar = sum g_i, C = 1 + Cbar, diffusivity (1/omega - 1/2)/3
+ *   wall node    full-way bounce-back: zero scalar flux, no momentum term for moving walls
+ *   source node  every population is set to t_i (C_s - 1 + 3 C_s c_i.u); observers report C_s there
+ * u is the flow's velocity after the collide-stream of the same iteration: j/rho of the post-stream populations plus half of the
+ * body and IBM force that collide consumed -- hcl_scalar_step belongs after hcl_step_end.  hc_iterate runs one step per
+ * iteration there, before the interpolation (core/hemoCell.cpp:320-325); hcl_collide_stream alone does not step the scalar.
+ * Refused (HC_ERR_ARG, with a message): omega outside (0,2); n_slabs > 1; a lattice with open-boundary nodes, a Lees-Edwards
+ * boundary, interior viscosity or a pre-inlet handle (hcl_preinlet_create / hcp_preinlet_create*), and those calls refuse a
+ * lattice that has a scalar; a second scalar on one lattice.  hcl_destroy destroys the lattice's scalar with it.
+ * A new field holds C = 1.  box: inclusive node ranges {x0, x1, y0, y1, z0, z1}, clipped to the lattice; NULL = every node.
+ * Sources: at most HC_MAX_SCALAR_SOURCES distinct values on the lattice at a time (a value whose nodes were all painted over
+ * gives its slot back); a box that would bring one more, or a value that is not a number, is refused and changes nothing; a
+ * box wholly outside the lattice registers nothing.
+ * Arrays are in the bulk numbering z + nz * (y + ny * x): C_out [n], populations [n][19] in the visible post-stream convention
+ * of hcl_download_populations, u_out [n][3] (0 on nodes that are not fluid), out3 = {sum, minimum, maximum} of C over the
+ * fluid nodes.  hcp_sample_scalar: C at every vertex through the IBM interpolation stencil (fluid nodes only, weights
+ * renormalised), in the vertex order of hcp_download; removed vertices give 0. */
+typedef struct hc_scalar hc_scalar;
+#define HC_MAX_SCALAR_SOURCES 8
+int hcl_scalar_create(hc_lattice *L, double omega, hc_scalar **out);
+int hcl_scalar_destroy(hc_scalar *S);
+int hcl_scalar_init_equilibrium(hc_scalar *S, const int box[6] /* or NULL */, double C);
+int hcl_scalar_set_source_box(hc_scalar *S, const int box[6], double C);
+int hcl_scalar_clear_sources(hc_scalar *S);
+int hcl_scalar_step(hc_scalar *S);
+int hcl_scalar_download(hc_scalar *S, double *C_out);
+int hcl_scalar_download_populations(hc_scalar *S, double *g_aos);
+int hcl_scalar_upload_populations(hc_scalar *S, const double *g_aos);
+int hcl_scalar_download_velocity(hc_scalar *S, double *u_out);
+int hcl_scalar_stats(hc_scalar *S, double out3[3]);
+int hcp_sample_scalar(hc_cells *C, hc_scalar *S, double *out_per_vertex);
+
 /* --------------------------------------------------------------- cell types */
 #define HC_MODEL_RBC_HO 0     /* mechanics/rbcHighOrderModel.cpp */
 #define HC_MODEL_PLT_SIMPLE 1 /* mechanics/pltSimpleModel.cpp    */
