@@ -153,6 +153,21 @@ SIGNATURES = {
     "hcp_interior_membrane": (C.c_int, [VP]),
     "hcp_interior_normals": (C.c_int, [VP, C.c_int, c_double_p]),
     "hc_debug_interior_block": (C.c_int, [C.c_int]),
+    "hcl_binding_populate": (C.c_int, [VP, c_int_p]),
+    "hcl_binding_clear": (C.c_int, [VP]),
+    "hcl_binding_download": (C.c_int, [VP, VP]),
+    "hcl_binding_upload": (C.c_int, [VP, VP]),
+    "hcl_download_mask": (C.c_int, [VP, VP]),
+    "hcl_download_tresca": (C.c_int, [VP, c_double_p]),
+    "hcl_upload_solidified_mask": (C.c_int, [VP, VP]),
+    "hcp_type_set_solidify": (C.c_int, [VP, C.c_int, C.c_double, C.c_double]),
+    "hcp_set_solidify_timescale": (C.c_int, [VP, C.c_int]),
+    "hcp_solidify_prepare": (C.c_int, [VP]),
+    "hcp_solidify_flag": (C.c_int, [VP]),
+    "hcp_solidify_flags_download": (C.c_int, [VP, VP]),
+    "hcp_solidify_flags_upload": (C.c_int, [VP, VP]),
+    "hcp_solidify_counts": (C.c_int, [VP, c_long_p]),
+    "hc_debug_solidify_block": (C.c_int, [C.c_int]),
     "hc_params_base": (C.c_int, [C.POINTER(Params)] + [C.c_double] * 5),
     "hcp_celltype_create": (C.c_int, [C.POINTER(VP), C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Material)]),
     "hcp_celltype_create_wbc": (C.c_int, [C.POINTER(VP), C.c_int, C.POINTER(Params), C.POINTER(Material),

@@ -175,6 +175,22 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
     if (gx(-1) < 0) std::copy(a.begin() + pc, a.begin() + 2 * pc, a.begin());
     if (gx(nx) < 0) std::copy(a.begin() + (size_t)nx * pc, a.begin() + (size_t)(nx + 1) * pc, a.begin() + (size_t)(nx + 1) * pc);
   };
+  // solidify mechanics: nodes that turned to wall since the start join the global flags as BounceBack(1.) nodes, so that
+  // Boundary, and what the dynamics of such a node answer, follow the mask the device holds; the binding field for BindingSites
+  const bool binding_used = !cepac && !blk && (global.enableSolidifyMechanics || !h.cellfields->bindingBoxes.empty()) && global.world == 1;
+  vector<uint8_t> sites;
+  if (binding_used) {
+    hc_lattice *b = h.cellfields->bindingDevice();
+    vector<uint8_t> walls(nn); sites.resize(nn);
+    hc_check(hcl_download_mask(b, walls.data()), "hcl_download_mask");
+    hc_check(hcl_binding_download(b, sites.data()), "hcl_binding_download");
+    for (size_t k = 0; k < nn; k++)
+      if (walls[k] && !L->mask[k]) {
+        L->mask[k] = 1;
+        if (L->bounce_back.empty()) { L->bounce_back.assign(L->mask.size(), 0); L->bb_rho = 1.0; }
+        L->bounce_back[k] = 1;
+      }
+  }
   // node classes of the extended block from the global flags
   vector<uint8_t> maskx(ne), bbx(ne, 0);
   for (plint x = -1; x <= nx; x++) {
@@ -307,6 +323,8 @@ inline void writeFluidField_HDF5(HemoCell &h, const string &dir, const OutputBlo
       }
     } else if (var == OUTPUT_INTERIOR_POINTS && nclasses > 0) {   // tau at the tagged nodes, 0 elsewhere (:335-350)
       write4("InteriorPoints", 1, [&](size_t k, int) { return (float)taux[k]; });
+    } else if (var == OUTPUT_BINDING_SITES && binding_used) {   // the binding field, 1 at a site (io/FluidHdf5IO.cpp:306-333); 0 on the two x-planes of the envelope
+      write4("BindingSites", 1, [&](size_t k, int) { return k >= (size_t)plane && k < (size_t)plane + nn ? (float)sites[k - (size_t)plane] : 0.f; });
     } else if (var == OUTPUT_BINDING_SITES || var == OUTPUT_INTERIOR_POINTS) {   // the feature does not exist here / is not in use: what the reference writes then (:306-350)
       pcout << (var == OUTPUT_BINDING_SITES ? "(FluidHdf5) (Error) OUTPUT_BINDING_SITES requested, but binding sites not used, outputting a zero field"
                                             : "(FluidHdf5) (Error) OUTPUT_INTERIOR_POINTS requested, but interior viscosity not used, outputting a zero field") << endl;

@@ -230,6 +230,7 @@ struct Global {   // config/config.h:80-96 (ConfigValues) plus this rank's place
   ProfilerView statistics; bool cellsDeletedInfo = false; bool hemoCellInitialized = false;
   int rank = 0, world = 1;
   int enableCEPACfield = 0;     // <parameters><enableCEPACfield> (config/config.cpp:183)
+  int enableSolidifyMechanics = 0;   // <parameters><enableSolidifyMechanics> (config/config.cpp:186); the library is always a SOLIDIFY_MECHANICS build
   string checkpointDirectory;   // config/config.h:84, set by loadDirectories
 };
 static Global global;
@@ -352,6 +353,7 @@ class HemoCellField {
   void create_device_type(int model);
   // the rest of core/hemoCellField.h:41-83
   T restingCellVolume = 0; bool outputTriangles = false, doSolidifyMechanics = false, doInteriorViscosity = false; T interiorViscosityTau = 1.0;
+  T solidifyDistanceThreshold = 0, solidifyShearThreshold = 0;   // <distanceThreshold> (lattice units), <shearThreshold> of the type's <MaterialModel>
   string getIdentifier() const { return name; }
   int getNumberOfCells_Global() const { return 0; }   // core/hemoCellField.cpp:192 answers 0 as well
   void setOutputVariables(const vector<int> &outputs) {   // :139-147 (OUTPUT_TRIANGLES stays in the list here; the writer looks for it)
@@ -557,9 +559,23 @@ class HemoCellFields {
   inline void unify_force_vectors() {}
   inline void updateResidenceTime(unsigned int) {}   // "Res Time" is written as zeros
   void refuse(const char *what);   // log + exit(1), like HemoCell::refuse
-  inline void solidifyCells() { refuse("solidify mechanics (solidifyCells)"); }
-  inline void prepareSolidification() { refuse("solidify mechanics (prepareSolidification)"); }
-  inline void populateBindingSites(plb::Box3D * = nullptr) { refuse("binding sites (populateBindingSites)"); }
+  // Solidify mechanics (core/hemoCellParticleField.cpp:920-1065, mechanics/pltSimpleModel.cpp:211-252) on the device
+  // (csrc/solidify.hip); hc_iterate runs prepare and flag at solidifyTimescale.  The library's passes live on one whole domain
+  // and beside none of open boundaries, Lees-Edwards, interior viscosity and a pre-inlet: such a run is refused, at the call and
+  // again before the first queued iteration, by which time the driver has declared all of them.
+  pluint solidifyTimescale = 1;
+  bool solidifyPushed = false;
+  inline bool solidifyCombines();
+  void checkSolidify() { if (!solidifyCombines()) refuse("solidify mechanics (solidifyCells)"); }
+  inline void solidifyCells() { checkSolidify(); hc_check(hcp_solidify_flag(device()), "hcp_solidify_flag"); }
+  inline void prepareSolidification() { checkSolidify(); hc_check(hcp_solidify_prepare(device()), "hcp_solidify_prepare"); }
+  // the boxes are kept: the device lattice is created late and may be created again while the driver still describes it, and
+  // the binding field goes with it.  bindingDevice() replays them on the device lattice in hand.
+  vector<plb::Box3D> bindingBoxes; size_t bindingApplied = 0; long bindingGeneration = -1;
+  inline void populateBindingSites(plb::Box3D *box = nullptr);
+  inline hc_lattice *bindingDevice();
+  bool bindingUsed() const { return !bindingBoxes.empty() || hemocell_solidify(); }
+  inline bool hemocell_solidify() const;
   // core/hemoCellParticleField.cpp:745-807 on the device (csrc/interior.hip); hc_iterate runs them at these cadences
   unsigned int interiorViscosityTimescale = 1, interiorViscosityEntireGridTimescale = 1;
   bool interiorViscosity = false;   // a bound type has enableInteriorViscosity (global.enableInteriorViscosity of the reference)
@@ -599,6 +615,7 @@ class HemoCell {
     }
     try { global.cellsDeletedInfo = (*cfg)["verbose"]["cellsDeletedInfo"].read<int>() != 0; } catch (std::invalid_argument &) {}   // config/config.cpp:180
     try { global.enableCEPACfield = (*cfg)["parameters"]["enableCEPACfield"].read<int>(); } catch (std::invalid_argument &) {}   // :183
+    try { global.enableSolidifyMechanics = (*cfg)["parameters"]["enableSolidifyMechanics"].read<int>(); } catch (std::invalid_argument &) {}   // :186
     if (global.rank != 0) hlog_instance().to_stdout = false;   // the log is rank 0's (config/logfile.h)
     loadDirectories(true);
     hlog << "(HemoCell) (Config) reading " << configFileName << endl;
@@ -716,8 +733,14 @@ class HemoCell {
   // ---- the rest of hemocell.h:86-253.  Features outside the path are refused the way the reference refuses
   // what it cannot do -- a line in the log and exit(1) -- never ignored
   void refuse(const char *what) { hlog << "(HemoCell) (GPU backend) " << what << " is not part of this back end (DESIGN.md section 0), exiting ..." << endl; std::exit(1); }
-  void enableSolidifyMechanics(string) { refuse("solidify mechanics (enableSolidifyMechanics)"); }
-  void setSolidifyTimeScaleSeperation(unsigned int) { refuse("solidify mechanics (setSolidifyTimeScaleSeperation)"); }
+  // hemocell.h: the type takes part in the solidify check; its two thresholds come from its own <MaterialModel>
+  // (core/hemoCellParticleField.cpp:1057-1058).  The type is marked on the device when it is bound, or now when it is already.
+  inline void enableSolidifyMechanics(string name);
+  void setSolidifyTimeScaleSeperation(unsigned int separation) {   // core/hemoCell.cpp:399-402
+    hlog << "(HemoCell) (Solidify Timescale Seperation) Setting seperation to " << separation << " timesteps" << endl;
+    flush();
+    cellfields->solidifyTimescale = separation; cellfields->solidifyPushed = false;
+  }
   void setInteriorViscosityTimeScaleSeperation(unsigned int separation, unsigned int separation_entire_grid) {   // core/hemoCell.cpp:404-410
     hlog << "(HemoCell) (Interior Viscosity Timescale Seperation) Setting seperation to " << separation << " timesteps" << endl;
     hlog << "(HemoCell) (Interior Viscosity Timescale Seperation) Setting entire grid refresh to " << separation_entire_grid << " timesteps" << endl;
@@ -789,6 +812,11 @@ class HemoCell {
       lattice->device();
       if (cellfields->CEPACfield) cellfields->CEPACfield->device();   // hc_iterate steps the scalar its lattice has
       interiorViscositySanity(c);
+      if (global.enableSolidifyMechanics || !cellfields->bindingBoxes.empty()) {
+        if (global.enableSolidifyMechanics) cellfields->checkSolidify();
+        cellfields->bindingDevice();
+        if (!cellfields->solidifyPushed) { hc_check(hcp_set_solidify_timescale(c, (int)cellfields->solidifyTimescale), "hcp_set_solidify_timescale"); cellfields->solidifyPushed = true; }
+      }
       queued_timescale = cellfields->particleVelocityUpdateTimescale;
     }
     const bool particle_step = iter % cellfields->particleVelocityUpdateTimescale == 0;
@@ -951,6 +979,7 @@ inline hc_cells *HemoCellFields::device() {
       // core/hemoCellField.cpp:102-116: the type's nodes relax with omega = 1 / interiorViscosityTau (the library refuses other
       // models than RbcHighOrderModel, slabs, open boundaries, Lees-Edwards and a pre-inlet beside it, each with its message)
       if (f->doInteriorViscosity) { hc_check(hcp_type_set_interior_viscosity(dev, index, f->interiorViscosityTau), "hcp_type_set_interior_viscosity"); interiorViscosity = true; }
+      if (f->doSolidifyMechanics) { checkSolidify(); hc_check(hcp_type_set_solidify(dev, index, f->solidifyDistanceThreshold, f->solidifyShearThreshold), "hcp_type_set_solidify"); }
     }
     types_bound = true;
   }
@@ -1009,6 +1038,43 @@ inline void HemoCellFields::applyBoundaryRepulsionForce() {
   hc_check(hcp_boundary_repulsion(c), "hcp_boundary_repulsion"); particleField.invalidate();
 }
 inline void HemoCellFields::refuse(const char *what) { hemocell.refuse(what); }
+inline bool HemoCellFields::solidifyCombines() {
+  auto *L = hemocell.lattice;
+  bool visc = interiorViscosity;
+  for (auto *f : cellFields) visc = visc || f->doInteriorViscosity;
+  return global.world == 1 && !hemocell.preInlet && !visc && !(L && (L->le.on || !L->open_decls.empty()));
+}
+inline bool HemoCellFields::hemocell_solidify() const { return global.enableSolidifyMechanics != 0; }
+inline void HemoCellFields::populateBindingSites(plb::Box3D *box) {
+  if (!solidifyCombines()) refuse("binding sites (populateBindingSites)");
+  bindingBoxes.push_back(box ? *box : hemocell.lattice->getBoundingBox());
+  bindingDevice();
+}
+inline hc_lattice *HemoCellFields::bindingDevice() {
+  auto *L = hemocell.lattice;
+  hc_lattice *d = L->device();
+  if (bindingGeneration != L->dev_generation) { bindingGeneration = L->dev_generation; bindingApplied = 0; }
+  for (; bindingApplied < bindingBoxes.size(); bindingApplied++) {
+    const plb::Box3D &b = bindingBoxes[bindingApplied];
+    const int box[6] = {(int)b.x0, (int)b.x1, (int)b.y0, (int)b.y1, (int)b.z0, (int)b.z1};
+    hc_check(hcl_binding_populate(d, box), "hcl_binding_populate");
+  }
+  return d;
+}
+inline void HemoCell::enableSolidifyMechanics(string name) {
+  HemoCellField *f = (*cellfields)[name];
+  hlog << "(HemoCell) (Solidify) Enabling solidify mechanics for " << name << endl;
+  if (!cellfields->solidifyCombines()) cellfields->refuse("solidify mechanics (solidifyCells)");
+  try {
+    f->solidifyDistanceThreshold = (*f->materialCfg)["MaterialModel"]["distanceThreshold"].read<T>();
+    f->solidifyShearThreshold = (*f->materialCfg)["MaterialModel"]["shearThreshold"].read<T>();
+  } catch (std::invalid_argument &) {
+    hlog << "(HemoCell) (Solidify) " << name << ".xml needs <distanceThreshold> and <shearThreshold> in its <MaterialModel>, exiting ..." << endl; std::exit(1);
+  }
+  f->doSolidifyMechanics = true;
+  global.enableSolidifyMechanics = 1;
+  if (cellfields->types_bound) hc_check(hcp_type_set_solidify(cellfields->device(), (int)f->ctype, f->solidifyDistanceThreshold, f->solidifyShearThreshold), "hcp_type_set_solidify");
+}
 inline bool HemoCellFields::CEPACcombines() {
   auto *L = hemocell.lattice;
   bool visc = interiorViscosity;
@@ -1114,6 +1180,7 @@ inline void HemoCell::loadParticles() {
 // root with the iteration); the binary format here is this back end's own: populations in the reference node
 // order, then per type the cell ids and the vertex position / velocity / force arrays.
 constexpr long CEPAC_CHECKPOINT_MARK = -0x43455041L;   // "CEPA", negated
+constexpr long SOLIDIFY_CHECKPOINT_MARK = -0x534f4c49L;   // "SOLI", negated
 inline string checkpoint_file(const string &dir) { return dir + (global.world > 1 ? "/checkpoint." + std::to_string(global.rank) + ".bin" : string("/checkpoint.bin")); }
 
 inline void HemoCell::saveCheckPoint() {
@@ -1175,6 +1242,19 @@ inline void HemoCell::saveCheckPoint() {
       o.write((const char *)b, sizeof(b)); o.write((const char *)&op.C, sizeof(double));
     }
   }
+  // solidify mechanics (bindingFieldHelper::checkpoint, core/hemoCell.cpp:213-215): a marker, the binding field, the mask the device
+  // holds now (nodes solidified since the start included) and the flag of every vertex, in the order of the records' cells
+  if (global.enableSolidifyMechanics || !cellfields->bindingBoxes.empty()) {
+    hc_lattice *b = cellfields->bindingDevice();
+    vector<uint8_t> sites(n), walls(n), flags((size_t)nvt);
+    hc_check(hcl_binding_download(b, sites.data()), "hcl_binding_download");
+    hc_check(hcl_download_mask(b, walls.data()), "hcl_download_mask");
+    hc_check(hcp_solidify_flags_download(c, flags.data()), "hcp_solidify_flags_download");
+    const long mark[3] = {SOLIDIFY_CHECKPOINT_MARK, (long)n, nvt};
+    o.write((const char *)mark, sizeof(mark));
+    o.write((const char *)sites.data(), (std::streamsize)n); o.write((const char *)walls.data(), (std::streamsize)n);
+    o.write((const char *)flags.data(), (std::streamsize)flags.size());
+  }
   o.close();
   if (!o) { hlog << "(HemoCell) (saveCheckPoint) could not write " << tmp_name << endl; std::exit(1); }
   rename(final_name.c_str(), (final_name + ".old").c_str());
@@ -1231,7 +1311,8 @@ inline void HemoCell::loadCheckPoint() {
   hc_check(hcp_upload_records(c, rec.data(), nrec), "hcp_upload_records");
   // core/hemoCellFields.cpp:272-274: load, syncEnvelopes, deleteIncompleteCells -- a checkpoint written while a cell had lost
   // particles at a wall (removeParticles(1)) holds that cell incomplete
-  hc_check(hcp_delete_incomplete_cells(c, nullptr), "hcp_delete_incomplete_cells");
+  const bool solid_run = global.enableSolidifyMechanics || !cellfields->bindingBoxes.empty();
+  if (!solid_run) hc_check(hcp_delete_incomplete_cells(c, nullptr), "hcp_delete_incomplete_cells");   // (a solidify run: once the flags are in, below)
   {   // the class field of a run with interior viscosity (binding the types above has enabled it on the lattice)
     int nclasses = 0; hc_check(hcl_interior_info(d, &nclasses, nullptr), "hcl_interior_info");
     const std::streampos at = in.tellg();
@@ -1247,6 +1328,7 @@ inline void HemoCell::loadCheckPoint() {
     }
   }
   {   // the CEPAC field: populations and sources replace what the driver's set-up gave the scalar
+    const std::streampos at_cepac = in.tellg();
     long mark[3] = {0, 0, 0}; in.read((char *)mark, sizeof(mark));
     const bool present = in.good() && mark[0] == CEPAC_CHECKPOINT_MARK && mark[1] == (long)n && mark[2] >= 0;
     CEPACField *cf = cellfields->CEPACfield;
@@ -1270,6 +1352,23 @@ inline void HemoCell::loadCheckPoint() {
         for (const CEPACField::Op &op : sources) cf->add(1, op.box, op.C);
       }
     }
+    else { in.clear(); in.seekg(at_cepac); }   // the end of the file, or the block of another feature
+  }
+  if (solid_run) {   // solidify mechanics (bindingFieldHelper::restore, core/hemoCell.cpp:202-204): sites, grown walls and flags replace the set-up's
+    long nvt = 0; hcp_counts(c, &nvt, nullptr, nullptr);
+    long mark[3] = {0, 0, 0}; in.read((char *)mark, sizeof(mark));
+    if (!(in.good() && mark[0] == SOLIDIFY_CHECKPOINT_MARK && mark[1] == (long)n && mark[2] == nvt)) {
+      hlog << "(HemoCell) (loadCheckPoint) the checkpoint holds no binding field for this case, and this run has solidify mechanics" << endl; std::exit(1);
+    }
+    vector<uint8_t> sites(n), walls(n), flags((size_t)nvt);
+    in.read((char *)sites.data(), (std::streamsize)n); in.read((char *)walls.data(), (std::streamsize)n); in.read((char *)flags.data(), (std::streamsize)flags.size());
+    if (!in.good()) truncated();
+    hc_lattice *b = cellfields->bindingDevice();
+    hc_check(hcl_upload_solidified_mask(b, walls.data()), "hcl_upload_solidified_mask");
+    hc_check(hcl_binding_upload(b, sites.data()), "hcl_binding_upload");
+    bool typed = false; for (auto *f : cellfields->cellFields) typed = typed || f->doSolidifyMechanics;
+    if (typed && nvt) hc_check(hcp_solidify_flags_upload(c, flags.data()), "hcp_solidify_flags_upload");
+    hc_check(hcp_delete_incomplete_cells(c, nullptr), "hcp_delete_incomplete_cells");
   }
   long nct = 0; hcp_counts(c, nullptr, &nct, nullptr);
   cellfields->number_of_cells = (int)nct;

@@ -1,7 +1,7 @@
 // Internal declarations shared by the translation units that work on membrane vertices
 // (cells.hip: storage and stepping, ibm.hip: spread / interpolate, mechanics.hip: membrane models,
 // exchange.hip: slab envelopes and statistics, repulsion.hip: vertex-vertex and boundary repulsion,
-// preinlet.hip: cell injection and the outflow sink).
+// preinlet.hip: cell injection and the outflow sink, solidify.hip: binding sites and solidification).
 //
 // Layout (HBM): vertices are a structure of arrays pos/vel/frc[3][n], cell major (a cell's nv vertices are
 // contiguous, cells of one type contiguous in a fixed-capacity region), so a wavefront touches 64 consecutive
@@ -89,7 +89,19 @@ struct hc_cells {
   int visc_every = 1, visc_grid_every = 1;
   Staged<int> visc_rank; std::vector<long> visc_ids_seen;   // the ids (per marked type, behind a separator) the staged ranks were formed from
   bool visc_on() const { for (int t = 0; t < ntypes; t++) if (visc_class[t]) return true; return false; }
-  long n_deleted = 0;              // cells removed entirely
+  // solidify mechanics (solidify.hip): per type the two thresholds of its <MaterialModel> (solid_on[t] = 0: the type takes no
+  // part), the cadence of the check inside hc_iterate, and a one-byte flag per vertex that exists once a type is enabled and
+  // travels with the cells through the host staging (HostCells::sflag).  d_solid = {cells solidified, nodes solidified} since
+  // the container was made, counted on the device; h_solid is where solidify_refresh_mask reads them, and solid_nodes_seen the
+  // node count the lattice's host mask was last refreshed at.  A solidified cell also counts in d_ntag[0] and d_ntag[3], so
+  // that the compaction takes it out and n_deleted leaves it out.
+  int solid_on[8] = {0}; double solid_dist[8] = {0}, solid_shear[8] = {0};
+  int solid_every = 1;
+  DevBuf<unsigned char> d_sflag;   // [cap]
+  DevBuf<int> d_solid; MappedBuf<int> h_solid;
+  long solid_nodes_seen = 0;
+  bool solidify_on() const { for (int t = 0; t < ntypes; t++) if (solid_on[t]) return true; return false; }
+  long n_deleted = 0;              // cells removed entirely (by a wall or by the caller; solidified cells are counted apart)
   long n_particles_deleted = 0;    // single particles removed (reference mode), including those of cells removed later
 };
 
@@ -207,6 +219,10 @@ int sync_to_host(hc_cells *C);     // device arrays -> host staging before host-
 // advance ran since the last time) and compacts gone cells away.  Every entry point that reports or edits cells calls it.
 int settle(hc_cells *C);
 TypeArrays vert_arrays(hc_cells *C, int t);
+int ensure_sflag(hc_cells *C);     // solidify.hip: the flag array, zeroed, once a type is enabled and the vertex arrays exist
+int solidify_refresh_mask(hc_cells *C);   // solidify.hip: hmask follows the device mask when nodes were solidified since (one host wait)
+int solidify_check(hc_cells *C);   // solidify.hip: prepare, then flag, as hc_iterate runs them; no host wait
+const char *solidify_refusal(const hc_lattice *L);   // solidify.hip: what on the lattice the feature does not combine with, or null
 int ensure_rep(hc_cells *C);       // the three force_repulsion arrays, zeroed, once a repulsion is enabled and the vertex arrays exist
 // stage a small host int array on the device in a persistent scratch slot (through a pinned block; stream ordered)
 int stage_ints(hc_cells *C, int which, int **d, const int *h, int n);

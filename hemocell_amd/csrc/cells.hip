@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void advance_kernel(LatView v, long n, double 
 }
 
 // the counters go to pinned host memory by a one-thread kernel: a copy operation in the stream would hold the next kernel back
-__global__ void publish_counters_kernel(const int *counters, int *host_view) { for (int k = 0; k < 3; k++) host_view[k] = counters[k]; }
-__global__ void sub_counters_kernel(int *counters, int a, int b, int c) { atomicSub(&counters[0], a); atomicSub(&counters[1], b); atomicSub(&counters[2], c); }
+__global__ void publish_counters_kernel(const int *counters, int *host_view) { for (int k = 0; k < 4; k++) host_view[k] = counters[k]; }   // [3]: those of [0] that solidified
+__global__ void sub_counters_kernel(int *counters, int a, int b, int c, int d) { atomicSub(&counters[0], a); atomicSub(&counters[1], b); atomicSub(&counters[2], c); if (d) atomicSub(&counters[3], d); }
 
 // deleteIncompleteCells (core/hemoCellParticleField.cpp:512-553): every incomplete cell goes
 __global__ void delete_incomplete_kernel(long ncells, int *tag, int *counters) {
@@ -73,7 +73,7 @@ namespace hcc {
 // the regions are about to be laid out anew: every array sized by the vertex or cell capacity goes
 static void drop_regions(hc_cells *C) {
   for (int d = 0; d < 3; d++) { C->pos[d].reset(); C->vel[d].reset(); C->frc[d].reset(); C->rep[d].reset(); }
-  C->d_tag.reset(); C->d_vdead.reset(); C->d_vert_cell.reset();
+  C->d_tag.reset(); C->d_vdead.reset(); C->d_vert_cell.reset(); C->d_sflag.reset();
   C->cap = 0; C->tag_cap = 0;
   for (int t = 0; t < 8; t++) C->capc[t] = 0;
 }
@@ -136,6 +136,7 @@ int sync_to_device(hc_cells *C) {
       HC_HIP(hipGetLastError());
     }
   }
+  if (C->solidify_on() && (rc = ensure_sflag(C)) != HC_OK) return rc;   // new regions, or a type enabled since the last layout
   C->nverts = nverts;
   for (int t = 0; t < C->ntypes; t++) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
@@ -146,6 +147,7 @@ int sync_to_device(hc_cells *C) {
   }
   HC_HIP(hipMemsetAsync(C->d_tag, 0, C->tag_cap * sizeof(int), hc::stream()));
   HC_HIP(hipMemsetAsync(C->d_vdead, 0, (size_t)C->cap, hc::stream()));
+  if (C->d_sflag) HC_HIP(hipMemsetAsync(C->d_sflag, 0, (size_t)C->cap, hc::stream()));
   HC_HIP(hipStreamSynchronize(hc::stream()));
   for (int t = 0; t < C->ntypes; t++) {
     const long nc = C->ncells[t], n = nc * C->types[t]->host.nv;
@@ -154,6 +156,7 @@ int sync_to_device(hc_cells *C) {
     const HostCells &H = C->host[t];
     HC_HIP(hipMemcpy(C->d_tag + C->cell0[t], H.tag.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice));
     HC_HIP(hipMemcpy(C->d_vdead + C->first[t], H.dead.data(), (size_t)n, hipMemcpyHostToDevice));
+    if (C->d_sflag) HC_HIP(hipMemcpy(C->d_sflag + C->first[t], H.sflag.data(), (size_t)n, hipMemcpyHostToDevice));
     if (H.has_rep && C->rep[0] && (rc = upload_xyz(C->rep, C->first[t], H.rep.data(), n)) != HC_OK) return rc;
   }
   C->host_dirty = false;
@@ -176,6 +179,7 @@ int sync_to_host(hc_cells *C) {
       HC_HIP(hipMemcpy(H.tag.data(), C->d_tag + C->cell0[t], (size_t)C->ncells[t] * sizeof(int), hipMemcpyDeviceToHost));
       HC_HIP(hipMemcpy(H.dead.data(), C->d_vdead + C->first[t], (size_t)n, hipMemcpyDeviceToHost));
     }
+    if (C->d_sflag) HC_HIP(hipMemcpy(H.sflag.data(), C->d_sflag + C->first[t], (size_t)n, hipMemcpyDeviceToHost));
     if (H.has_rep && (rc = download_xyz(H.rep.data(), C->rep, C->first[t], n)) != HC_OK) return rc;
   }
   return HC_OK;
@@ -699,13 +703,14 @@ static int compact_gone(hc_cells *C) {
 
 // the counters have landed in the pinned block: account for them, compact when cells are gone
 static int apply_counters(hc_cells *C) {
-  const int gone = C->h_ntag[0];
+  const int gone = C->h_ntag[0], solidified = C->h_ntag[3];
   C->n_particles_deleted += C->h_ntag[2];
   if (C->h_ntag[0] == 0 && C->h_ntag[2] == 0) return HC_OK;
   // take off what was read, not more: advance kernels enqueued after that read may have counted further deletions already
-  hipLaunchKernelGGL(sub_counters_kernel, dim3(1), dim3(1), 0, hc::stream(), C->d_ntag, C->h_ntag[0], C->h_ntag[1], C->h_ntag[2]);
+  hipLaunchKernelGGL(sub_counters_kernel, dim3(1), dim3(1), 0, hc::stream(), C->d_ntag, C->h_ntag[0], C->h_ntag[1], C->h_ntag[2], solidified);
   HC_HIP(hipGetLastError());
-  C->h_ntag[0] = C->h_ntag[1] = C->h_ntag[2] = 0;
+  C->h_ntag[0] = C->h_ntag[1] = C->h_ntag[2] = C->h_ntag[3] = 0;
+  C->n_deleted -= solidified;   // compact_gone counts every gone cell as deleted: the solidified ones are counted apart
   return gone ? compact_gone(C) : HC_OK;
 }
 
@@ -826,6 +831,11 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
   const bool visc = C->visc_on();
   if (visc) HC_REQUIRE(C->visc_every % particle_timescale == 0 && C->visc_grid_every % particle_timescale == 0,
                        "hc_iterate: the velocity-update timescale must divide both interior-viscosity timescales (hcp_set_interior_timescales)");
+  // Solidify mechanics (core/hemoCell.cpp:334-340): prepare, then flag, between the interpolation and the advance of every
+  // iteration the cadence names, whether or not it is a velocity-update step.  Such an iteration runs on the main timeline
+  // alone; nothing inside the check waits for the host.  The lattice's host mask follows once, before the call returns.
+  const bool solid = C->solidify_on();
+  if (solid) { const char *why = solidify_refusal(L); if (why) { hc::set_error(std::string("hc_iterate: ") + why); return HC_ERR_STATE; } }
   struct ForkGuard { ~ForkGuard() { if (hc::forked()) hc::join(); else hc::route(0); } } guard;   // error paths leave one timeline behind
   const bool may_overlap = g_overlap && !C->rep_enabled && !C->brep_enabled;
   bool spread_done = false;
@@ -842,7 +852,8 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     spread_done = false;
     const bool particle_step = it % particle_timescale == 0;
     const bool visc_grid = visc && it % C->visc_grid_every == 0, visc_membrane = visc && it % C->visc_every == 0;
-    const bool overlap = may_overlap && !particle_step && !visc_grid && !visc_membrane && s + 1 < n;
+    const bool solid_check = solid && it % C->solid_every == 0;
+    const bool overlap = may_overlap && !particle_step && !visc_grid && !visc_membrane && !solid_check && s + 1 < n;
     if (overlap && (rc = hc::fork()) != HC_OK) return rc;
     if ((rc = hcl_collide_stream_part(L, 0)) != HC_OK) return rc;               // :317
     hcl_step_end(L);
@@ -854,6 +865,7 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     // collide consumed, which nothing on the side stream writes
     if (L->scalar && (rc = hcl_scalar_step(L->scalar)) != HC_OK) return rc;
     if (particle_step) { if ((rc = hcp_interpolate(C)) != HC_OK) return rc; }   // :327-332
+    if (solid_check) { if ((rc = solidify_check(C)) != HC_OK) return rc; }      // :334-340
     if (overlap) hc::route(1);
     if ((rc = hcp_advance(C, 0)) != HC_OK) return rc;                           // :342
     if ((rc = hcp_mechanics(C, it, 0)) != HC_OK) return rc;                     // :345
@@ -869,7 +881,8 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     *iter = it + 1;                                                             // :374 (force zeroing is fused into the collide kernel)
     if (!overlap && (it + 1) % deletion_check_every == 0 && s + 1 < n) { if ((rc = poll_deletions(C, true)) != HC_OK) return rc; }   // on the main timeline only
   }
-  return poll_deletions(C, true);
+  if ((rc = poll_deletions(C, true)) != HC_OK) return rc;
+  return solid ? solidify_refresh_mask(C) : HC_OK;
 }
 
 }  // extern "C"

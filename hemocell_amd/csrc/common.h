@@ -102,7 +102,7 @@ template <class T> struct Staged {
 };
 
 // per-kernel hipEvent timing (hc_profile_*)
-enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_SCALAR, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
+enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_SCALAR, PK_SOLIDIFY_PREPARE, PK_SOLIDIFY_FLAG, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
 void prof_count(int kernel);   // one more launch of `kernel`, without a time (while profiling is on)
 struct ProfScope {
   int k; bool on;
@@ -298,6 +298,10 @@ struct hc_lattice {
   // iteration.  It does not combine with open boundaries, Lees-Edwards, interior viscosity or a pre-inlet: each of those calls
   // refuses a lattice that has one, and hcl_scalar_create a lattice that has any of them.
   hc_scalar *scalar = nullptr;
+  // Solidify mechanics (solidify.hip): the binding field, one byte per node, 1 = a binding site.  Allocated, all 0, by the first
+  // hcl_binding_* call.  hcp_solidify_prepare turns fluid nodes into bounce-back nodes and binding sites while a run is
+  // queued: it writes mask, binding and wallbrick on the device, and hmask follows at the end of the call that ran it.
+  hc::DevBuf<uint8_t> binding;   // [npad], device
   hc::DevBuf<int> ob_list;      // staging of hcl_plane_velocity's node list
   hc::DevBuf<double> ob_out;    // ... and of its output when the caller's buffer is on the host
 };

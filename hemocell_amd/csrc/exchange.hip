@@ -214,6 +214,7 @@ int hcp_pack_cells(hc_cells *C, int type, const int *slots, int n, double x_shif
 
 int hcp_unpack_cells(hc_cells *C, int type, const int *slots, const long *cell_ids, const int *is_new, int n, const double *dev_buf) {
   HC_REQUIRE(C && type >= 0 && type < C->ntypes && n >= 0, "hcp_unpack_cells: bad arguments");
+  HC_REQUIRE(!C->solidify_on(), "hcp_unpack_cells: the slot moves of the slab exchange do not carry the solidify flags; solidify mechanics run on one domain");
   if (n == 0) return HC_OK;
   HC_REQUIRE(slots && cell_ids && is_new && dev_buf, "hcp_unpack_cells: null pointer");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
@@ -234,6 +235,7 @@ int hcp_unpack_cells(hc_cells *C, int type, const int *slots, const long *cell_i
 
 int hcp_remove_cells(hc_cells *C, int type, const int *slots, int n) {
   HC_REQUIRE(C && type >= 0 && type < C->ntypes && n >= 0, "hcp_remove_cells: bad arguments");
+  HC_REQUIRE(!C->solidify_on(), "hcp_remove_cells: the slot moves of the slab exchange do not carry the solidify flags; solidify mechanics run on one domain");
   if (n == 0) return HC_OK;
   HC_REQUIRE(slots, "hcp_remove_cells: null pointer");
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;

@@ -6,7 +6,8 @@
 //    second half of that span); outside it the payload arrays keep stale sizes and contents and nobody reads them.
 //  - Whenever the payload is held, every payload array is sized to ids.size(): pos, vel, frc 3 * nv per cell ([cell][vertex][xyz]);
 //    tag 1 per cell (0 complete, 2 incomplete; a gone cell, 1, lives only until compact drops it); dead nv per cell (1 = this
-//    particle was removed, reference deletion mode); rep (force_repulsion) 3 * nv per cell if and only if has_rep, else empty.
+//    particle was removed, reference deletion mode); sflag nv per cell (1 = the particle carries the solidify flag);
+//    rep (force_repulsion) 3 * nv per cell if and only if has_rep, else empty.
 //  - No code outside this struct infers anything from a vector's size: has_rep says whether rep is there, cells() how many.
 // cells() and hc_cells::ncells[t] are two numbers on purpose: ncells is what the device regions hold, and the two differ while
 // host_dirty is set (cells appended or compacted on the host and not yet uploaded).
@@ -20,7 +21,7 @@ struct HostCells {
   std::vector<long> ids;
   std::vector<double> pos, vel, frc, rep;
   std::vector<int> tag;
-  std::vector<unsigned char> dead;
+  std::vector<unsigned char> dead, sflag;
   bool has_rep = false;
 
   size_t cells() const { return ids.size(); }
@@ -34,10 +35,10 @@ struct HostCells {
   void fit() {
     const size_t n = cells() * (size_t)nv;
     pos.resize(3 * n, 0.0); vel.resize(3 * n, 0.0); frc.resize(3 * n, 0.0); rep.resize(has_rep ? 3 * n : 0, 0.0);
-    tag.resize(cells(), 0); dead.resize(n, 0);
+    tag.resize(cells(), 0); dead.resize(n, 0); sflag.resize(n, 0);
   }
-  // for a download of cells() cells: tag, dead and rep zeroed (all complete, all live), pos / vel / frc to be overwritten
-  void size_payload(bool with_rep) { has_rep = with_rep; rep.clear(); tag.clear(); dead.clear(); fit(); }
+  // for a download of cells() cells: tag, dead, sflag and rep zeroed (all complete, all live, none flagged), pos / vel / frc to be overwritten
+  void size_payload(bool with_rep) { has_rep = with_rep; rep.clear(); tag.clear(); dead.clear(); sflag.clear(); fit(); }
   // one more cell, zero in every array; returns its positions [nv][3] for the caller to write.  A repulsion enabled since
   // the payload was taken (with_rep and not yet has_rep) gives the cells already here a zero force_repulsion.
   double *append(long id, bool with_rep) {
@@ -57,6 +58,7 @@ struct HostCells {
       if (w != c) {
         move(pos); move(vel); move(frc); if (has_rep) move(rep);
         std::copy(dead.begin() + c * k, dead.begin() + (c + 1) * k, dead.begin() + w * k);
+        std::copy(sflag.begin() + c * k, sflag.begin() + (c + 1) * k, sflag.begin() + w * k);
         tag[w] = tag[c]; ids[w] = ids[c];
       }
       w++;

@@ -560,7 +560,7 @@ int hcp_slab_sync_placement(hc_cells *C, long *global_cells_per_type) {
     }
     if (w != nc) {
       // dropping a cell resets the deletion state of the cells that stay: every survivor becomes complete and whole
-      H.tag.assign(w, 0); H.dead.assign(w * (size_t)H.nv, 0);
+      H.tag.assign(w, 0); H.dead.assign(w * (size_t)H.nv, 0); H.sflag.assign(w * (size_t)H.nv, 0);
       C->host_dirty = true;
     }
   }

@@ -374,6 +374,49 @@ class Lattice:
         check(self.lib.hcl_interior_download_classes(self.ptr, out.ctypes.data))
         return out
 
+    # solidify mechanics (SOLIDIFY_MECHANICS builds of the reference): the binding field, one byte per node
+    def populateBindingSites(self, box):
+        """populateBindingSites(box): every boundary node of the inclusive box (x0, x1, y0, y1, z0, z1) with a fluid node
+        among its 26 neighbours becomes a binding site; calls add up"""
+        b = [int(v) for v in box]
+        if len(b) != 6:
+            raise HcError("a box is (x0, x1, y0, y1, z0, z1), got %r" % (box,))
+        check(self.lib.hcl_binding_populate(self.ptr, (C.c_int * 6)(*b)))
+
+    def bindingSites(self):
+        """uint8 [nx][ny][nz]: 1 = a binding site"""
+        out = np.empty((self.nx, self.ny, self.nz), dtype=np.uint8)
+        check(self.lib.hcl_binding_download(self.ptr, out.ctypes.data))
+        return out
+
+    def setBindingSites(self, sites):
+        ss = np.ascontiguousarray(sites, dtype=np.uint8)
+        if ss.size != self.n:
+            raise HcError("the binding field must have %d entries, got %d" % (self.n, ss.size))
+        check(self.lib.hcl_binding_upload(self.ptr, ss.ctypes.data))
+
+    def clearBindingSites(self):
+        check(self.lib.hcl_binding_clear(self.ptr))
+
+    def mask(self):
+        """uint8 [nx][ny][nz]: the mask classes the device holds now (0 fluid, 1 bounce-back, 2 inert solid, 3..6 moving
+        walls), nodes solidified since defineBounceBack included"""
+        out = np.empty((self.nx, self.ny, self.nz), dtype=np.uint8)
+        check(self.lib.hcl_download_mask(self.ptr, out.ctypes.data))
+        return out
+
+    def node_counts(self):
+        """(nodes, fluid nodes, nodes the collide visits)"""
+        o = (C.c_long * 3)()
+        check(self.lib.hcl_node_counts(self.ptr, o))
+        return tuple(int(v) for v in o)
+
+    def tresca(self):
+        """eigenValueFromCell per node: (lambda_max - lambda_min) / 2 of S = -omega 3 / (2 rho) PiNeq; 0 off the fluid"""
+        out = np.empty(self.n, dtype=np.float64)
+        check(self.lib.hcl_download_tresca(self.ptr, dptr(out)))
+        return out
+
     def createCEPACfield(self, tau):
         """the CEPAC scalar field of this lattice (core/hemoCellFields.cpp:120-133), relaxing with omega = 1 / tau:
         diffusivity (tau - 0.5) / 3 in lattice units"""
@@ -735,8 +778,10 @@ class CellType:
 
     def __init__(self, P, model, shape, radius, min_triangles, kLink, kArea, kVolume, kBend, eta_m=0.0,
                  aspect_ratio=0.3, inner_edges=None, wbc=None, kInnerLink=None, stl=None, ex=False,
-                 interior_viscosity=False, viscosity_ratio=None):
-        """interior_viscosity, viscosity_ratio: <enableInteriorViscosity> and <viscosityRatio> of the cell XML
+                 interior_viscosity=False, viscosity_ratio=None, solidify=None):
+        """solidify: (distanceThreshold in lattice units, shearThreshold) of the cell XML's <MaterialModel>, for
+        MODEL_PLT_SIMPLE: Cells.addCellType then enables solidify mechanics for the type (enableSolidifyMechanics).
+        interior_viscosity, viscosity_ratio: <enableInteriorViscosity> and <viscosityRatio> of the cell XML
         (core/hemoCellField.cpp:100-112): Cells.addCellType then marks the type with tau_int = ratio (tau - 0.5) + 0.5.
         wbc: (kInnerRigid, kCytoskeleton, coreRadius, radius) in SI units, for MODEL_WBC_HO only;
         kInnerLink: for MODEL_RBC_MALARIA only; stl: the STL file of shape MESH_FROM_STL (any model).
@@ -785,6 +830,7 @@ class CellType:
         if interior_viscosity and viscosity_ratio is None:
             raise HcError("interior_viscosity=True needs viscosity_ratio=")
         self.interior_viscosity = bool(interior_viscosity)
+        self.solidify = None if solidify is None else (float(solidify[0]), float(solidify[1]))
         self.interiorViscosityTau = None if viscosity_ratio is None else float(viscosity_ratio) * (P.tau - 0.5) + 0.5
 
     @classmethod
@@ -889,7 +935,44 @@ class Cells:
         self.types.append(celltype)
         if getattr(celltype, "interior_viscosity", False):
             check(self.lib.hcp_type_set_interior_viscosity(self.ptr, idx.value, celltype.interiorViscosityTau))
+        if getattr(celltype, "solidify", None) is not None:
+            self.enableSolidifyMechanics(idx.value, *celltype.solidify)
         return idx.value
+
+    # solidify mechanics (core/hemoCell.cpp:334-340; core/hemoCellParticleField.cpp:1002-1065)
+    def enableSolidifyMechanics(self, type_index, distance_threshold_lu, shear_threshold):
+        check(self.lib.hcp_type_set_solidify(self.ptr, int(type_index), float(distance_threshold_lu), float(shear_threshold)))
+
+    def setSolidifyTimeScaleSeparation(self, n):
+        """iterate() then runs prepareSolidification and solidifyCells every n iterations, before advanceParticles"""
+        check(self.lib.hcp_set_solidify_timescale(self.ptr, int(n)))
+
+    def prepareSolidification(self):
+        """every complete cell of an enabled type with a flagged vertex turns its inner fluid nodes into wall nodes and
+        binding sites, and leaves"""
+        check(self.lib.hcp_solidify_prepare(self.ptr))
+
+    def solidifyCells(self):
+        """flags the vertices of enabled types that lie near a binding site under enough shear"""
+        check(self.lib.hcp_solidify_flag(self.ptr))
+
+    def solidifyFlags(self):
+        """bool per vertex, in the order of positions"""
+        out = np.empty(self.counts()[0], dtype=np.uint8)
+        check(self.lib.hcp_solidify_flags_download(self.ptr, out.ctypes.data))
+        return out.astype(bool)
+
+    def setSolidifyFlags(self, flags):
+        ff = np.ascontiguousarray(np.asarray(flags).astype(bool), dtype=np.uint8)
+        if ff.shape != (self.counts()[0],):
+            raise HcError("one flag per vertex: expected %d, got %s" % (self.counts()[0], ff.shape))
+        check(self.lib.hcp_solidify_flags_upload(self.ptr, ff.ctypes.data))
+
+    def solidify_counts(self):
+        """(cells solidified, nodes solidified, vertices flagged now)"""
+        o = (C.c_long * 3)()
+        check(self.lib.hcp_solidify_counts(self.ptr, o))
+        return tuple(int(v) for v in o)
 
     # interior viscosity (core/hemoCell.cpp:347-357, 404-410; core/hemoCellParticleField.cpp:745-807)
     def setInteriorViscosityTimeScaleSeparation(self, separation, separation_entire_grid):

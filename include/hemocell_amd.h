@@ -554,6 +554,52 @@ int hcp_interior_membrane(hc_cells *C);
 int hcp_interior_normals(hc_cells *C, int type, double *out);
 /* tests: the workgroup size of the two passes (64, 128, 256 or 512; default 256) -- the class field does not depend on it */
 int hc_debug_interior_block(int threads);
+/* ---- solidify mechanics (SOLIDIFY_MECHANICS builds of the reference: core/hemoCellParticleField.cpp:920-1065,
+ * mechanics/pltSimpleModel.cpp:211-252): platelets that come near a binding site on the wall, under enough shear, turn into
+ * wall nodes, and those nodes become binding sites.
+ * The binding field is one byte per node, 1 = a binding site, allocated (all 0) by the first hcl_binding_* call that writes.
+ * hcl_binding_populate (populateBindingSites): every boundary node (mask != 0) of the inclusive box (x0, x1, y0, y1, z0, z1),
+ * clipped to the lattice, with a fluid node among its 26 neighbours becomes a site; calls add up.  The neighbours wrap on
+ * periodic axes and are dropped beyond a non-periodic end.  hcl_binding_download / _upload move the field as [nx][ny][nz]
+ * bytes (a checkpoint carries it that way), hcl_binding_clear zeroes it.  hcl_download_mask: the mask classes the device
+ * holds now, [nx][ny][nz], nodes solidified since hcl_set_mask included.
+ * hcl_download_tresca (eigenValueFromCell): (lambda_max - lambda_min) / 2 of S = -omega * 3 / (2 rho) * PiNeq on fluid
+ * nodes, PiNeq and rho as hcl_download_pi_neq and hcl_download_rho_u report them; 0 on every other node.  Formed with the
+ * lattice's one omega: refused on slabs, with open boundaries and with interior viscosity.
+ * hcp_type_set_solidify (enableSolidifyMechanics + <distanceThreshold>, <shearThreshold> of the type's <MaterialModel>; the
+ * distance in lattice units): only HC_MODEL_PLT_SIMPLE, thresholds >= 0.  From then on every vertex carries a flag byte (0 for
+ * new vertices), moved by hcp_solidify_flags_download / _upload in the vertex order of hcp_download.
+ * hcp_solidify_prepare (prepareSolidification): every complete cell of an enabled type with a flagged vertex turns the fluid
+ * nodes inside it (the ray cast of hcp_interior_find) into bounce-back nodes and binding sites, populations untouched, and
+ * leaves like a cell that reached a wall.  hcp_solidify_flag (solidifyCells): a live vertex of an enabled type is flagged
+ * when a binding site among its nearest node n = floor(pos + 0.5) and the 26 around it lies within the distance threshold
+ * and |tresca(n) / 1e-7| exceeds the shear threshold; set flags stay set.  Both end by bringing the lattice's host mask up to
+ * date (one host wait).  hc_iterate runs prepare, then flag, without a host wait, between hcp_interpolate and hcp_advance of
+ * every iteration `it` with it % every == 0 (hcp_set_solidify_timescale, default 1; core/hemoCell.cpp:334-340), and refreshes
+ * the host mask once before it returns.  hcp_solidify_counts: {cells solidified, nodes solidified, vertices flagged now};
+ * solidified cells do not count in hcp_counts' n_deleted.  While a type is enabled, hcp_remove_cells and hcp_unpack_cells (the slot
+ * moves of the slab exchange, which do not carry the flags) are refused on that container.
+ * Refused (HC_ERR_ARG from these calls, HC_ERR_STATE from hc_iterate when the other feature came second): n_slabs > 1, open
+ * boundaries, a Lees-Edwards boundary, interior viscosity, a pre-inlet.  A CEPAC field is fine: its step reads the flow's
+ * mask, so a node that turns to wall bounces the scalar back from the next step on. */
+int hcl_binding_populate(hc_lattice *L, const int box[6]);
+int hcl_binding_clear(hc_lattice *L);
+int hcl_binding_download(hc_lattice *L, uint8_t *out);
+int hcl_binding_upload(hc_lattice *L, const uint8_t *in);
+int hcl_download_mask(hc_lattice *L, uint8_t *out);
+int hcl_download_tresca(hc_lattice *L, double *out);
+/* a checkpoint's way back: every node with in[node] != 0 ([nx][ny][nz]) that is fluid now becomes a bounce-back node exactly as
+ * hcp_solidify_prepare leaves it (class 1, populations untouched, wall-brick byte set, host mask refreshed) */
+int hcl_upload_solidified_mask(hc_lattice *L, const uint8_t *in);
+int hcp_type_set_solidify(hc_cells *C, int type, double distance_threshold_lu, double shear_threshold);
+int hcp_set_solidify_timescale(hc_cells *C, int every);
+int hcp_solidify_prepare(hc_cells *C);
+int hcp_solidify_flag(hc_cells *C);
+int hcp_solidify_flags_download(hc_cells *C, unsigned char *out);
+int hcp_solidify_flags_upload(hc_cells *C, const unsigned char *in);
+int hcp_solidify_counts(hc_cells *C, long out[3]);
+/* tests: the workgroup size of the prepare pass (64, 128, 256 or 512; default 256) -- the result does not depend on it */
+int hc_debug_solidify_block(int threads);
 /* HemoCell::iterate() (core/hemoCell.cpp:299-376) n times, followed each time by the driver's body-force
  * re-application (examples/pipeflow/pipeflow.cpp:144-146).  particle_timescale =
  * setParticleVelocityUpdateTimeScaleSeparation. iter is read and advanced.  Particles that reach a wall are deleted on
