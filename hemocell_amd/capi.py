@@ -147,6 +147,8 @@ SIGNATURES = {
     "hcl_scalar_download_velocity": (C.c_int, [VP, c_double_p]),
     "hcl_scalar_stats": (C.c_int, [VP, c_double_p]),
     "hcp_sample_scalar": (C.c_int, [VP, VP, c_double_p]),
+    "hcp_type_set_ibm_kernel": (C.c_int, [VP, C.c_int, C.c_int]),
+    "hcp_type_get_ibm_kernel": (C.c_int, [VP, C.c_int, c_int_p]),
     "hcp_type_set_interior_viscosity": (C.c_int, [VP, C.c_int, C.c_double]),
     "hcp_set_interior_timescales": (C.c_int, [VP, C.c_int, C.c_int]),
     "hcp_interior_find": (C.c_int, [VP]),

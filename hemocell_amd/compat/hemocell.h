@@ -282,6 +282,18 @@ inline void interpolationCoefficientsPhi2(plb::BlockLattice3D<T, DESCRIPTOR> &, 
   std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi2 runs on the device (csrc/ibm.hip); it cannot be called on the host" << std::endl;
   std::exit(1);
 }
+// core/immersedBoundaryMethod.h:140-153 declares these two and the reference has no body for them.  Here
+// field.kernelMethod = interpolationCoefficientsPhi3 (or ...Phi4) selects the three-point (Roma) or four-point (Peskin) delta
+// function of csrc/ibm_wide.hip for the cell type (hcp_type_set_ibm_kernel, include/hemocell_amd.h: the definitions are this
+// back end's own).  Assign before the first call that needs the cells on the device (loadParticles, iterate, ...).
+inline void interpolationCoefficientsPhi3(plb::BlockLattice3D<T, DESCRIPTOR> &, HemoCellParticle &) {
+  std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi3 runs on the device (csrc/ibm_wide.hip); it cannot be called on the host" << std::endl;
+  std::exit(1);
+}
+inline void interpolationCoefficientsPhi4(plb::BlockLattice3D<T, DESCRIPTOR> &, HemoCellParticle &) {
+  std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi4 runs on the device (csrc/ibm_wide.hip); it cannot be called on the host" << std::endl;
+  std::exit(1);
+}
 
 // ------------------------------------------------------------------ mechanics/commonCellConstants.h:38-85
 class CommonCellConstants {
@@ -970,12 +982,14 @@ inline hc_cells *HemoCellFields::device() {
   if (!dev) { hc_check(hcp_create(&dev, hemocell.lattice->device(), &Parameters::raw()), "hcp_create"); hemocell.lattice->cells_bound = true; }
   if (!types_bound) {
     for (auto *f : cellFields) {
-      if (f->kernelMethod != interpolationCoefficientsPhi2) {   // core/hemoCellField.h:67: a user IBM kernel is host code
+      const int ibm_kernel = f->kernelMethod == interpolationCoefficientsPhi3 ? HC_IBM_PHI3 : f->kernelMethod == interpolationCoefficientsPhi4 ? HC_IBM_PHI4 : HC_IBM_PHI2;
+      if (ibm_kernel == HC_IBM_PHI2 && f->kernelMethod != interpolationCoefficientsPhi2) {   // core/hemoCellField.h:67: a user IBM kernel is host code
         hlog << "(HemoCell) (GPU backend) cell type " << f->name << " installs its own IBM kernelMethod; only interpolationCoefficientsPhi2 (core/immersedBoundaryMethod.h:62-138) runs on the device. Exiting." << endl;
         std::exit(1);
       }
       int index = -1;
       hc_check(hcp_add_type(dev, f->dev, (int)f->timescale, &index), "hcp_add_type");
+      if (ibm_kernel != HC_IBM_PHI2) hc_check(hcp_type_set_ibm_kernel(dev, index, ibm_kernel), "hcp_type_set_ibm_kernel");   // refuses slabs, open boundaries, a pre-inlet
       // core/hemoCellField.cpp:102-116: the type's nodes relax with omega = 1 / interiorViscosityTau (the library refuses other
       // models than RbcHighOrderModel, slabs, open boundaries, Lees-Edwards and a pre-inlet beside it, each with its message)
       if (f->doInteriorViscosity) { hc_check(hcp_type_set_interior_viscosity(dev, index, f->interiorViscosityTau), "hcp_type_set_interior_viscosity"); interiorViscosity = true; }

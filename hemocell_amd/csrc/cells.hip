@@ -377,6 +377,7 @@ int hcp_envelope(const hc_cells *C, double *share_in_use, long *late_copies) {
 int hcp_destroy(hc_cells *C) {
   if (!C) return HC_OK;
   (void)hipStreamSynchronize(hc::stream());
+  hc::ibm_wide_remove(C);
   delete C;
   return HC_OK;
 }

@@ -328,6 +328,13 @@ void preinlet_pair_add(const void *owner, const hc_lattice *L);
 void preinlet_pair_remove(const void *owner);
 void preinlet_pair_forget(const hc_lattice *L);   // hcl_destroy: the address may be handed out again
 bool in_preinlet_pair(const hc_lattice *L);
+// The lattices whose containers hold a cell type on a three- or four-point IBM kernel (hcp_type_set_ibm_kernel), for the refusals
+// of open boundaries and the pre-inlet; kept like the list above.  `owner` is the container, once per wide type.
+void ibm_wide_add(const void *owner, const hc_lattice *L);
+void ibm_wide_remove_one(const void *owner);   // a type went back to two points
+void ibm_wide_remove(const void *owner);       // hcp_destroy
+void ibm_wide_forget(const hc_lattice *L);     // hcl_destroy
+bool ibm_wide(const hc_lattice *L);
 }
 
 // slab.hip: HemoCell::iterate / collideAndStream on one x-slab of a multi-GPU run (halo and envelope exchange inside)

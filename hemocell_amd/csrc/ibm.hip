@@ -4,8 +4,7 @@
 //   core/immersedBoundaryMethod.h:62-138          interpolationCoefficientsPhi2 (cells.h: phi2_stencil)
 //   core/hemoCellParticleField.cpp:841-863        spreadParticleForce
 //   core/hemoCellParticleField.cpp:819-839        interpolateFluidVelocity
-#include "cells.h"
-#include <type_traits>
+#include "ibm_common.h"
 #include <hipcub/hipcub.hpp>
 #include <cstdlib>
 #include <cstring>
@@ -95,66 +94,6 @@ __global__ __launch_bounds__(256) void spread_gather_kernel(LatView v, long n, c
   Fn[0] += a0; Fn[1] += a1; Fn[2] += a2;   // this thread alone touches the node
 }
 
-// ----------------------------------------------------------------------------
-// interpolate: v = sum_j w_j * (j/rho + F/2)(node_j) on the post-stream state
-struct PopView {
-  const double *f; const double *F; double bx, by, bz; long qs;   // qs: population stride
-  hc::BodyRegions reg;
-};
-// lattices with Zou-He open boundaries (hc_lattice::ob_n > 0) run the OPEN instantiations of the interpolation kernels: the
-// gathered populations of a fluid open-boundary node are completed (zou_he_node, as the collide is about to) before the moments
-// are taken.  Every other lattice keeps PopView, its kernel-argument block and its code.
-struct OpenPopView : PopView { const int *ob_code; const double *ob_val; };
-template <bool OPEN> using Pops = std::conditional_t<OPEN, OpenPopView, PopView>;
-
-template <bool OPEN = false>
-__device__ __forceinline__ void node_velocity(const LatView &v, const Pops<OPEN> &pv, int lx, int ly, int lz, long node, double u[3]) {
-  // A node on the OUTER halo plane of a slab would pull from beyond the allocation.  Only particles whose nearest node lies
-  // outside the slab have such a node in their stencil, and their interpolated velocity is never used (the owner's record
-  // replaces it, "a local particle wins"), so the value does not matter -- the access must not happen.
-  if (v.halo_x && (lx <= -HALO || lx >= v.nx + HALO - 1)) { u[0] = u[1] = u[2] = 0.0; return; }
-  // first halo plane of a slab: the neighbour that owns the node has evaluated this very expression and sent the result
-  // (3 doubles per node instead of the 19 population planes the gather below would need, slab.hip)
-  if (v.halo_x && (lx == -1 || lx == v.nx)) {
-    const double *hu = v.halo_u[lx < 0 ? 0 : 1];
-    if (hu) { const long k = (long)ly * v.nz + lz; u[0] = hu[k]; u[1] = hu[v.ny_nz + k]; u[2] = hu[2L * v.ny_nz + k]; return; }
-  }
-  // gather S(node,q) = P(node - c_q, q) through the neighbour and wrap rules the collide kernel uses (d3q19.h)
-  const hc::Nbr nb = hc::neighbours(v, v.plane, lx, ly, lz);
-  double r = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
-  [[maybe_unused]] double f[OPEN ? HC_Q : 1];   // OPEN: the gathered populations are kept, completed, and summed afterwards in the same order
-#define M(Q, CX, CY, CZ)                                                              \
-  {                                                                                   \
-    bool ok; const long off = hc::src_off<CX, CY, CZ>(nb, ok);                        \
-    const double fq = ok ? pv.f[(long)Q * pv.qs + node + off] : 0.0;                 \
-    if constexpr (OPEN) f[Q] = fq;                                                    \
-    else {                                                                            \
-      r += fq;                                                                        \
-      if (CX == 1) jx += fq; else if (CX == -1) jx += -fq;                            \
-      if (CY == 1) jy += fq; else if (CY == -1) jy += -fq;                            \
-      if (CZ == 1) jz += fq; else if (CZ == -1) jz += -fq;                            \
-    }                                                                                 \
-  }
-  FOR_Q(M)
-#undef M
-  if constexpr (OPEN) {
-    if (v.mask[node] == 0) {
-      const int code = pv.ob_code[node];
-      if (code >= 0) hc::zou_he_node(f, code, pv.ob_val);
-    }
-    hc::moments(f, r, jx, jy, jz);
-  }
-  const double invRho = 1.0 / (1.0 + r);
-  double bx = pv.bx, by = pv.by, bz = pv.bz;
-  if (pv.reg.n) {   // a halo plane of a slab, or the wrapped image, is the global node next door
-    int xg = v.x0 + lx;
-    if (xg < 0) xg += v.nx_global; else if (xg >= v.nx_global) xg -= v.nx_global;
-    region_force(pv.reg, xg, ly, lz, bx, by, bz);
-  }
-  u[0] = jx * invRho + (bx + pv.F[3 * node]) / 2.0;
-  u[1] = jy * invRho + (by + pv.F[3 * node + 1]) / 2.0;
-  u[2] = jz * invRho + (bz + pv.F[3 * node + 2]) / 2.0;
-}
 
 // node velocities of one face plane of a slab (lx = 0 or nx - 1), for the neighbour whose first halo plane it is.  OPEN: a fluid
 // open-boundary node of the plane sends the moments of its completed populations (a velocity node u_bc + F / 2), the rule the
@@ -205,18 +144,6 @@ __global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, Pops<OP
 constexpr int TILE_CAP = 5832;       // nodes per tile: 18 x 18 x 18, any orientation of a 642-vertex RBC; three workgroups per CU fit the 160 KB LDS
 constexpr int NODE_CAP = 1536;       // distinct nodes of one cell for the interpolation (an RBC touches ~1300)
 
-// bounding box of a cell's stencil nodes: origin o (global), extent e, origin ow in local wrapped coordinates,
-// reciprocals for the index decode
-struct Tile { int o[3]; int e[3]; int vol; int ow[3]; float r1, r2; };
-
-// tile index -> (tx, ty, tz) without integer division.  Exact for i < 2^16: (i + 0.5) / e is at least 0.5 / e
-// away from an integer while the float error stays below 1e-3 / e.
-__device__ __forceinline__ void tile_decode(const Tile &t, int i, int &tx, int &ty, int &tz) {
-  const int q = (int)(((float)i + 0.5f) * t.r2);
-  tz = i - q * t.e[2];
-  tx = (int)(((float)q + 0.5f) * t.r1);
-  ty = q - tx * t.e[1];
-}
 
 __device__ __forceinline__ int stencil_base(const LatView &v, double px, double py, double pz, int b[3]) {
   const double p[3] = {px, py, pz};
@@ -225,16 +152,6 @@ __device__ __forceinline__ int stencil_base(const LatView &v, double px, double 
   return 0;
 }
 
-// global lattice element of tile entry i (only meaningful for entries that were admitted by a stencil)
-__device__ __forceinline__ long tile_node(const LatView &v, const Tile &t, int i, int &lx, int &ly, int &lz) {
-  int tx, ty, tz;
-  tile_decode(t, i, tx, ty, tz);
-  lx = t.ow[0] + tx; ly = t.ow[1] + ty; lz = t.ow[2] + tz;
-  if (v.wrap_x && lx >= v.nx) lx -= v.nx;     // the tile is no wider than the domain (cell_prologue), one wrap suffices
-  if (v.per_y && ly >= v.ny) ly -= v.ny;
-  if (v.per_z && lz >= v.nz) lz -= v.nz;
-  return (long)(lx + HALO) * v.plane + ly * v.nz + lz;
-}
 
 // Workgroups are handed to the 8 XCDs round robin, and every XCD has its own L2.  Cells are stored in placement order,
 // neighbours in space mostly next to each other; giving each XCD a contiguous range of cells lets neighbouring cells,
@@ -251,11 +168,10 @@ __device__ __forceinline__ int xcd_contiguous(int b, int n) {
 struct VStencil { double w[8]; int base; unsigned adm; };   // base = tile index of the lowest corner; adm = admitted-node bits
 
 constexpr int NVPT = 3;        // vertices per thread held in registers (642 vertices / 256 threads)
-// Eight waves per cell (512 threads, two vertices each) were tried for both kernels: the spread gains 3.5 % at 10 % hematocrit
+// Four waves per workgroup (MAXW, ibm_common.h).  Eight waves per cell (512 threads, two vertices each) were tried for both kernels: the spread gains 3.5 % at 10 % hematocrit
 // and nothing at 25 % (and loses once its loads are reordered), the interpolation loses 9-15 % (184 VGPRs: one cell per CU);
 // capping the interpolation at 168 / 128 VGPRs for three cells per CU spills and loses 15 %.  Both kernels wait 80 % of their
 // wave cycles (rocprofv3 SQ_WAIT_ANY + SQ_WAIT_INST_ANY) and respond to neither more waves nor shorter workgroups.
-constexpr int MAXW = 4;        // waves per workgroup
 
 // -DHC_IBM_PHASE_TIMES (scratch builds only): thread 0 of every workgroup adds the shader cycles between consecutive stamps to
 // g_phase[k]; hc_debug_phase_times() reads and clears them
@@ -272,28 +188,6 @@ __device__ unsigned long long g_phase[32];
 #define STAMP(k) do {} while (0)
 #endif
 
-// bounding box of all stencil nodes of the cell: per-thread min/max -> wave shuffles -> LDS -> everyone
-__device__ __forceinline__ void block_bbox(int lo[3], int hi[3], int *s_red, Tile &t) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { lo[a] = min(lo[a], __shfl_xor(lo[a], off)); hi[a] = max(hi[a], __shfl_xor(hi[a], off)); }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) { s_red[(tid >> 6) * 6 + a] = lo[a]; s_red[(tid >> 6) * 6 + 3 + a] = hi[a]; }
-  }
-  __syncthreads();
-  const int nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    int l = s_red[a], h = s_red[3 + a];
-    for (int w = 1; w < nw; w++) { l = min(l, s_red[w * 6 + a]); h = max(h, s_red[w * 6 + 3 + a]); }
-    t.o[a] = l; t.e[a] = h >= l ? h - l + 1 : 0;   // no live vertex at all (every particle of the cell removed): an empty tile
-  }
-  const long vol = (long)t.e[0] * t.e[1] * t.e[2];
-  t.vol = vol > 0x7fffffff ? 0x7fffffff : (int)vol;
-}
 
 // local (wrapped) origin and decode reciprocals; false when the tile cannot be used
 __device__ __forceinline__ bool tile_finish(const LatView &v, Tile &t) {
@@ -306,18 +200,6 @@ __device__ __forceinline__ bool tile_finish(const LatView &v, Tile &t) {
   return true;
 }
 
-// mask class of tile entry i: 0 fluid, 1/2 boundary, 3 not addressable (outside the domain / halo range)
-__device__ __forceinline__ unsigned char tile_mask(const LatView &v, const Tile &t, int i) {
-  int tx, ty, tz;
-  tile_decode(t, i, tx, ty, tz);
-  int lx = t.ow[0] + tx, ly = t.ow[1] + ty, lz = t.ow[2] + tz;
-  if (v.wrap_x) { if (lx >= v.nx) lx -= v.nx; }
-  else if (v.halo_x) { if (lx < -HALO || lx >= v.nx + HALO) return 3; }
-  else if (lx < 0 || lx >= v.nx) return 3;
-  if (v.per_y) { if (ly >= v.ny) ly -= v.ny; } else if (ly < 0 || ly >= v.ny) return 3;
-  if (v.per_z) { if (lz >= v.nz) lz -= v.nz; } else if (lz < 0 || lz >= v.nz) return 3;
-  return v.mask[(long)(lx + HALO) * v.plane + ly * v.nz + lz];
-}
 
 // interpolationCoefficientsPhi2 against the LDS copy of the mask; same arithmetic and visiting order as phi2_stencil
 __device__ __forceinline__ void tile_stencil(const Tile &t, const unsigned char *mt, double px, double py, double pz, const int b[3], VStencil &o) {
@@ -618,25 +500,8 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
   }
 }
 
-// state after hcl_step_end: f[cur] holds the populations just written, force[(fcur+2)%3] the force they were collided with
-PopView make_pops(const hc_lattice *L) {
-  return PopView{L->f[L->cur], L->force[(L->fcur + 2) % 3], L->body[0], L->body[1], L->body[2], (long)L->qstride, L->regions};
-}
-// the arguments of the open-boundary instantiations (hc::launch_open)
-OpenPopView open_of(const hc_lattice *L, const PopView &pv) {
-  OpenPopView o;
-  static_cast<PopView &>(o) = pv;
-  o.ob_code = L->ob_code; o.ob_val = L->ob_val;
-  return o;
-}
 
 }  // namespace
-
-// K<OPEN> through the one open-boundary dispatch (hc::launch_open)
-#define HC_LAUNCH_POPS(K, grid, block, v, pv, ...)                                                                      \
-  hc::launch_open(L, pv, [&](auto open, const auto &pops) {                                                             \
-    hipLaunchKernelGGL(K<decltype(open)::value>, grid, block, 0, hc::stream(), v, pops, __VA_ARGS__);                   \
-  })
 
 static int g_ibm_per_vertex = 0;  // 1: one thread per vertex with direct global atomics (kept for A/B and as reference)
 extern "C" int hc_debug_ibm_per_vertex(int on) { g_ibm_per_vertex = on; return HC_OK; }
@@ -650,8 +515,15 @@ extern "C" int hc_set_reproducible_spread(int on) { g_reproducible = on ? 1 : 0;
 // the gather form of the spread: entries -> stable sort by node -> one sequential sum per node
 static int spread_reproducible(hc_cells *C, int force_limit) {
   const LatView v = make_view(C->L);
-  HC_REQUIRE(v.npad * 3 < 0xffffffffL && C->nverts * 8 < 0x7fffffffL, "reproducible spread: lattice or vertex count beyond its 32-bit keys");
-  const long n_e = C->nverts * 8;
+  // entries: 8 per vertex of a type on two points, 27 or 64 on the wide kernels (ibm_wide.hip).  A type's entries start on a
+  // multiple of 8, the unit spread_emit_kernel counts its base in; entries in between keep an invalid key
+  long n_e = 0, first_e[8];
+  for (int t = 0; t < C->ntypes; t++) {
+    const long w = ibm_width(C, t);
+    first_e[t] = n_e;
+    n_e += (C->ncells[t] * C->types[t]->host.nv * w * w * w + 7) / 8 * 8;
+  }
+  HC_REQUIRE(v.npad * 3 < 0xffffffffL && n_e < 0x7fffffffL, "reproducible spread: lattice or vertex count beyond its 32-bit keys");
   int rc;
   if (n_e > C->det_cap) {
     HC_HIP(hipDeviceSynchronize());
@@ -677,17 +549,18 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
   }
   int *d_order = nullptr;
   rc = stage_ints(C, 2, &d_order, order.data(), (int)order.size()); if (rc != HC_OK) return rc;
-  long ebase = 0;
+  if (C->ibm_wide_on()) HC_HIP(hipMemsetAsync(C->det_keys[0].p, 0xff, (size_t)n_e * sizeof(unsigned int), hc::stream()));   // the entries between two types
   for (int t = 0; t < C->ntypes; t++) {
     const int nv = C->types[t]->host.nv;
     const long n = C->ncells[t] * nv;
     if (n == 0) continue;
+    if (ibm_width(C, t) != HC_IBM_PHI2) { if ((rc = wide_emit(C, t, d_order + obase[(size_t)t], first_e[t], force_limit)) != HC_OK) return rc; continue; }
+    const long ebase = first_e[t] / 8;
     const TypeArrays a = vert_arrays(C, t);   // r is set exactly when rep_on(), see vert_arrays: hcp_spread has synchronised to the device
     hipLaunchKernelGGL(spread_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, nv, n, (const int *)(d_order + obase[(size_t)t]), ebase,
                        a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], force_limit, C->P.f_limit, a.tag, a.dead, C->det_keys[0], C->det_vals[0],
                        C->det_val[0], C->det_val[1], C->det_val[2]);
     HC_HIP(hipGetLastError());
-    ebase += n;
   }
   // only the bits a node index needs: 2^bits > npad, so the low bits of an invalid key (all ones) still sort behind every node
   int bits = 1;
@@ -723,6 +596,7 @@ int hcp_spread(hc_cells *C, int force_limit) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
     const int nv = C->types[t]->host.nv;
+    if (ibm_width(C, t) != HC_IBM_PHI2) { if ((rc = wide_spread(C, t, force_limit, g_ibm_per_vertex)) != HC_OK) return rc; continue; }
     const TypeArrays a = vert_arrays(C, t);   // r is set exactly when rep_on(), see vert_arrays: the sync_to_device above has run
     if (g_ibm_per_vertex)
       hipLaunchKernelGGL(ibm_spread_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2],
@@ -747,6 +621,7 @@ int hcp_interpolate(hc_cells *C) {
     const long n = C->ncells[t] * C->types[t]->host.nv;
     if (n == 0) continue;
     const int nv = C->types[t]->host.nv;
+    if (ibm_width(C, t) != HC_IBM_PHI2) { if ((rc = wide_interpolate(C, t, nullptr, 0, g_ibm_per_vertex)) != HC_OK) return rc; continue; }
     const TypeArrays a = vert_arrays(C, t);
     if (g_ibm_per_vertex)
       HC_LAUNCH_POPS(ibm_interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), v, pv, n, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
@@ -811,6 +686,7 @@ int hcc::interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n
   int *d_slots = nullptr;
   rc = stage_ints(C, which, &d_slots, slots, n); if (rc != HC_OK) return rc;
   hc::ProfScope prof(hc::PK_INTERP);
+  if (ibm_width(C, type) != HC_IBM_PHI2) return wide_interpolate(C, type, d_slots, n, 0);
   const hc_lattice *L = C->L;
   const LatView v = make_view(L);
   const PopView pv = make_pops(L);

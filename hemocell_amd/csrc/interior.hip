@@ -200,6 +200,7 @@ int hcp_type_set_interior_viscosity(hc_cells *C, int type, double tau_int) {
   HC_REQUIRE(C && type >= 0 && type < C->ntypes, "hcp_type_set_interior_viscosity: unknown cell type");
   HC_REQUIRE(C->types[type]->host.model == HC_MODEL_RBC_HO, "hcp_type_set_interior_viscosity: interior viscosity needs the vertex normals of HC_MODEL_RBC_HO (RbcHighOrderModel); no other model carries them");
   HC_REQUIRE(tau_int > 0.5, "hcp_type_set_interior_viscosity: tau_int must exceed 0.5");
+  HC_REQUIRE(C->ibm_kernel[type] == HC_IBM_PHI2, "hcp_type_set_interior_viscosity: the type is on a three- or four-point IBM kernel; the membrane pass walks the eight-node stencil");
   hc_lattice *L = C->L;
   const double omega = 1.0 / tau_int;
   // a type is marked once: a second tau_int would leave the first omega behind as a class no type uses, one of the seven

@@ -673,6 +673,21 @@ void hc::preinlet_pair_forget(const hc_lattice *L) {
 bool hc::in_preinlet_pair(const hc_lattice *L) {
   return std::any_of(g_preinlet_pairs.begin(), g_preinlet_pairs.end(), [&](const auto &e) { return e.second == L; });
 }
+static std::vector<std::pair<const void *, const hc_lattice *>> g_ibm_wide;
+void hc::ibm_wide_add(const void *owner, const hc_lattice *L) { g_ibm_wide.emplace_back(owner, L); }
+void hc::ibm_wide_remove_one(const void *owner) {
+  const auto it = std::find_if(g_ibm_wide.begin(), g_ibm_wide.end(), [&](const auto &e) { return e.first == owner; });
+  if (it != g_ibm_wide.end()) g_ibm_wide.erase(it);
+}
+void hc::ibm_wide_remove(const void *owner) {
+  g_ibm_wide.erase(std::remove_if(g_ibm_wide.begin(), g_ibm_wide.end(), [&](const auto &e) { return e.first == owner; }), g_ibm_wide.end());
+}
+void hc::ibm_wide_forget(const hc_lattice *L) {
+  g_ibm_wide.erase(std::remove_if(g_ibm_wide.begin(), g_ibm_wide.end(), [&](const auto &e) { return e.second == L; }), g_ibm_wide.end());
+}
+bool hc::ibm_wide(const hc_lattice *L) {
+  return std::any_of(g_ibm_wide.begin(), g_ibm_wide.end(), [&](const auto &e) { return e.second == L; });
+}
 
 // the four z-layers a Lees-Edwards pass reads or writes populations of (z = 0, 1, nz-2, nz-1): every bulk node there must
 // be fluid, so that each stored slot the pass writes has the one reader the pass means (mask: device numbering)
@@ -775,6 +790,7 @@ int hcl_destroy(hc_lattice *L) {
   hcs::lattice_destroyed(L);
   hc::scalar_lattice_destroyed(L);
   hc::preinlet_pair_forget(L);
+  hc::ibm_wide_forget(L);
   hipStreamSynchronize(hc::stream());
   delete L;
   return HC_OK;
@@ -1033,6 +1049,8 @@ static int ob_add(const std::string &who, hc_lattice *L, int kind, int axis, int
   HC_REQUIRE(!L->le_on, who + ": the lattice has a Lees-Edwards boundary; open boundaries and Lees-Edwards do not combine");
   // the open-boundary and the interior-viscosity collide are two instantiations; no kernel does both
   HC_REQUIRE(L->visc_n == 0, who + ": the lattice has interior viscosity enabled; interior viscosity and open boundaries do not combine");
+  // the OPEN interpolation exists for the two-point kernels only (hcp_type_set_ibm_kernel)
+  HC_REQUIRE(!hc::ibm_wide(L), who + ": a cell type of the lattice is on a three- or four-point IBM kernel; those and open boundaries do not combine");
   // the scalar step takes plain moments of the flow's populations and knows no open faces of its own
   HC_REQUIRE(!L->scalar, who + ": the lattice has a scalar field; the scalar field and open boundaries do not combine");
   // a node holds one slot: declaring it again (in this call or an earlier one) would orphan the first slot and let the second
@@ -1219,6 +1237,7 @@ int hcl_preinlet_create(hc_preinlet **out, hc_lattice *pre, hc_lattice *domain, 
   HC_REQUIRE(pre->n_slabs == 1, "hcl_preinlet_create: needs n_slabs = 1 on the pre-inlet lattice");
   HC_REQUIRE(pre->visc_n == 0 && domain->visc_n == 0, "hcl_preinlet_create: a lattice has interior viscosity enabled; interior viscosity and a pre-inlet do not combine");
   HC_REQUIRE(!pre->scalar && !domain->scalar, "hcl_preinlet_create: a lattice has a scalar field; the scalar field and a pre-inlet do not combine");
+  HC_REQUIRE(!hc::ibm_wide(pre) && !hc::ibm_wide(domain), "hcl_preinlet_create: a cell type of a lattice is on a three- or four-point IBM kernel; those and a pre-inlet do not combine");
   // a slab domain: the inlet plane of an x direction lies on one rank, whose local slots these are; a y or z plane would span the ranks
   HC_REQUIRE(domain->n_slabs == 1 || axis == 0, "hcl_preinlet_create: axis 1 and 2 need n_slabs = 1 on the domain; a slab domain is coupled along x only (axis 0)");
   HC_REQUIRE(pre_plane >= 0 && pre_plane < axis_extent(pre, axis), "hcl_preinlet_create: plane outside the pre-inlet lattice");

@@ -392,6 +392,7 @@ int hcp_preinlet_create(hc_preinlet_cells **out, hc_cells *pre, hc_cells *domain
   HC_REQUIRE(orientation == -1 || orientation == 1, "hcp_preinlet_create: orientation must be -1 (*neg) or +1 (*pos)");
   HC_REQUIRE(pre->L->n_slabs == 1 && domain->L->n_slabs == 1, "hcp_preinlet_create: needs n_slabs = 1 on both lattices");
   HC_REQUIRE(!pre->L->scalar && !domain->L->scalar, "hcp_preinlet_create: a lattice has a scalar field; the scalar field and a pre-inlet do not combine");
+  HC_REQUIRE(!hc::ibm_wide(pre->L) && !hc::ibm_wide(domain->L), "hcp_preinlet_create: a cell type of a lattice is on a three- or four-point IBM kernel; those and a pre-inlet do not combine");
   HC_REQUIRE(pre->L->periodic[axis], "hcp_preinlet_create: the pre-inlet must be periodic on the inlet axis");
   HC_REQUIRE(pre->ntypes == domain->ntypes, "hcp_preinlet_create: the containers hold different numbers of cell types");
   for (int t = 0; t < pre->ntypes; t++) {
@@ -433,6 +434,7 @@ int hcp_preinlet_create_slab(hc_preinlet_cells **out, hc_cells *pre, hc_cells *d
     if (!pre) return HC_OK;
     HC_REQUIRE(pre != domain && pre->L->n_slabs == 1, fn + ": the pre-inlet needs n_slabs = 1 (it lives whole on the inlet rank)");
     HC_REQUIRE(!pre->L->scalar, fn + ": the pre-inlet's lattice has a scalar field; the scalar field and a pre-inlet do not combine");
+    HC_REQUIRE(!hc::ibm_wide(pre->L), fn + ": a cell type of the pre-inlet's lattice is on a three- or four-point IBM kernel; those and a pre-inlet do not combine");
     { const int rc = check_pair(fn, pre, domain, axis, window_lo, window_hi, id_stride); if (rc != HC_OK) return rc; }
     // an arriving cell is held by this rank alone until the ordinary envelope synchronisation replicates it
     const double a = window_lo + shift[0], b = window_hi + shift[0], x0 = (double)L->x0, x1 = (double)(L->x0 + L->nx), e = domain->e_share;

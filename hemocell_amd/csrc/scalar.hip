@@ -441,6 +441,7 @@ int hcl_scalar_stats(hc_scalar *S, double out[3]) {
 int hcp_sample_scalar(hc_cells *C, hc_scalar *S, double *out_per_vertex) {
   HC_REQUIRE(C && S && out_per_vertex, "hcp_sample_scalar: null pointer");
   HC_REQUIRE(C->L == S->L, "hcp_sample_scalar: the cells and the scalar field are bound to different lattices");
+  HC_REQUIRE(!C->ibm_wide_on(), "hcp_sample_scalar: a cell type is on a three- or four-point IBM kernel; the sample goes through the eight-node stencil");
   int rc = settle(C); if (rc != HC_OK) return rc;
   if ((rc = sync_to_device(C)) != HC_OK) return rc;
   if (C->nverts == 0) return HC_OK;

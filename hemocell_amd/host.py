@@ -22,6 +22,7 @@ MODEL_RBC_HO = 0
 MODEL_PLT_SIMPLE = 1
 MODEL_WBC_HO = 2
 MODEL_RBC_MALARIA = 3
+IBM_PHI2, IBM_PHI3, IBM_PHI4 = 2, 3, 4   # hcp_type_set_ibm_kernel: nodes per axis of a type's IBM delta function
 WBC_SPHERE = 0             # config/constant_defaults.h:83
 RBC_FROM_SPHERE = 1        # config/constant_defaults.h:80
 MESH_FROM_STL = 2          # config/constant_defaults.h:84
@@ -938,6 +939,17 @@ class Cells:
         if getattr(celltype, "solidify", None) is not None:
             self.enableSolidifyMechanics(idx.value, *celltype.solidify)
         return idx.value
+
+    # HemoCellField::kernelMethod (core/hemoCellField.h:67)
+    def setIbmKernel(self, type_index, kernel):
+        """the delta function of one type: IBM_PHI2 (the reference's interpolationCoefficientsPhi2, the default), IBM_PHI3
+        (three-point, Roma) or IBM_PHI4 (four-point, Peskin); types of different widths share the container"""
+        check(self.lib.hcp_type_set_ibm_kernel(self.ptr, int(type_index), int(kernel)))
+
+    def ibmKernel(self, type_index):
+        k = C.c_int()
+        check(self.lib.hcp_type_get_ibm_kernel(self.ptr, int(type_index), C.byref(k)))
+        return k.value
 
     # solidify mechanics (core/hemoCell.cpp:334-340; core/hemoCellParticleField.cpp:1002-1065)
     def enableSolidifyMechanics(self, type_index, distance_threshold_lu, shear_threshold):

@@ -523,6 +523,28 @@ int hcp_mechanics(hc_cells *C, long iter, int forced);
 /* separate_force_vectors output mode (core/hemoCellParticleField.cpp:590-614): comp = [6][n][3]
  * (volume, area, bending, link, visc, inner link) for the vertices of one type */
 int hcp_mechanics_components(hc_cells *C, int type, double *comp);
+/* ---- the width of a type's IBM delta function (HemoCellField::kernelMethod, core/hemoCellField.h:67).  The reference declares
+ * phi3, phi4, interpolationCoefficientsPhi3 and ...Phi4 (core/immersedBoundaryMethod.h:43-50, :140-153) without bodies; the
+ * definitions here are this back end's own, the standard three-point (Roma) and four-point (Peskin) functions:
+ *   phi3(r) = (1 + sqrt(1 - 3 r^2)) / 3 for |r| <= 0.5, (5 - 3 |r| - sqrt(-2 + 6 |r| - 3 r^2)) / 6 for 0.5 < |r| <= 1.5, else 0;
+ *     nodes c - 1, c, c + 1 per axis with c = floor(p + 0.5)
+ *   phi4(r) = (3 - 2 |r| + sqrt(1 + 4 |r| - 4 r^2)) / 8 for |r| <= 1, (5 - 2 |r| - sqrt(-7 + 12 |r| - 4 r^2)) / 8 for 1 < |r| <= 2, else 0;
+ *     nodes f - 1 ... f + 2 per axis with f = floor(p)
+ * Everything else is interpolationCoefficientsPhi2 (:99-137): weight = phi(dx) phi(dy) phi(dz), nodes in ascending x, y, z, a
+ * node beyond a non-periodic face, a node that is not fluid and a zero weight skipped, the admitted weights times 1 / total.
+ * hcp_spread, hcp_interpolate, hcp_interpolate_cells and hc_iterate then run the type through the kernels of that width, in
+ * all three forms (per cell, per vertex, reproducible spread); types of different widths share a container.  A cell whose
+ * stencil nodes exceed the tile or node cap of its width takes the per-vertex path inside the per-cell kernels.
+ * HC_ERR_ARG, and nothing changes: another value of `kernel`; a wide kernel on a lattice with n_slabs > 1 (four points need two
+ * halo planes), with open-boundary nodes or in a pre-inlet pair, or for a type with interior viscosity (the membrane pass walks
+ * the eight-node stencil).  The other way round, hcl_open_boundary_add*, hcl_preinlet_create, hcp_preinlet_create*,
+ * hcp_type_set_interior_viscosity and hcp_sample_scalar refuse while a type of the container (a container of the lattice) is
+ * on a wide kernel.  Default HC_IBM_PHI2, which launches exactly what it launched before this call existed. */
+#define HC_IBM_PHI2 2
+#define HC_IBM_PHI3 3
+#define HC_IBM_PHI4 4
+int hcp_type_set_ibm_kernel(hc_cells *C, int type, int kernel);
+int hcp_type_get_ibm_kernel(hc_cells *C, int type, int *kernel);
 /* ---- interior viscosity: which nodes lie inside a cell (core/hemoCellParticleField.cpp:745-807, helper/octree.h:107-147,
  * helper/mollerTrumbore.h).  hcp_type_set_interior_viscosity marks a type (<enableInteriorViscosity>, tau_int =
  * viscosityRatio (tau - 0.5) + 0.5): omega = 1 / tau_int becomes a class of the lattice (an equal omega shares a class;
