@@ -225,6 +225,14 @@ SIGNATURES = {
     "hcp_preinlet_destroy": (C.c_int, [VP]),
     "hc_preinlet_iterate": (C.c_int, [VP, VP, c_long_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "hcp_cell_info": (C.c_int, [VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_packing_create": (C.c_int, [C.POINTER(VP), c_int_p, C.c_int, c_double_p, c_int_p, c_double_p, c_double_p, C.c_double, C.c_int,
+                                    C.c_int, C.c_double]),
+    "hc_packing_run": (C.c_int, [VP, C.c_int, c_double_p]),
+    "hc_packing_count": (C.c_int, [VP, c_int_p, c_int_p]),
+    "hc_packing_state": (C.c_int, [VP, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_packing_pairs": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_double_p,
+                                   c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]),
+    "hc_packing_destroy": (C.c_int, [VP]),
 }
 
 _lib = None

@@ -50,3 +50,333 @@ def pack_pipe_rbc(nx, ny, nz, hematocrit, seed=12345, rbc_volume_lu=649.0, x0=0,
                     centres.append(c)
                     angles.append(np.array([90.0, 0.0, 0.0]) + a)
     return np.array(centres).reshape(-1, 3), np.array(angles).reshape(-1, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# tools/packCells: cells to a target hematocrit in a periodic box.  packing_plan is the host arithmetic of packCells.cpp and
+# Packing::initBlood; pack_cells runs the force-bias packing on the GPU (csrc/packing.hip, hc_packing_*).
+
+# full axes of the enclosing ellipsoids in um (packCells.cpp:88-96)
+CELL_SIZES_UM = {
+    "RBC": (8.4, 4.4, 8.4),
+    "PLT": (2.4, 1.05, 2.4),
+    "WBC": (8.4, 8.4, 8.4),
+    "vRBC": (3.5, 6.0, 11.0),
+    "RBC_m": (5.8, 3.4, 5.8),
+    "PLT_m": (1.84, 1.05, 1.84),
+    "PLT_mko": (1.71, 1.71, 1.71),
+}
+RBC_VOLUME_NOMINAL_UM3 = 97.0   # packCells.cpp:203
+MAX_ITER_DEFAULT = 2147483647 - 100   # packCells.cpp:106
+
+
+class PackingPlan:
+    """what packCells decides before it packs: the cell types with their counts and sizes, the sizing factor, the grid of the
+    collision check, the nominal volume fraction of the enclosing ellipsoids and the box that is really packed"""
+
+    def __init__(self, size_um, names, counts, sizes_um, scale, grid, nominal_fraction, hematocrit, plt_ratio):
+        self.size_um = tuple(float(s) for s in size_um)
+        self.names = list(names)
+        self.counts = [int(c) for c in counts]
+        self.sizes_um = np.array(sizes_um, dtype=np.float64).reshape(-1, 3)
+        self.scale = float(scale)
+        self.sizes_scaled = self.sizes_um * self.scale
+        self.grid = tuple(int(g) for g in grid)
+        self.nominal_fraction = float(nominal_fraction)
+        self.hematocrit = hematocrit
+        self.plt_ratio = plt_ratio
+        self.box_um = tuple(g * (1.0 / self.scale) for g in self.grid)
+        self.warning = None
+        if self.nominal_fraction > 0.7:   # packing.h:249-253
+            self.warning = ("the enclosing ellipsoids yield a nominal volume ratio of %.6f; the densest possible packing is "
+                            "around 0.77" % self.nominal_fraction)
+
+    def count(self, name):
+        return sum(c for n, c in zip(self.names, self.counts) if n == name)
+
+
+def _c_round(x):
+    """C's round(): halves away from zero"""
+    return int(np.floor(x + 0.5)) if x >= 0 else -int(np.floor(-x + 0.5))
+
+
+def packing_plan(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=None):
+    """packCells.cpp:197-241 and Packing::initBlood (packing.h:198-262), pure host code.
+
+    size_um: the requested box; cells: a list of (name, count) with a name of CELL_SIZES_UM, or (name, count, (dx, dy, dz))
+    for a custom ellipsoid, in the order of the command line; hematocrit adds round(Hct V / 97) RBC and round(nRBC ratio)
+    PLT after them.  As in the reference, hematocrit excludes explicit RBC and PLT counts, and one of the two is needed.
+    scale=None is 1.2 / (largest axis of the most numerous type).  Reference quirks that stay: the grid is ceil(size * scale)
+    cells per axis, so the packed box (box_um) is larger than requested (24 um: 4 cells = 28 um) while the nominal fraction
+    is computed from the requested size; the reference carries the hematocrit and the scaled box sizes in single precision,
+    which decides the rounding of a borderline count or grid and is kept."""
+    size = [float(s) for s in size_um]
+    if len(size) != 3 or not all(np.isfinite(s) and s > 0 for s in size):
+        raise ValueError("size_um must be three positive lengths")
+    types = []
+    for c in (cells or []):
+        name, n = c[0], int(c[1])
+        if len(c) > 2:
+            dims = tuple(float(v) for v in c[2])
+        elif name in CELL_SIZES_UM:
+            dims = CELL_SIZES_UM[name]
+        else:
+            raise ValueError("unknown cell type %r: give (name, count, (dx, dy, dz))" % (name,))
+        if n < 0 or len(dims) != 3 or not all(np.isfinite(v) and v > 0 for v in dims):
+            raise ValueError("cell type %r needs a count >= 0 and three positive sizes" % (name,))
+        types.append((name, n, dims))
+    if hematocrit is not None and any(len(c) == 2 and c[0] in ("RBC", "PLT") for c in (cells or [])):
+        raise ValueError("hematocrit is mutually exclusive with explicit RBC and PLT counts")   # packCells.cpp:120-146
+    if hematocrit is None and not types:
+        raise ValueError("specify at least a cell type or the hematocrit")                     # packCells.cpp:197-200
+    if hematocrit is not None:
+        h = float(np.float32(hematocrit))
+        if not (np.isfinite(h) and h >= 0):
+            raise ValueError("hematocrit must be a non-negative number")
+        volume = size[0] * size[1] * size[2]
+        n_rbc = _c_round(h * volume / RBC_VOLUME_NOMINAL_UM3)
+        types.append(("RBC", n_rbc, CELL_SIZES_UM["RBC"]))
+        n_plt = _c_round(n_rbc * float(plt_ratio))
+        if n_plt > 0:
+            types.append(("PLT", n_plt, CELL_SIZES_UM["PLT"]))
+    if scale is None or scale <= 0.0:   # packCells.cpp:216-241: the first of the most numerous types
+        most, largest = 0, 0.0
+        for _, n, dims in types:
+            if most < n:
+                most, largest = n, max(dims)
+        if most == 0:
+            raise ValueError("no cells to pack")
+        scale = (1. / largest) * 1.2
+    scale = float(scale)
+    # initBlood: float sizeX *= Sizing; ceil; the volume is the product of the three floats
+    fs = [np.float32(np.float64(np.float32(s)) * scale) for s in size]
+    grid = [int(np.ceil(v)) for v in fs]
+    domain = float(np.float32(np.float32(fs[0] * fs[1]) * fs[2]))
+    cell_volume = 0.0
+    for _, n, dims in types:
+        dx, dy, dz = (v * scale for v in dims)
+        cell_volume += ((4. / 3. * 3.141592653589793 * dx / 2. * dy / 2. * dz / 2.) * n)
+    return PackingPlan(size, [t[0] for t in types], [t[1] for t in types], [t[2] for t in types], scale, grid, cell_volume / domain,
+                       hematocrit, plt_ratio if hematocrit is not None else None)
+
+
+def quaternion_matrix(q):
+    """Quaternion::countQ (geometry.h:424-428) of (s, p): 2 (p p^T - s skew(p) + (s^2 - 1/2) I); [..., 3, 3]"""
+    q = np.asarray(q, dtype=np.float64)
+    s, p = q[..., 0], q[..., 1:]
+    skew = np.zeros(q.shape[:-1] + (3, 3))
+    skew[..., 0, 1], skew[..., 0, 2] = -p[..., 2], p[..., 1]
+    skew[..., 1, 0], skew[..., 1, 2] = p[..., 2], -p[..., 0]
+    skew[..., 2, 0], skew[..., 2, 1] = -p[..., 1], p[..., 0]
+    return 2.0 * (p[..., :, None] * p[..., None, :] - s[..., None, None] * skew + (s * s - 0.5)[..., None, None] * np.eye(3))
+
+
+def euler_angles_deg(q):
+    """the angles packCells writes (saveBloodCellPositions, packing.h:634-636): (atan2(Q12, Q22), -asin(Q02), atan2(Q01, Q00))
+    of countQ(), in degrees.  A .pos reader (io/readPositionsBloodCells.cpp:40-109, 228-229; host.Cells.addCell) turns them
+    into the body-to-world rotation Rz(c) Ry(b) Rx(a), which is the transpose of countQ()."""
+    Q = quaternion_matrix(q)
+    a = np.arctan2(Q[..., 1, 2], Q[..., 2, 2])
+    b = -np.arcsin(np.clip(Q[..., 0, 2], -1.0, 1.0))
+    c = np.arctan2(Q[..., 0, 1], Q[..., 0, 0])
+    return np.stack([a, b, c], axis=-1) * (180 / 3.141592653589793)
+
+
+class PackResult:
+    """a finished (or interrupted) packing: per type the centres in um and the Euler angles in degrees of a .pos file"""
+
+    def __init__(self, plan, positions_um, quaternions, status, seed):
+        self.plan = plan
+        self.names, self.counts = plan.names, plan.counts
+        self.box_um = plan.box_um   # the box that was packed: grid cells / scale, not the requested size
+        self.seed = seed
+        self.positions, self.angles, self.quaternions = {}, {}, {}
+        at = 0
+        for name, n in zip(plan.names, plan.counts):
+            self.positions[name] = positions_um[at:at + n].copy()
+            self.quaternions[name] = quaternions[at:at + n].copy()
+            self.angles[name] = euler_angles_deg(quaternions[at:at + n]).reshape(n, 3)
+            at += n
+        self.steps, self.finished = int(status[0]), bool(status[1])
+        self.outer_diameter, self.inner_diameter = float(status[2]), float(status[3])
+        self.density, self.nominal_density = float(status[4]), float(status[5])   # Pactual, DensityNominal
+        self.force_per_particle = float(status[6])
+        self.max_root_evaluations = int(status[10])
+
+    def write_pos(self, directory="."):
+        """<name>.pos per type as saveBloodCellPositions writes them (packing.h:617-648): the count, then x y z ax ay az per
+        cell, um and degrees.  Returns the paths."""
+        import os
+        os.makedirs(directory, exist_ok=True)
+        paths = []
+        for name in self.names:
+            path = os.path.join(directory, name + ".pos")
+            with open(path, "w") as f:
+                f.write("%d\n" % len(self.positions[name]))
+                for p, a in zip(self.positions[name], self.angles[name]):
+                    f.write(" ".join("%.10g" % v for v in (*p, *a)) + "\n")
+            paths.append(path)
+        return paths
+
+
+def read_pos(path):
+    """a .pos file: (centres [n][3] in um, angles [n][3] in degrees)"""
+    with open(path) as f:
+        n = int(f.readline().split()[0])
+        rows = np.array([[float(v) for v in f.readline().split()[:6]] for _ in range(n)], dtype=np.float64).reshape(n, 6)
+    return rows[:, :3].copy(), rows[:, 3:].copy()
+
+
+PROGRESS_HEADER = ("\n     Steps     Actual       Nominal        Inner         Outer             Force\n"
+                   "              density       density       diameter      diameter       per particle\n")
+
+
+def progress_line(status):
+    """the reference's progress columns (Packing::output, packing.h:516-527)"""
+    return "%9d%14.10f%14.10f%14.10f%14.10f%19.15f" % (int(status[0]), status[4], status[5], status[3], status[2], status[6])
+
+
+def pack_cells(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=None, rotate=True, max_iter=MAX_ITER_DEFAULT, seed=0,
+               steps_per_wait=64, progress=None):
+    """Bargiel's force-biased packing of the cell types' enclosing ellipsoids in a periodic box, on the GPU.
+
+    The plan is packing_plan's.  Every ellipsoid starts at a uniform random point of the box, drawn here from
+    numpy.random.Generator(PCG64(seed)) in particle order (the reference seeds drand48 with the clock), with the identity
+    orientation; the outer diameter shrinks while overlapping pairs push and turn each other (rotate=False: push only), until
+    no pair overlaps or max_iter iterations are done.  The device queues steps_per_wait iterations per host wait;
+    progress(status) is called after each wait.  Returns a PackResult; see packing_plan for the reference quirks that stay."""
+    import ctypes as C
+    from . import capi, host
+    plan = packing_plan(size_um, hematocrit, plt_ratio, cells, scale)
+    n = sum(plan.counts)
+    if n == 0:
+        raise ValueError("no cells to pack")
+    if max_iter < 0 or steps_per_wait < 1:
+        raise ValueError("max_iter must be >= 0 and steps_per_wait >= 1")
+    host.ensure_init()
+    lib = capi.lib()
+    grid = np.array(plan.grid, dtype=np.int32)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    pos = np.ascontiguousarray(rng.random((n, 3)) * grid.astype(np.float64))
+    sizes = np.ascontiguousarray(plan.sizes_scaled)
+    counts = np.array(plan.counts, dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    handle = C.c_void_p()
+    capi.check(lib.hc_packing_create(C.byref(handle), grid.ctypes.data_as(ip), len(counts), capi.dptr(sizes), counts.ctypes.data_as(ip),
+                                     capi.dptr(pos), None, plan.nominal_fraction, int(bool(rotate)), 0, 0.0))
+    try:
+        status = np.zeros(12)
+        capi.check(lib.hc_packing_run(handle, 0, capi.dptr(status)))
+        while not status[1] and int(status[0]) < max_iter:
+            capi.check(lib.hc_packing_run(handle, int(min(steps_per_wait, max_iter - int(status[0]))), capi.dptr(status)))
+            if progress is not None:
+                progress(status)
+        quat = np.zeros((n, 4))
+        capi.check(lib.hc_packing_state(handle, capi.dptr(pos), capi.dptr(quat), None, None))
+    finally:
+        lib.hc_packing_destroy(handle)
+    return PackResult(plan, pos * (1. / plan.scale), quat, status, seed)
+
+
+def _main(argv=None):
+    """python -m hemocell_amd.packing sX sY sZ [...]: the options of tools/packCells, and --seed"""
+    import argparse
+    import sys
+    usage = ("USAGE: python -m hemocell_amd.packing sX sY sZ [OPTIONAL ARGUMENTS ...]\n"
+             "\n"
+             "OPTIONAL ARGUMENTS:\n"
+             "  --hematocrit <0-1.0>                 -h Hematocrit of the suspension (human blood only)\n"
+             "  --plt_ratio <ratio>                     Platelets per red blood cell, default=0.07\n"
+             "  --rbc <n>                               Number of red blood cells\n"
+             "  --plt <n>                               Number of platelets\n"
+             "  --rbc_m <n>                             Number of mouse red blood cells\n"
+             "  --plt_m <n>                             Number of mouse wild-type platelets\n"
+             "  --plt_mko <n>                           Number of mouse knockout platelets\n"
+             "  --wbc <n>                               Number of white blood cells\n"
+             "  --vrbc <n>                              Number of stage V gametocytes\n"
+             "  --cell <name> <n> <e1> <e2> <diameter>  Custom cell type given by its ellipsoid\n"
+             "  --noRotate                              Keep the ellipsoids' orientations fixed\n"
+             "  --scale <ratio>                      -s Scale of the neighbourhood grid (expert use)\n"
+             "  --maxiter <n>                           Maximum number of iterations\n"
+             "  --seed <n>                              Seed of the initial positions, default=0\n"
+             "  --outdir <dir>                          Directory the .pos files go to, default=.\n"
+             "  --help                                  Print this\n"
+             "OUTPUT:\n"
+             "  <Cell>.pos for every cell type. The first line holds the number of cells,\n"
+             "  every other line one cell as \"Location<X Y Z> Rotation<X Y Z>\".\n"
+             "NOTE:\n"
+             "  sX, sY, sZ and the output are in [um], not in lattice units\n"
+             "  --hematocrit excludes --rbc and --plt\n"
+             "  --plt_ratio needs --hematocrit\n")
+    ap = argparse.ArgumentParser(prog="python -m hemocell_amd.packing", add_help=False, allow_abbrev=False)
+    ap.add_argument("size", nargs="*")
+    ap.add_argument("--hematocrit", "-h", type=float)
+    ap.add_argument("--plt_ratio", type=float, default=0.07)
+    named = (("rbc", "RBC"), ("plt", "PLT"), ("wbc", "WBC"), ("vrbc", "vRBC"), ("rbc_m", "RBC_m"), ("plt_m", "PLT_m"), ("plt_mko", "PLT_mko"))
+    order = []
+
+    class Named(argparse.Action):
+        def __call__(self, parser, ns, values, option_string=None):
+            order.append((dict(named)[self.dest], int(values)))
+
+    class Custom(argparse.Action):
+        def __call__(self, parser, ns, values, option_string=None):
+            order.append((values[0], int(values[1]), tuple(float(v) for v in values[2:5])))
+
+    for opt, _ in named:
+        ap.add_argument("--" + opt, action=Named)
+    ap.add_argument("--cell", nargs=5, action=Custom)
+    ap.add_argument("--noRotate", action="store_true")
+    ap.add_argument("--scale", "-s", type=float)
+    ap.add_argument("--maxiter", type=int, default=MAX_ITER_DEFAULT)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--help", action="store_true")
+    ap.add_argument("--outdir", default=".")
+    ap.error = lambda msg: (sys.stderr.write(msg + "\n\n" + usage), sys.exit(1))
+    a = ap.parse_args(argv)
+    if a.help:
+        sys.stderr.write(usage)
+        return 1
+    if len(a.size) != 3:
+        print("Insufficient arguments.\n")
+        sys.stderr.write(usage)
+        return 1
+    size = [int(float(s)) for s in a.size]   # atoi, packCells.cpp:193-195
+    try:
+        plan = packing_plan(size, a.hematocrit, a.plt_ratio, order, a.scale)
+    except ValueError as e:
+        sys.stderr.write("%s, exiting...\n" % e)
+        sys.stderr.write(usage)
+        return 1
+    print("Parameters:")
+    print("  Domain Size [um]: ( %d , %d , %d )" % tuple(size))
+    print("  Maximum Iterations : %d" % a.maxiter)
+    print("  Scale              : %.6f" % plan.scale)
+    print("  Rotation           : %d" % (not a.noRotate))
+    print("  Seed               : %d" % a.seed)
+    if a.hematocrit is not None:
+        print("  Hematocrit    : %.6f" % a.hematocrit)
+        print("  PLT/RBC Ratio : %.6f" % a.plt_ratio)
+    print("The following cell types are defined:")
+    for name, n, dims in zip(plan.names, plan.counts, plan.sizes_um):
+        print("  %s\n    No   : %d\n    Sizes: (%.6f , %.6f , %.6f )" % (name, n, dims[0], dims[1], dims[2]))
+        print("    Volume: %.6f [um3]." % (4.0 / 3.0 * 3.141592653589793 * dims[0] * dims[1] * dims[2] / 8.0))
+    print("\nSizing parameter: %.6f" % plan.scale)
+    print("Resolution of collision check: %d x %d x %d" % plan.grid)
+    print("Packed box [um]: %.6f x %.6f x %.6f" % plan.box_um)
+    print("\nNominal requested volume fraction: %.6f" % plan.nominal_fraction)
+    if plan.warning:
+        print("*** WARNING ***\n" + plan.warning)
+    print(PROGRESS_HEADER)
+    res = pack_cells(size, a.hematocrit, a.plt_ratio, order, a.scale, rotate=not a.noRotate, max_iter=a.maxiter, seed=a.seed,
+                     progress=lambda st: print(progress_line(st), flush=True))
+    if not res.finished:
+        print("WARNING: Force-free packing was NOT achieved! Potential overlaps might still exist.")
+    print(" PACKING DONE " if res.finished else " PACKING TERMINATED(!) ")
+    res.write_pos(a.outdir)
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(_main())

@@ -720,6 +720,37 @@ int hc_preinlet_iterate(hc_preinlet *F, hc_preinlet_cells *X, long *iter, int n,
  * volume and area are the triangle sums at the stored positions. */
 int hcp_cell_info(hc_cells *C, int type, double *volume, double *area, double *bbox, double *centroid);
 
+/* ------------------------------------------------------------------ packing
+ * tools/packCells of the reference (packing.h, ellipsoid.h, geometry.h): Bargiel's force-biased packing of ellipsoids in a
+ * periodic box with the Perram-Wertheim contact function.  Lengths are in grid cells: the box is grid[0] x grid[1] x grid[2],
+ * sizes are the full axes of each species' enclosing ellipsoid already multiplied by the sizing factor (initBlood,
+ * packing.h:198-262).  Particles are numbered species by species.  The caller supplies the initial state (the library draws
+ * nothing): pos [N][3] inside the box, quat [N][4] = (s, p) or null for identity.  create runs Packing::init and the
+ * calc_forces before the first iteration (:265-343, :179-182); ntau <= 0 and epsilon <= 0 take the reference's 102400 and
+ * 0.1.  Refused (HC_ERR_ARG): a null pointer, a grid outside 1..1023 per axis, no particle in total, a negative count, a
+ * non-positive size, anything non-finite, a position outside the box.
+ * hc_packing_run queues up to max_steps more iterations (iterate, :345-368) and waits once; every kernel returns at once
+ * after the end, so a run past it changes nothing.  status = { steps done in total, finished, Douter, Dinner, Pactual,
+ * DensityNominal, Force_step, Relax, Nsf, error flag, largest root-search count, grow }.  The root search (zeroin, :697-764)
+ * is capped at 256 evaluations: a pair that reaches the cap contributes nothing, sets the sticky error flag and this and every
+ * later run returns HC_ERR_STATE.  grow = 1: a partner list was too short; the run stopped in front of that iteration's forces
+ * with fewer steps done, the storage has grown, and the next run completes the iteration first.  max_steps < 0 is HC_ERR_ARG.
+ * hc_packing_state: positions, quaternions, forces and torques in particle order (any pointer may be null).
+ * hc_packing_pairs is a probe of the pair function the step uses (Packing::calc_forces(e, ei, ej), :108-144) on n given
+ * pairs: sizes [n][3], quaternions [n][4] as Quaternion(s, p) takes them (it normalises), rij = pos_B - pos_A [n][3],
+ * douter2 [n].  Out: lambda, 4 f_AB(lambda), n [n][3], the force and torque increments of A and B [n][3] each, the number of
+ * evaluations of the root search and kind (0: nothing, lambda < 1e-10; 1: f_AB >= 1; 2: overlap; -1: the cap). */
+typedef struct hc_packing hc_packing;
+int hc_packing_create(hc_packing **out, const int grid[3], int n_species, const double *sizes, const int *counts, const double *pos,
+                      const double *quat, double nominal_density, int rotate, int ntau, double epsilon);
+int hc_packing_run(hc_packing *P, int max_steps, double status[12]);
+int hc_packing_count(const hc_packing *P, int *n_particles, int *list_capacity);
+int hc_packing_state(hc_packing *P, double *pos, double *quat, double *force, double *torque);
+int hc_packing_pairs(int n, const double *size_a, const double *quat_a, const double *size_b, const double *quat_b, const double *rij,
+                     const double *douter2, int rotate, double *lambda, double *f_ab_scl, double *nvec, double *f_a, double *t_a,
+                     double *f_b, double *t_b, int *evals, int *kind);
+int hc_packing_destroy(hc_packing *P);
+
 #ifdef __cplusplus
 }
 #endif
