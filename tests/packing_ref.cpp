@@ -2,8 +2,8 @@
 // Independent of hemocell_amd/csrc/packing.hip: no shared header.  Compiled by the tests with g++ -O2 -ffp-contract=off.
 // It follows tools/packCells of the reference operation for operation (ellipsoid.h:303-405, packing.h:108-144, :345-428,
 // :697-764, geometry.h) with the deviations the design lists: minimum image on both pair paths, sums in ascending partner
-// index, the iprec table, a caller-given initial state, the root search capped at 256 evaluations and a step rotation that
-// always has unit norm.
+// index, the iprec table, a caller-given initial state, the root search capped at 256 evaluations, a step rotation that
+// always has unit norm, and cell ranges taken by the floor modulo outside the box.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -271,7 +271,8 @@ struct Sim {
     }
     return r;
   }
-  // packing.h:387-395, :438-463: is B < A a partner of A?
+  // packing.h:387-395, :438-463: is B < A a partner of A?  B has a cell only where (int)x lies in 0..grid-1, and A's range is
+  // taken by the floor modulo, so that it stays a range of cells once x + grid - Rcut is negative (the design's deviation 11)
   bool active(int A, int B) const {
     const double Rcut = 0.55 * Douter * (size[3 * spec[A]] + Rc_max);
     if (!((int)(2.0 * Rcut) < ncell_min - 1)) return true;
@@ -280,7 +281,7 @@ struct Sim {
       const int c = (int)pos[B].v[k];
       if (c < 0 || c >= grid[k]) return false;   // the reference would index past its cell array
       bool in = false;
-      for (int leap = low; leap <= lim; leap++) if (leap % grid[k] == c) in = true;
+      for (int leap = low; leap <= lim; leap++) if ((leap % grid[k] + grid[k]) % grid[k] == c) in = true;
       if (!in) return false;
     }
     return true;

@@ -234,3 +234,181 @@ def test_to_the_end_shape_finishes_well_inside_the_cap():
     st = S.run(1000)
     print("24^3 at 0.40, seed 1: finished after %d iterations" % st["steps"])
     assert st["finished"] == 1 and st["steps"] <= 500 and st["error"] == 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The conditions the starts of tests/packing_cases.py rest on (tests/test_gpu_packing_shapes.py runs them on the device)
+import functools
+import hashlib
+
+import packing_cases as PC
+
+
+@functools.lru_cache(maxsize=None)
+def _walk(name, rotate, marks=(0, 1, 5, 20)):
+    """the restatement on a case: [(status, state)] after each of marks iterations"""
+    c = PC.build(name)
+    S = R.Packing(c.grid, c.sizes_scaled, c.counts, c.pos, c.quat, c.nominal_fraction, rotate)
+    out, done = [], 0
+    for upto in marks:
+        st = S.run(upto - done)
+        done = upto
+        out.append((st, S.state()))
+    return c, out
+
+
+def _inside(case, pos):
+    return (pos >= 0).all() and (pos <= np.array(case.grid, dtype=np.float64)).all()
+
+
+@pytest.mark.parametrize("rotate", [True, False])
+@pytest.mark.parametrize("name", PC.UNEVEN)
+def test_uneven_cases_reach_what_they_claim(name, rotate):
+    """grids with three different axes, a sphere, given orientations, N past a wave and past a block: the path of every species
+    from the rule itself, the pair counts of the restatement against an independent count in numpy (packing_cases.partner_matrix),
+    nothing outside the box, no error, and root searches far below the 128 the device tests allow (33 at the most here)"""
+    c, walk = _walk(name, rotate)
+    n, all_pairs = c.n, c.n * (c.n - 1) // 2
+    assert n == {"uneven288": 288, "uneven134": 134, "uneven70": 70}[name] and n > 64 and n % 64
+    assert len(set(c.grid)) == 3 and np.abs(np.linalg.norm(c.quat, axis=1) - 1).max() < 1e-15
+    st0 = walk[0][0]
+    assert st0["Douter"] == PC.first_diameter(c)
+    for st, state in walk:
+        mode = PC.modes(c, st["Douter"])
+        assert mode == PC.UNEVEN_MODES[name]
+        assert st["pairs"] == PC.partner_matrix(c, state[0], st["Douter"]).sum()
+        if "part" in mode:
+            assert 0 < st["pairs"] < all_pairs
+        else:
+            assert st["pairs"] == all_pairs
+        assert _inside(c, state[0]) and st["error"] == 0 and st["maxeval"] <= 40
+        assert not st["finished"]
+    assert [st["steps"] for st, _ in walk] == [0, 1, 5, 20]
+    counts = PC.partner_counts(c, c.pos, st0["Douter"])
+    if name == "uneven288":
+        assert n > 256 and -(-n // 64) == 5
+        assert st0["pairs"] == 6369 and counts.max() == 72 and PC.list_capacity(c) == 274 < n - 1
+    elif name == "uneven134":
+        assert st0["pairs"] == 7597 and PC.list_capacity(c) == n - 1   # the seed-5 start; it walks through 7614 a few steps on
+    else:
+        assert counts.min() == n - 1 and PC.list_capacity(c) == n - 1
+    # the sphere: no torque of its own and an orientation that stays; the RBCs have both
+    state = walk[-1][1]
+    assert not state[3][c.rows("WBC")].any() and np.array_equal(state[1][c.rows("WBC")], c.quat[c.rows("WBC")])
+    assert state[2][c.rows("WBC")].any()
+    assert state[3][c.rows("RBC")].any() == bool(rotate)
+    assert np.array_equal(state[1], c.quat) == (not rotate)
+
+
+@pytest.mark.parametrize("rotate", [True, False])
+def test_uneven288_finishes_well_inside_the_cap(rotate):
+    """the (5, 6, 8) start of seed 5 runs to the end under a cap of 1000 on the device: the restatement ends it after 94
+    iterations with rotation and 312 without (the bound is half the cap, not those counts)"""
+    c = PC.build("uneven288")
+    S = R.Packing(c.grid, c.sizes_scaled, c.counts, c.pos, c.quat, c.nominal_fraction, rotate)
+    st = S.run(1000)
+    print("(5, 6, 8) with 288 particles, seed 5, rotate %d: finished after %d iterations" % (rotate, st["steps"]))
+    assert st["finished"] == 1 and st["steps"] <= 500 and st["error"] == 0 and st["maxeval"] < 128
+    assert _inside(c, S.state()[0])
+
+
+@pytest.mark.parametrize("rotate", [True, False])
+def test_cluster_start_needs_longer_lists(rotate):
+    """200 particles inside a cube of edge 0.9 on 8^3: both species are on the cell list, yet every particle is every other's
+    partner (199 each, 19900 pairs) while hc_packing_create starts with lists of 161.  The first step then scatters them
+    (Force_step about 61) and the lists shrink to about 40; nothing leaves the box in 20 iterations."""
+    c, walk = _walk("cluster", rotate)
+    st0, state0 = walk[0]
+    assert PC.modes(c, st0["Douter"]) == ["part", "part"]
+    assert PC.list_capacity(c) == 161
+    counts = PC.partner_counts(c, c.pos, st0["Douter"])
+    assert counts.min() == counts.max() == 199 > 161 and st0["pairs"] == 19900
+    assert PC.grown_capacity(c, 199) == 199
+    for st, state in walk:
+        assert _inside(c, state[0]) and st["error"] == 0 and not st["finished"]
+        assert st["pairs"] == PC.partner_matrix(c, state[0], st["Douter"]).sum()
+    assert 50 < walk[1][0]["Force_step"] < 70
+    assert PC.partner_counts(c, walk[1][1][0], walk[1][0]["Douter"]).max() < 50
+    assert walk[-1][0]["steps"] == 20 and walk[-1][0]["maxeval"] == (19 if rotate else 18)
+
+
+@pytest.mark.parametrize("rotate", [True, False])
+def test_faces_start(rotate):
+    """deviation 8: a particle exactly on an upper face has no cell.  Particle 0 is the lowest index, so it is never an A; as B
+    it is in nobody's range, and it neither feels a force nor moves.  Particle 1, at the origin, does."""
+    c, walk = _walk("faces", rotate)
+    assert walk[0][0]["pairs"] == 828 and PC.partner_counts(c, c.pos, walk[0][0]["Douter"])[0] == 0
+    box = np.array(c.grid, dtype=np.float64)
+    for st, state in walk:
+        assert st["error"] == 0 and st["maxeval"] <= 19 and _inside(c, state[0]) and not st["finished"]
+        assert not state[2][0].any() and not state[3][0].any() and np.array_equal(state[0][0], c.pos[0])
+        assert st["pairs"] == PC.partner_matrix(c, state[0], st["Douter"]).sum()
+    assert walk[0][1][2][1].any()
+    assert (walk[-1][1][0] == box).sum() == 3 and walk[-1][1][0][0, 0] == 4.0
+    # no two particles at the same point modulo the box
+    wrapped = np.mod(c.pos, box)
+    assert len(np.unique(wrapped, axis=0)) == c.n
+
+
+def test_coincident_start_ends_in_the_error_flag():
+    """rows 1 and 45 are the same point modulo the box: rij = 0, the contact polynomials vanish, the search returns lambda = 1
+    at once and the force is 0 / 0.  Create goes through (nothing reaches the cap); the first iteration moves both to NaN and
+    every search with them runs into the cap."""
+    c = PC.build("coincident")
+    assert not np.mod(c.pos[1] - c.pos[45], 4.0).any()
+    S = R.Packing(c.grid, c.sizes_scaled, c.counts, c.pos, None, c.nominal_fraction, True)
+    st = S.status()
+    assert st["error"] == 0 and st["maxeval"] < 128 and st["Dinner"] == 0.0
+    f = S.state()[2]
+    assert np.isnan(f[1]).all() and np.isnan(f[45]).all() and np.isfinite(np.delete(f, (1, 45), axis=0)).all()
+    st = S.run(5)
+    assert st["error"] == 1 and st["maxeval"] == 256 and st["steps"] == 1   # the restatement counts the iteration that failed
+    assert S.run(5)["steps"] == 1
+
+
+def test_thrown_start_leaves_the_box():
+    """deviation 11: 320 particles within half a cell on 8^3.  The first step is longer than the box, pbc wraps once, and
+    coordinates stay outside for two iterations.  Outside, a particle has a cell only where (int)x is in 0..grid-1, and its
+    range as A is taken by the floor modulo: the restatement's pair count equals the numpy count of that rule at every step."""
+    c, walk = _walk("thrown", True, (0, 1, 2, 4))
+    box = np.array(c.grid, dtype=np.float64)
+    outside = [int(((s[0] < 0) | (s[0] > box)).sum()) for _, s in walk]
+    print("coordinates outside the box after 0, 1, 2 and 4 iterations:", outside)
+    assert outside[0] == 0 and outside[1] > 100 and outside[2] > 0
+    low = min((s[0] + box - 0.55 * st["Douter"] * 2 * c.sizes_scaled[:, 0].max()).min() for st, s in walk)
+    assert low < -1.0   # a range that starts below zero: where a truncating and a floor modulo part
+    assert PC.partner_counts(c, c.pos, walk[0][0]["Douter"]).min() == 319 > PC.list_capacity(c) == 182
+    for st, state in walk:
+        assert st["error"] == 0 and st["maxeval"] < 128 and np.isfinite(state[0]).all()
+        assert st["pairs"] == PC.partner_matrix(c, state[0], st["Douter"]).sum()
+
+
+def _digest(S):
+    st = S.status()
+    h = hashlib.sha256()
+    for a in S.state():
+        h.update(np.ascontiguousarray(a).tobytes())
+    return dict(steps=st["steps"], finished=st["finished"], Nsf=st["Nsf"], pairs=st["pairs"], maxeval=st["maxeval"],
+                Douter=float(st["Douter"]).hex(), Dinner=float(st["Dinner"]).hex(), Force_step=float(st["Force_step"]).hex(),
+                state_sha256=h.hexdigest())
+
+
+def test_restatement_unchanged_inside_the_box():
+    """tests/golden/packing_restatement_runs.json holds the restatement's trajectories on the shapes of the tests above and of
+    tests/test_gpu_packing.py (start, 20 iterations, the end), recorded while active() still compared leap % grid with the cell.
+    Inside the box x + grid - Rcut is positive and the two rules are one: every number and every bit of the states is the same."""
+    runs = json.load(open(os.path.join(ROOT, "tests", "golden", "packing_restatement_runs.json")))["runs"]
+    assert len(runs) == 12
+    for r in runs:
+        kw = dict(r["plan"])
+        if "cells" in kw:
+            kw["cells"] = [tuple(x) for x in kw["cells"]]
+        plan = packing.packing_plan((r["size"],) * 3, **kw)
+        S = R.Packing(plan.grid, plan.sizes_scaled, plan.counts, R.initial_positions(plan.grid, sum(plan.counts), r["seed"]), None,
+                      plan.nominal_fraction, r["rotate"])
+        where = (r["size"], r["seed"], r["rotate"])
+        assert _digest(S) == r["start"], where
+        S.run(20)
+        assert _digest(S) == r["after20"], where
+        S.run(1000)
+        assert _digest(S) == r["end"] and r["end"]["finished"] == 1, where
