@@ -233,6 +233,11 @@ SIGNATURES = {
     "hc_packing_pairs": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_double_p,
                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]),
     "hc_packing_destroy": (C.c_int, [VP]),
+    "hc_packing_set_walls": (C.c_int, [VP, VP, c_int_p, C.c_double, c_int_p, C.c_double]),
+    "hc_packing_wall_field": (C.c_int, [VP, c_double_p]),
+    "hc_packing_reserve_lists": (C.c_int, [VP, C.c_int]),
+    "hc_packing_walls": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p,
+                                   c_double_p, c_int_p, c_int_p]),
 }
 
 _lib = None

@@ -17,6 +17,12 @@
 // index on both sides), which makes the two increments bitwise opposite without any floating-point atomic.  The control
 // scalars live in one device block (Ctl); every kernel of an iteration returns at once when finished, error or grow is
 // set, so hc_packing_run queues its iterations blind and waits once.
+//
+// Walls (hc_packing_set_walls; this back end's own, the reference packs periodic boxes only): a particle near a wall gets one
+// more partner, its mirror image across the wall's tangent plane (wall_eval), evaluated by pk_wall and added by pk_sum after
+// the partner slots.  The wall's signed distance comes from a field built once on the device (pk_edt_*), sampled trilinearly
+// (wall_sample).  pk_motion, pk_pair and pk_sum are templates on WALLS; without walls the <false> instances run, whose code
+// is that of the periodic packing, and pk_wall is not launched.
 #include "common.h"
 #include <cmath>
 
@@ -301,11 +307,90 @@ struct View {
   int *pcell, *plow, *plen; // [N]: packed cell of the particle, low cell and length of its range per axis, bit 30 = all pairs
   int *cnt, *list;          // [N], [N][K]
   double *rec;              // [7][N K]: force[3], torque[3], Dinner^2 candidate of every list slot
+  // walls (hc_packing_set_walls; DESIGN §6 "packing walls").  walls = 0: nothing below is read
+  int walls, wrap[3], wd[3];   // wrap: the axis is periodic; wd: nodes of the wall field per axis
+  double wsp, wmargin;         // node spacing and wall margin, in grid cells
+  const double *snode;         // [wd0][wd1][wd2]: signed distance of a node to the wall surface, in node spacings
+  double *wrec;                // [7][N]: the wall slot's force[3], torque[3] and Dinner^2 candidate
 };
+
+constexpr int ERR_ROOT_CAP = 1, ERR_WALL_NODE = 2;   // Ctl::error
+constexpr double WALL_S_MIN = 1e-6;                   // the image pair is evaluated no closer to the surface than this (grid cells)
 
 __device__ __forceinline__ bool halted(const Ctl *c) { return c->finished | c->error | c->grow; }
 
-// calc_motion (packing.h:399-428) and, by the first thread, Douter -= Relax (iterate, :347-348): nothing here reads Douter
+// ---------------------------------------------------------------------------------------------------------------- walls
+// A node index along an axis: the floor modulo on a periodic axis, clamped to the field elsewhere.
+PK_FN int wall_node(int i, int d, int wrap) {
+  if (wrap) { i %= d; return i < 0 ? i + d : i; }
+  return i < 0 ? 0 : (i > d - 1 ? d - 1 : i);
+}
+PK_FN double wall_floor(double u) {   // floor, kept where the conversion to int is defined
+  double fl = floor(u);
+  if (!(fl > -1e9)) fl = -1e9;
+  if (fl > 1e9) fl = 1e9;
+  return fl;
+}
+PK_FN double lerp(double a, double b, double t) { return a + t * (b - a); }
+
+// s and n at x: the trilinear form of snode over the eight nodes around x and its analytic gradient.  Order: along z first
+// (four edges), then y, then x; s = lerp(f0, f1, tx) wsp - wmargin.  false: the gradient's norm is below 1e-12.
+PK_FN bool wall_sample(const View &v, const V3 &x, double *s, V3 *n) {
+  int lo[3], hi[3]; double t[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double u = x.v[k] / v.wsp, fl = wall_floor(u);
+    t[k] = u - fl;
+    lo[k] = wall_node((int)fl, v.wd[k], v.wrap[k]);
+    hi[k] = wall_node((int)fl + 1, v.wd[k], v.wrap[k]);
+  }
+  const size_t sy = (size_t)v.wd[2], sx = sy * v.wd[1];
+  const double c000 = v.snode[lo[0] * sx + lo[1] * sy + lo[2]], c001 = v.snode[lo[0] * sx + lo[1] * sy + hi[2]];
+  const double c010 = v.snode[lo[0] * sx + hi[1] * sy + lo[2]], c011 = v.snode[lo[0] * sx + hi[1] * sy + hi[2]];
+  const double c100 = v.snode[hi[0] * sx + lo[1] * sy + lo[2]], c101 = v.snode[hi[0] * sx + lo[1] * sy + hi[2]];
+  const double c110 = v.snode[hi[0] * sx + hi[1] * sy + lo[2]], c111 = v.snode[hi[0] * sx + hi[1] * sy + hi[2]];
+  const double e00 = lerp(c000, c001, t[2]), e01 = lerp(c010, c011, t[2]), e10 = lerp(c100, c101, t[2]), e11 = lerp(c110, c111, t[2]);
+  const double f0 = lerp(e00, e01, t[1]), f1 = lerp(e10, e11, t[1]);
+  *s = lerp(f0, f1, t[0]) * v.wsp - v.wmargin;
+  V3 g;
+  g.v[0] = f1 - f0;
+  g.v[1] = lerp(e01 - e00, e11 - e10, t[0]);
+  g.v[2] = lerp(lerp(c001 - c000, c011 - c010, t[1]), lerp(c101 - c100, c111 - c110, t[1]), t[0]);
+  const double len = sqrt(dot3(g, g));
+  if (!(len >= 1e-12)) return false;
+  *n = vmul(g, 1 / len);
+  return true;
+}
+
+// the node nearest to x is a wall node, or x lies off the field on an axis that does not wrap
+PK_FN bool wall_hit(const View &v, const V3 &x) {
+  int at[3];
+  bool out = false;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double u = x.v[k] / v.wsp;
+    if (!v.wrap[k] && !(u >= 0 && u <= v.wd[k] - 1)) out = true;
+    at[k] = wall_node((int)wall_floor(u + 0.5), v.wd[k], v.wrap[k]);
+  }
+  return out || v.snode[((size_t)at[0] * v.wd[1] + at[1]) * v.wd[2] + at[2]] < 0;
+}
+
+// The wall as the particle's mirror image across the tangent plane at distance s along -n: same semi-axes, centre at
+// x - 2 s n, orientation H R diag(1, 1, -1) with H = I - 2 n n^T.  As H = -Rot(n, pi) and diag(1, 1, -1) = -Rot(z, pi), the
+// image's quaternion is the product (0, z) q (0, n) in quat_mul's order: no branch, the sign is the product's.
+PK_FN void wall_eval(PairResult &o, const double r[3], const Q4 &q, double s, const V3 &n, double Douter2, bool rotate) {
+  const double se = s > WALL_S_MIN ? s : WALL_S_MIN;
+  Q4 qz; qz.s = 0; qz.p.v[0] = 0; qz.p.v[1] = 0; qz.p.v[2] = 1;
+  Q4 qn; qn.s = 0; qn.p = n;
+  const Q4 qi = quat_mul(quat_mul(qz, q), qn);
+  pair_eval(o, r, q, r, qi, vmul(n, -2 * se), Douter2, rotate);
+  // a principal axis along n: X n is parallel to n, the torque's direction is 0/0 in pair_eval, and by symmetry there is none
+  if (o.tA.v[0] != o.tA.v[0] || o.tA.v[1] != o.tA.v[1] || o.tA.v[2] != o.tA.v[2]) { o.tA.v[0] = 0; o.tA.v[1] = 0; o.tA.v[2] = 0; }
+}
+
+// calc_motion (packing.h:399-428) and, by the first thread, Douter -= Relax (iterate, :347-348): nothing here reads Douter.
+// WALLS: only periodic axes wrap; a centre that lands on a wall node or off the field sets the error flag.
+template <bool WALLS>
 __global__ __launch_bounds__(256) void pk_motion(View v) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (halted(v.ctl)) return;
@@ -315,12 +400,15 @@ __global__ __launch_bounds__(256) void pk_motion(View v) {
 #pragma unroll
   for (int k = 0; k < 3; k++) { f.v[k] = v.f[k][i]; fu.v[k] = v.fu[k][i]; }
   v.fnorm[i] = sqrt(dot3(f, f));   // :408
+  V3 xn;
 #pragma unroll
   for (int k = 0; k < 3; k++) {    // :410-412, vector3::pbc (geometry.h:104-112)
     double x = v.pos[k][i] + f.v[k] * v.eps_scl;
-    if (x < 0) x += v.box[k]; else if (x > v.box[k]) x -= v.box[k];
+    if (!WALLS || v.wrap[k]) { if (x < 0) x += v.box[k]; else if (x > v.box[k]) x -= v.box[k]; }
     v.pos[k][i] = x;
+    xn.v[k] = x;
   }
+  if (WALLS && wall_hit(v, xn)) atomicMax(&v.ctl->error, ERR_WALL_NODE);
   if (!v.rotate || sphere(v.size + 3 * v.spec[i])) return;   // :415-417
   const double len = v.eps_rot * sqrt(dot3(fu, fu));
   const double cp = 1 / sqrt(1 + len * len);
@@ -405,6 +493,8 @@ __device__ __forceinline__ void load_particle(const View &v, int i, double r[3],
 }
 
 // One thread per list slot: the pair (A, B) of particle i and its partner, and i's own share of it.
+// WALLS: the minimum image is taken on periodic axes only.
+template <bool WALLS>
 __global__ __launch_bounds__(256) void pk_pair(View v) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (halted(v.ctl)) return;
@@ -418,14 +508,14 @@ __global__ __launch_bounds__(256) void pk_pair(View v) {
 #pragma unroll
   for (int k = 0; k < 3; k++) {   // rij = pos_B - pos_A, then pbc_diff (packing.h:483-484, geometry.h:113-121), on both paths
     double d = xb.v[k] - xa.v[k];
-    if (d < -v.half[k]) d += v.box[k]; else if (d > v.half[k]) d -= v.box[k];
+    if (!WALLS || v.wrap[k]) { if (d < -v.half[k]) d += v.box[k]; else if (d > v.half[k]) d -= v.box[k]; }
     rij.v[k] = d;
   }
   const double Douter2 = v.ctl->Douter2;
   PairResult o;
   pair_eval(o, ra, qa, rb, qb, rij, Douter2, v.rotate != 0);
   atomicMax(&v.ctl->maxeval, o.evals);
-  if (o.capped) atomicMax(&v.ctl->error, 1);
+  if (o.capped) atomicMax(&v.ctl->error, ERR_ROOT_CAP);
   const size_t stride = (size_t)v.N * v.K;
   const bool isA = i == A;
   const V3 tq = isA ? o.tA : o.tB;
@@ -437,7 +527,36 @@ __global__ __launch_bounds__(256) void pk_pair(View v) {
   v.rec[6 * stride + t] = o.kind == 2 ? o.fscl : Douter2;   // :131, overlapping pairs only
 }
 
-// A particle's force and torque: its slots added in list order, which is ascending partner index.
+// The wall slot of particle i, one thread each: while s < 0.55 Douter (largest axis), pk_bin's cut-off for a pair of two such
+// particles halved, i takes the A side of the pair with its mirror image.  Without the slot (beyond the cut-off, or no
+// gradient) the record is what a pair that does not overlap leaves: zero force and torque, Douter^2 as candidate.
+__global__ __launch_bounds__(256) void pk_wall(View v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (halted(v.ctl) || i >= v.N) return;
+  double r[3]; Q4 q; V3 x;
+  load_particle(v, i, r, q, x);
+  double amax = r[0];
+  if (r[1] > amax) amax = r[1];
+  if (r[2] > amax) amax = r[2];
+  const double Douter2 = v.ctl->Douter2;
+  const double cut = 0.55 * v.ctl->Douter * amax;
+  double rec[7] = {0, 0, 0, 0, 0, 0, Douter2};
+  double s; V3 n;
+  if (wall_sample(v, x, &s, &n) && s < cut) {
+    PairResult o;
+    wall_eval(o, r, q, s, n, Douter2, v.rotate != 0);
+    atomicMax(&v.ctl->maxeval, o.evals);
+    if (o.capped) atomicMax(&v.ctl->error, ERR_ROOT_CAP);
+#pragma unroll
+    for (int k = 0; k < 3; k++) { rec[k] = -o.f.v[k]; rec[3 + k] = -o.tA.v[k]; }
+    if (o.kind == 2) rec[6] = o.fscl;
+  }
+#pragma unroll
+  for (int k = 0; k < 7; k++) v.wrec[(size_t)k * v.N + i] = rec[k];
+}
+
+// A particle's force and torque: its slots added in list order, which is ascending partner index; WALLS: then the wall slot.
+template <bool WALLS>
 __global__ __launch_bounds__(256) void pk_sum(View v) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (halted(v.ctl) || i >= v.N) return;
@@ -448,6 +567,12 @@ __global__ __launch_bounds__(256) void pk_sum(View v) {
 #pragma unroll
     for (int k = 0; k < 6; k++) a[k] += v.rec[k * stride + at + s];
     const double d = v.rec[6 * stride + at + s];
+    if (d < dmin) dmin = d;
+  }
+  if (WALLS) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) a[k] += v.wrec[(size_t)k * v.N + i];
+    const double d = v.wrec[(size_t)6 * v.N + i];
     if (d < dmin) dmin = d;
   }
 #pragma unroll
@@ -522,6 +647,56 @@ __global__ __launch_bounds__(256) void pk_probe(int n, const double *in /*[n][21
   iout[3 * t] = o.kind; iout[3 * t + 1] = o.evals; iout[3 * t + 2] = o.capped ? 1 : 0;
 }
 
+// hc_packing_walls: the same wall_eval on caller-given particles, distances and normals
+__global__ __launch_bounds__(256) void pk_wall_probe(int n, const double *in /*[n][12]*/, int rotate, double *out /*[n][7]*/, int *iout /*[n][3]*/) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const double *x = in + 12 * (size_t)t;
+  double r[3]; V3 p, nv;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { r[k] = x[k]; p.v[k] = x[4 + k]; nv.v[k] = x[8 + k]; }
+  const Q4 q = quat_make(x[3], p);
+  PairResult o;
+  wall_eval(o, r, q, x[7], nv, x[11], rotate != 0);
+  double *y = out + 7 * (size_t)t;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { y[k] = 0.0 - o.f.v[k]; y[3 + k] = 0.0 - o.tA.v[k]; }
+  y[6] = o.kind == 2 ? o.fscl : x[11];
+  iout[3 * t] = o.kind; iout[3 * t + 1] = o.evals; iout[3 * t + 2] = o.capped ? 1 : 0;
+}
+
+// The wall's distance field: exact squared Euclidean distance in node spacings from every node to the nearest wall node,
+// truncated at R, as three separable passes min_k g[k] + (k - j)^2 on integers (z, then y, then x).  One thread per node
+// with z fastest, so that the lanes of a wave read consecutive z in every pass.  Integer minima: no order dependence.
+constexpr int EDT_FAR = 1 << 29;
+__global__ __launch_bounds__(256) void pk_edt_init(size_t n, const unsigned char *mask, int *g) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < n) g[t] = mask[t] ? 0 : EDT_FAR;
+}
+__global__ __launch_bounds__(256) void pk_edt_pass(size_t n, const int *in, int *out, int d0, int d1, int d2, int axis, int wrap, int R) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const int z = (int)(t % d2), y = (int)((t / d2) % d1), x = (int)(t / ((size_t)d2 * d1));
+  const int j = axis == 0 ? x : (axis == 1 ? y : z), d = axis == 0 ? d0 : (axis == 1 ? d1 : d2);
+  const size_t stride = axis == 0 ? (size_t)d1 * d2 : (axis == 1 ? (size_t)d2 : 1);
+  const size_t base = t - (size_t)j * stride;
+  int best = EDT_FAR;
+  for (int o = -R; o <= R; o++) {
+    int k = j + o;
+    if (wrap) { k %= d; if (k < 0) k += d; }
+    else if (k < 0 || k >= d) continue;
+    const int g = in[base + (size_t)k * stride];
+    if (g < EDT_FAR && g + o * o < best) best = g + o * o;
+  }
+  out[t] = best;
+}
+__global__ __launch_bounds__(256) void pk_edt_finish(size_t n, const int *g, int R, double *snode) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const int d2 = g[t] < R * R ? g[t] : R * R;
+  snode[t] = sqrt((double)d2) - 0.5;   // the surface lies halfway to the wall node; a wall node gets -0.5
+}
+
 }  // namespace
 
 struct hc_packing {
@@ -531,6 +706,9 @@ struct hc_packing {
   hc::DevBuf<double> size, part, rec; // part: pos, quat, f, fu, fnorm, pmin = 15 arrays of N
   bool resume = false;                // an iteration moved the particles and then found the lists too short
   size_t max_slots;
+  hc::DevBuf<double> snode, wrec;     // walls: the distance field and the wall slots' records
+  bool started = false;               // a run has queued iterations: too late for hc_packing_set_walls
+  int wall_R = 0;                     // truncation of the distance field, in nodes
 };
 
 namespace {
@@ -552,8 +730,15 @@ void pk_queue_forces(hc_packing *P, int first) {
   const unsigned nb = (unsigned)((v.N + 255) / 256);
   hipLaunchKernelGGL(pk_bin, dim3(nb), dim3(256), 0, hc::stream(), v);
   hipLaunchKernelGGL(pk_list, dim3((unsigned)((v.N + 3) / 4)), dim3(256), 0, hc::stream(), v);
-  hipLaunchKernelGGL(pk_pair, dim3((unsigned)(((size_t)v.N * v.K + 255) / 256)), dim3(256), 0, hc::stream(), v);
-  hipLaunchKernelGGL(pk_sum, dim3(nb), dim3(256), 0, hc::stream(), v);
+  const dim3 slots((unsigned)(((size_t)v.N * v.K + 255) / 256));
+  if (v.walls) {
+    hipLaunchKernelGGL(pk_pair<true>, slots, dim3(256), 0, hc::stream(), v);
+    hipLaunchKernelGGL(pk_wall, dim3(nb), dim3(256), 0, hc::stream(), v);
+    hipLaunchKernelGGL(pk_sum<true>, dim3(nb), dim3(256), 0, hc::stream(), v);
+  } else {
+    hipLaunchKernelGGL(pk_pair<false>, slots, dim3(256), 0, hc::stream(), v);
+    hipLaunchKernelGGL(pk_sum<false>, dim3(nb), dim3(256), 0, hc::stream(), v);
+  }
   hipLaunchKernelGGL(pk_control, dim3(1), dim3(256), 0, hc::stream(), v, first);
 }
 
@@ -605,6 +790,8 @@ int hc_packing_create(hc_packing **out, const int grid[3], int n_species, const 
   hc_packing *P = new hc_packing;
   View &v = P->v;
   v.N = N; v.ns = n_species; v.rotate = rotate ? 1 : 0;
+  v.walls = 0; v.wsp = 1; v.wmargin = 0; v.snode = nullptr; v.wrec = nullptr;
+  for (int k = 0; k < 3; k++) { v.wrap[k] = 1; v.wd[k] = 0; }
   // Packing::init, packing.h:268-289
   const int No_cells = grid[0] * grid[1] * grid[2];
   v.ncell_min = grid[0] < grid[1] ? grid[0] : grid[1];
@@ -688,8 +875,12 @@ int hc_packing_run(hc_packing *P, int max_steps, double status[12]) {
   HC_REQUIRE(max_steps >= 0, "hc_packing_run: max_steps < 0");
   const View &v = P->v;
   const unsigned nb = (unsigned)((v.N + 255) / 256);
+  if (max_steps > 0) P->started = true;
   for (int s = 0; s < max_steps; s++) {
-    if (!P->resume) hipLaunchKernelGGL(pk_motion, dim3(nb), dim3(256), 0, hc::stream(), v);
+    if (!P->resume) {
+      if (v.walls) hipLaunchKernelGGL(pk_motion<true>, dim3(nb), dim3(256), 0, hc::stream(), v);
+      else hipLaunchKernelGGL(pk_motion<false>, dim3(nb), dim3(256), 0, hc::stream(), v);
+    }
     P->resume = false;
     pk_queue_forces(P, 0);
   }
@@ -699,6 +890,7 @@ int hc_packing_run(hc_packing *P, int max_steps, double status[12]) {
   if (rc != HC_OK) return rc;
   status[0] = c.steps; status[1] = c.finished; status[2] = c.Douter; status[3] = c.Dinner; status[4] = c.Pactual; status[5] = c.DensityNominal;
   status[6] = c.Force_step; status[7] = c.Relax; status[8] = c.Nsf; status[9] = c.error; status[10] = c.maxeval; status[11] = c.grow;
+  if (c.error == ERR_WALL_NODE) { hc::set_error("hc_packing_run: a particle's centre reached a wall node or left the wall field"); return HC_ERR_STATE; }
   if (c.error) { hc::set_error("hc_packing_run: a pair's root search did not end within 256 evaluations (non-finite state?)"); return HC_ERR_STATE; }
   if (c.grow) {   // between runs: the interrupted iteration has moved and has no forces yet; the next run starts with them
     if ((rc = pk_grow(P, c)) != HC_OK) return rc;
@@ -760,6 +952,149 @@ int hc_packing_pairs(int n, const double *size_a, const double *quat_a, const do
     const double *y = &outv[17 * (size_t)t];
     lambda[t] = y[0]; f_ab_scl[t] = y[1];
     for (int k = 0; k < 3; k++) { nvec[3 * t + k] = y[2 + k]; f_a[3 * t + k] = y[5 + k]; t_a[3 * t + k] = y[8 + k]; f_b[3 * t + k] = y[11 + k]; t_b[3 * t + k] = y[14 + k]; }
+    evals[t] = iout[3 * t + 1];
+    kind[t] = iout[3 * t + 2] ? -1 : iout[3 * t];
+  }
+  return HC_OK;
+}
+
+int hc_packing_reserve_lists(hc_packing *P, int capacity) {
+  HC_REQUIRE(P, "hc_packing_reserve_lists: null pointer");
+  HC_REQUIRE(capacity >= 1, "hc_packing_reserve_lists: the capacity must be at least 1");
+  if (capacity > P->v.N - 1) capacity = P->v.N > 1 ? P->v.N - 1 : 1;
+  return pk_reserve_pairs(P, capacity);   // the lists are rebuilt by every force evaluation; one that does not fit grows them
+}
+
+int hc_packing_set_walls(hc_packing *P, const unsigned char *mask, const int dims[3], double spacing, const int periodic[3], double wall_margin) {
+  HC_REQUIRE(P && mask && dims && periodic, "hc_packing_set_walls: null pointer");
+  HC_REQUIRE(!P->started, "hc_packing_set_walls: the packing has run; walls are set before the first hc_packing_run");
+  HC_REQUIRE(!P->v.walls, "hc_packing_set_walls: walls are already set");
+  HC_REQUIRE(std::isfinite(spacing) && spacing > 0, "hc_packing_set_walls: the spacing must be positive and finite");
+  HC_REQUIRE(std::isfinite(wall_margin) && wall_margin >= 0, "hc_packing_set_walls: the wall margin must be finite and not negative");
+  View &v = P->v;
+  size_t n = 1;
+  for (int k = 0; k < 3; k++) {
+    HC_REQUIRE(dims[k] >= 2 && dims[k] <= 4096, "hc_packing_set_walls: mask nodes per axis must be 2..4096");
+    n *= (size_t)dims[k];
+    if (periodic[k])
+      HC_REQUIRE(std::fabs(dims[k] * spacing - v.box[k]) <= 1e-9 * v.box[k],
+                 "hc_packing_set_walls: the mask and the box disagree: on a periodic axis nodes x spacing must equal the box");
+    else
+      HC_REQUIRE((dims[k] - 1) * spacing <= v.box[k] * (1 + 1e-9),
+                 "hc_packing_set_walls: the mask and the box disagree: the mask is longer than the box");
+  }
+  HC_REQUIRE(n < ((size_t)1 << 31), "hc_packing_set_walls: too many mask nodes");
+  const size_t sy = (size_t)dims[2], sx = sy * dims[1];
+  for (int k = 0; k < 3; k++) {
+    if (periodic[k]) continue;
+    const int a = (k + 1) % 3, b = (k + 2) % 3;
+    const size_t st[3] = {sx, sy, 1};
+    bool closed = true;
+    for (int i = 0; i < dims[a] && closed; i++)
+      for (int j = 0; j < dims[b]; j++) {
+        const size_t at = i * st[a] + j * st[b];
+        if (!mask[at] || !mask[at + (size_t)(dims[k] - 1) * st[k]]) { closed = false; break; }
+      }
+    if (!closed) {
+      hc::set_error(std::string("hc_packing_set_walls: axis ") + "xyz"[k] + " is not periodic and has an open face: every node of both of its faces must be wall");
+      return HC_ERR_ARG;
+    }
+  }
+
+  // the field is needed as far as the largest wall cut-off at the first diameter reaches, margin and half a node included
+  Ctl c;
+  int rc = pk_read_ctl(P, &c);
+  if (rc != HC_OK) return rc;
+  std::vector<double> sizes(3 * (size_t)v.ns), pos(3 * (size_t)v.N);
+  HC_HIP(hipMemcpy(sizes.data(), P->size.p, sizes.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HC_HIP(hipMemcpy(pos.data(), P->part.p, pos.size() * sizeof(double), hipMemcpyDeviceToHost));
+  double amax = 0;
+  for (double a : sizes) if (a > amax) amax = a;
+  const double reach = (0.55 * c.Douter * amax + wall_margin) / spacing + 0.5;
+  HC_REQUIRE(reach < 4000, "hc_packing_set_walls: the spacing is too fine for the particles (the distance field would reach past 4000 nodes)");
+  const int R = (int)std::ceil(reach) + 1;
+  for (int i = 0; i < v.N; i++) {
+    size_t at = 0;
+    bool out = false;
+    for (int k = 0; k < 3; k++) {
+      const double u = pos[(size_t)k * v.N + i] / spacing;
+      if (!periodic[k] && !(u >= 0 && u <= dims[k] - 1)) { out = true; break; }
+      int node = (int)std::floor(u + 0.5);
+      node = periodic[k] ? ((node % dims[k]) + dims[k]) % dims[k] : (node > dims[k] - 1 ? dims[k] - 1 : node);
+      at = at * dims[k] + node;
+    }
+    HC_REQUIRE(!out && !mask[at], "hc_packing_set_walls: a particle starts on a wall node or outside the mask");
+  }
+
+  hc::DevBuf<unsigned char> dmask;
+  hc::DevBuf<int> g0, g1;
+  if ((rc = dmask.reserve(n)) != HC_OK || (rc = g0.reserve(n)) != HC_OK || (rc = g1.reserve(n)) != HC_OK || (rc = P->snode.reserve(n)) != HC_OK ||
+      (rc = P->wrec.reserve(7 * (size_t)v.N)) != HC_OK)
+    return rc;
+  HC_HIP(hipMemcpyAsync(dmask.p, mask, n, hipMemcpyHostToDevice, hc::stream()));
+  const dim3 nb((unsigned)((n + 255) / 256));
+  hipLaunchKernelGGL(pk_edt_init, nb, dim3(256), 0, hc::stream(), n, (const unsigned char *)dmask.p, g0.p);
+  hipLaunchKernelGGL(pk_edt_pass, nb, dim3(256), 0, hc::stream(), n, (const int *)g0.p, g1.p, dims[0], dims[1], dims[2], 2, periodic[2] ? 1 : 0, R);
+  hipLaunchKernelGGL(pk_edt_pass, nb, dim3(256), 0, hc::stream(), n, (const int *)g1.p, g0.p, dims[0], dims[1], dims[2], 1, periodic[1] ? 1 : 0, R);
+  hipLaunchKernelGGL(pk_edt_pass, nb, dim3(256), 0, hc::stream(), n, (const int *)g0.p, g1.p, dims[0], dims[1], dims[2], 0, periodic[0] ? 1 : 0, R);
+  hipLaunchKernelGGL(pk_edt_finish, nb, dim3(256), 0, hc::stream(), n, (const int *)g1.p, R, P->snode.p);
+  HC_HIP(hipGetLastError());
+  HC_HIP(hipStreamSynchronize(hc::stream()));   // dmask, g0 and g1 go out of scope
+
+  v.walls = 1; v.wsp = spacing; v.wmargin = wall_margin; v.snode = P->snode; v.wrec = P->wrec;
+  for (int k = 0; k < 3; k++) { v.wrap[k] = periodic[k] ? 1 : 0; v.wd[k] = dims[k]; }
+  P->wall_R = R;
+  // the calc_forces before the first iteration once more, now with the wall slot and the axes that no longer wrap; the
+  // counters of the periodic evaluation that hc_packing_create ran are dropped
+  HC_HIP(hipMemsetAsync(&P->ctl.p->maxeval, 0, 2 * sizeof(int), hc::stream()));   // maxeval, maxcount
+  for (int attempt = 0;; attempt++) {
+    pk_queue_forces(P, 1);
+    HC_HIP(hipGetLastError());
+    if ((rc = pk_read_ctl(P, &c)) != HC_OK) return rc;
+    if (c.error) { hc::set_error("hc_packing_set_walls: a pair's root search did not end within 256 evaluations"); return HC_ERR_STATE; }
+    if (!c.grow) break;
+    if (attempt >= 4) { hc::set_error("hc_packing_set_walls: the pair lists did not settle"); return HC_ERR_STATE; }
+    if ((rc = pk_grow(P, c)) != HC_OK) return rc;
+  }
+  return HC_OK;
+}
+
+int hc_packing_wall_field(hc_packing *P, double *s_node) {
+  HC_REQUIRE(P && s_node, "hc_packing_wall_field: null pointer");
+  HC_REQUIRE(P->v.walls, "hc_packing_wall_field: no walls are set");
+  const size_t n = (size_t)P->v.wd[0] * P->v.wd[1] * P->v.wd[2];
+  HC_HIP(hipMemcpyAsync(s_node, P->snode.p, n * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  return HC_OK;
+}
+
+int hc_packing_walls(int n, const double *size, const double *quat, const double *s, const double *normal, const double *douter2, int rotate,
+                     double *force, double *torque, double *candidate, int *evals, int *kind) {
+  HC_REQUIRE(n >= 0, "hc_packing_walls: n < 0");
+  if (n == 0) return HC_OK;
+  HC_REQUIRE(size && quat && s && normal && douter2 && force && torque && candidate && evals && kind, "hc_packing_walls: null pointer");
+  std::vector<double> in(12 * (size_t)n), outv(7 * (size_t)n);
+  std::vector<int> iout(3 * (size_t)n);
+  for (int t = 0; t < n; t++) {
+    double *x = &in[12 * (size_t)t];
+    for (int k = 0; k < 3; k++) { x[k] = size[3 * t + k]; x[8 + k] = normal[3 * t + k]; }
+    for (int k = 0; k < 4; k++) x[3 + k] = quat[4 * t + k];
+    x[7] = s[t]; x[11] = douter2[t];
+  }
+  HC_REQUIRE(all_finite(in.data(), in.size()), "hc_packing_walls: non-finite input");
+  hc::DevBuf<double> din, dout; hc::DevBuf<int> diout;
+  int rc;
+  if ((rc = din.reserve(in.size())) != HC_OK || (rc = dout.reserve(outv.size())) != HC_OK || (rc = diout.reserve(iout.size())) != HC_OK) return rc;
+  HC_HIP(hipMemcpyAsync(din.p, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, hc::stream()));
+  hipLaunchKernelGGL(pk_wall_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), n, (const double *)din.p, rotate, dout.p, diout.p);
+  HC_HIP(hipGetLastError());
+  HC_HIP(hipMemcpyAsync(outv.data(), dout.p, outv.size() * sizeof(double), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipMemcpyAsync(iout.data(), diout.p, iout.size() * sizeof(int), hipMemcpyDeviceToHost, hc::stream()));
+  HC_HIP(hipStreamSynchronize(hc::stream()));
+  for (int t = 0; t < n; t++) {
+    const double *y = &outv[7 * (size_t)t];
+    for (int k = 0; k < 3; k++) { force[3 * t + k] = y[k]; torque[3 * t + k] = y[3 + k]; }
+    candidate[t] = y[6];
     evals[t] = iout[3 * t + 1];
     kind[t] = iout[3 * t + 2] ? -1 : iout[3 * t];
   }

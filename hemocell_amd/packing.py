@@ -100,7 +100,7 @@ def _c_round(x):
     return int(np.floor(x + 0.5)) if x >= 0 else -int(np.floor(-x + 0.5))
 
 
-def packing_plan(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=None):
+def packing_plan(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=None, volume_um3=None):
     """packCells.cpp:197-241 and Packing::initBlood (packing.h:198-262), pure host code.
 
     size_um: the requested box; cells: a list of (name, count) with a name of CELL_SIZES_UM, or (name, count, (dx, dy, dz))
@@ -109,7 +109,8 @@ def packing_plan(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=Non
     scale=None is 1.2 / (largest axis of the most numerous type).  Reference quirks that stay: the grid is ceil(size * scale)
     cells per axis, so the packed box (box_um) is larger than requested (24 um: 4 cells = 28 um) while the nominal fraction
     is computed from the requested size; the reference carries the hematocrit and the scaled box sizes in single precision,
-    which decides the rounding of a borderline count or grid and is kept."""
+    which decides the rounding of a borderline count or grid and is kept.  volume_um3 (this back end's own, for a vessel inside
+    the box): the hematocrit's cell counts come from this volume, the lumen, and not from the box; nothing else changes."""
     size = [float(s) for s in size_um]
     if len(size) != 3 or not all(np.isfinite(s) and s > 0 for s in size):
         raise ValueError("size_um must be three positive lengths")
@@ -134,6 +135,10 @@ def packing_plan(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=Non
         if not (np.isfinite(h) and h >= 0):
             raise ValueError("hematocrit must be a non-negative number")
         volume = size[0] * size[1] * size[2]
+        if volume_um3 is not None:
+            volume = float(volume_um3)
+            if not (np.isfinite(volume) and volume > 0):
+                raise ValueError("volume_um3 must be a positive volume")
         n_rbc = _c_round(h * volume / RBC_VOLUME_NOMINAL_UM3)
         types.append(("RBC", n_rbc, CELL_SIZES_UM["RBC"]))
         n_plt = _c_round(n_rbc * float(plt_ratio))
@@ -236,35 +241,185 @@ def progress_line(status):
     return "%9d%14.10f%14.10f%14.10f%14.10f%19.15f" % (int(status[0]), status[4], status[5], status[3], status[2], status[6])
 
 
+def wall_distance_field(mask, periodic, truncation):
+    """The packing's wall field on the host, as hc_packing_set_walls builds it on the device: sqrt(min(d^2, R^2)) - 1/2 per
+    node, d the exact Euclidean distance in node spacings to the nearest wall node (periodic axes wrap), R = truncation;
+    three separable passes min over k of g[k] + (k - j)^2 on integers, along z, y and x in turn.  uint8 mask [nx][ny][nz],
+    1 = wall; returns float64 of the same shape, -1/2 on wall nodes."""
+    m = np.asarray(mask)
+    R = int(truncation)
+    far = 1 << 40
+    g = np.where(m != 0, 0, far).astype(np.int64)
+    for axis in (2, 1, 0):
+        n = m.shape[axis]
+        best = np.full(m.shape, far, dtype=np.int64)
+        for o in range(-R, R + 1):
+            if periodic[axis]:
+                cand = np.roll(g, -o, axis=axis)   # cand[j] = g[(j + o) mod n]
+            else:
+                if abs(o) >= n:
+                    continue
+                cand = np.full(m.shape, far, dtype=np.int64)
+                dst = [slice(None)] * 3
+                src = [slice(None)] * 3
+                dst[axis] = slice(max(0, -o), n - max(0, o))
+                src[axis] = slice(max(0, o), n - max(0, -o))
+                cand[tuple(dst)] = g[tuple(src)]
+            best = np.minimum(best, np.where(cand < far, cand + o * o, far))
+        g = best
+    return np.sqrt(np.minimum(g, R * R).astype(np.float64)) - 0.5
+
+
+def _check_walls(mask, mask_dx_um, periodic, size_um):
+    """the refusals of a wall mask that need no device, with the messages of hc_packing_set_walls"""
+    m = np.asarray(mask)
+    if m.ndim != 3 or min(m.shape) < 2:
+        raise ValueError("wall_mask must be a three-dimensional array with at least 2 nodes per axis")
+    if mask_dx_um is None or not (np.isfinite(mask_dx_um) and mask_dx_um > 0):
+        raise ValueError("a wall mask needs its node spacing mask_dx_um")
+    periodic = tuple(bool(p) for p in periodic)
+    if len(periodic) != 3:
+        raise ValueError("periodic must hold one flag per axis")
+    for k in range(3):
+        if periodic[k]:
+            if abs(m.shape[k] * mask_dx_um - size_um[k]) > 1e-9 * size_um[k]:
+                raise ValueError("the mask and the box disagree: axis %s is periodic, so its %d nodes x %g um must equal the box's %g um"
+                                 % ("xyz"[k], m.shape[k], mask_dx_um, size_um[k]))
+            continue
+        if (m.shape[k] - 1) * mask_dx_um > size_um[k] * (1 + 1e-9):
+            raise ValueError("the mask and the box disagree: the mask is longer than the box along %s" % "xyz"[k])
+        faces = np.take(m, [0, m.shape[k] - 1], axis=k)
+        if not (faces != 0).all():
+            raise ValueError("axis %s is not periodic and has an open face: every node of both of its faces must be wall" % "xyz"[k])
+    return np.ascontiguousarray(m != 0, dtype=np.uint8), periodic
+
+
+def _wall_scale(size_um, periodic, scale0):
+    """the sizing factor nearest above scale0 at which every periodic axis is a whole number of grid cells long"""
+    axes = [k for k in range(3) if periodic[k]]
+    if not axes:
+        return scale0
+    scale = float(np.ceil(size_um[axes[0]] * scale0 - 1e-9)) / size_um[axes[0]]
+    for k in axes[1:]:
+        g = size_um[k] * scale
+        if abs(g - round(g)) > 1e-9 * g:
+            raise ValueError("the periodic axes %s and %s cannot both be a whole number of grid cells long at one sizing factor"
+                             % ("xyz"[axes[0]], "xyz"[k]))
+    return scale
+
+
+def wall_plan(size_um, wall_mask, mask_dx_um, periodic, hematocrit=None, plt_ratio=0.07, cells=None, scale=None):
+    """what pack_cells decides for a packing inside walls: (plan, mask as uint8, periodic, lumen volume in um^3).  The mask is
+    checked against the box, the hematocrit counts cells for the lumen (fluid nodes x mask_dx_um^3), and without a given
+    scale the sizing factor is the smallest one above 1.2 / (largest axis) that makes the periodic axes whole grid cells."""
+    size_um = [float(s) for s in size_um]
+    if len(size_um) != 3 or not all(np.isfinite(s) and s > 0 for s in size_um):
+        raise ValueError("size_um must be three positive lengths")
+    mask, periodic = _check_walls(wall_mask, mask_dx_um, periodic, size_um)
+    volume = float((mask == 0).sum()) * float(mask_dx_um) ** 3
+    if volume <= 0:
+        raise ValueError("the wall mask has no fluid node")
+    if scale is None or scale <= 0.0:
+        scale = _wall_scale(size_um, periodic, packing_plan(size_um, hematocrit, plt_ratio, cells, None, volume).scale)
+    return packing_plan(size_um, hematocrit, plt_ratio, cells, scale, volume), mask, periodic, volume
+
+
+def wall_start(plan, mask, mask_dx_um, periodic, margin_um, rng):
+    """the initial centres of a packing inside walls, by the rule of pack_cells' docstring: (pos [N][3] in grid cells, the mask's
+    spacing and the margin in grid cells)"""
+    grid = np.array(plan.grid, dtype=np.float64)
+    sizes = plan.sizes_scaled
+    n = sum(plan.counts)
+    spacing, margin = mask_dx_um * plan.scale, margin_um * plan.scale
+    for k in range(3):
+        if periodic[k] and abs(mask.shape[k] * spacing - grid[k]) > 1e-9 * grid[k]:
+            raise ValueError("the mask and the box disagree: at sizing factor %g the periodic axis %s is %g grid cells long"
+                             % (plan.scale, "xyz"[k], mask.shape[k] * spacing))
+    douter0 = (float(np.prod(grid)) / (3.141592653589793 / 6.) / n * plan.nominal_fraction) ** (1. / 3.)
+    reach = (0.55 * douter0 * float(sizes.max()) + margin) / spacing + 0.5
+    wall_s = wall_distance_field(mask, periodic, int(np.ceil(reach)) + 1) * spacing - margin
+    pos = np.zeros((n, 3))
+    dims = np.array(mask.shape)
+    at = 0
+    for s, count in enumerate(plan.counts):
+        bound = 0.5 * float(sizes[s].min()) * douter0
+        if int((wall_s > bound).sum()) < count:
+            bound = 0.0
+            if not (wall_s > bound).any():
+                raise ValueError("no mask node is further than the wall margin from the wall")
+        for _ in range(count):
+            while True:
+                x = rng.random(3) * grid
+                node = np.floor(x / spacing + 0.5).astype(np.int64)
+                ok = True
+                for k in range(3):
+                    if periodic[k]:
+                        node[k] %= dims[k]
+                    elif node[k] > dims[k] - 1:
+                        ok = False
+                if ok and wall_s[tuple(node)] > bound:
+                    break
+            pos[at] = x
+            at += 1
+    return pos, spacing, margin
+
+
 def pack_cells(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=None, rotate=True, max_iter=MAX_ITER_DEFAULT, seed=0,
-               steps_per_wait=64, progress=None):
+               steps_per_wait=64, progress=None, wall_mask=None, mask_dx_um=None, periodic=(True, True, True), wall_margin_um=None):
     """Bargiel's force-biased packing of the cell types' enclosing ellipsoids in a periodic box, on the GPU.
 
     The plan is packing_plan's.  Every ellipsoid starts at a uniform random point of the box, drawn here from
     numpy.random.Generator(PCG64(seed)) in particle order (the reference seeds drand48 with the clock), with the identity
     orientation; the outer diameter shrinks while overlapping pairs push and turn each other (rotate=False: push only), until
     no pair overlaps or max_iter iterations are done.  The device queues steps_per_wait iterations per host wait;
-    progress(status) is called after each wait.  Returns a PackResult; see packing_plan for the reference quirks that stay."""
+    progress(status) is called after each wait.  Returns a PackResult; see packing_plan for the reference quirks that stay.
+
+    wall_mask (uint8 [nx][ny][nz], 1 = wall, node i at i * mask_dx_um) packs inside walls: a cell near a wall is also pushed
+    by its own mirror image across the wall's tangent plane (hc_packing_set_walls).  periodic says which axes wrap; a
+    periodic axis must be nodes x mask_dx_um = size_um long, any other needs wall on both faces and the mask inside the box.
+    The hematocrit then counts cells for the lumen, fluid nodes x mask_dx_um^3.  With scale=None the sizing factor is raised
+    from 1.2 / (largest axis) until the first periodic axis is a whole number of grid cells, so that the packed box is the
+    mask's period.  wall_margin_um, default one mask_dx_um, is taken off every wall distance.
+    Initial centres with walls: the same PCG64(seed) stream, particle by particle in particle order; a candidate is three
+    doubles times the grid, and it is rejected and the next three drawn unless the mask node nearest to it (half up, wrapped
+    on periodic axes) has a wall distance, spacing x s_node - margin, above the species' smallest semi-axis at the initial
+    outer diameter.  A species with fewer such nodes than cells takes every node with a wall distance above 0 instead."""
     import ctypes as C
     from . import capi, host
-    plan = packing_plan(size_um, hematocrit, plt_ratio, cells, scale)
+    walls = wall_mask is not None
+    volume = None
+    if walls:
+        plan, mask, periodic, volume = wall_plan(size_um, wall_mask, mask_dx_um, periodic, hematocrit, plt_ratio, cells, scale)
+        mask_dx_um = float(mask_dx_um)
+        margin_um = mask_dx_um if wall_margin_um is None else float(wall_margin_um)
+        if not (np.isfinite(margin_um) and margin_um >= 0):
+            raise ValueError("wall_margin_um must be finite and not negative")
+    else:
+        plan = packing_plan(size_um, hematocrit, plt_ratio, cells, scale)
     n = sum(plan.counts)
     if n == 0:
         raise ValueError("no cells to pack")
     if max_iter < 0 or steps_per_wait < 1:
         raise ValueError("max_iter must be >= 0 and steps_per_wait >= 1")
-    host.ensure_init()
-    lib = capi.lib()
     grid = np.array(plan.grid, dtype=np.int32)
-    rng = np.random.Generator(np.random.PCG64(seed))
-    pos = np.ascontiguousarray(rng.random((n, 3)) * grid.astype(np.float64))
     sizes = np.ascontiguousarray(plan.sizes_scaled)
     counts = np.array(plan.counts, dtype=np.int32)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    if walls:
+        pos, spacing, margin = wall_start(plan, mask, mask_dx_um, periodic, margin_um, rng)
+    else:
+        pos = np.ascontiguousarray(rng.random((n, 3)) * grid.astype(np.float64))
+    host.ensure_init()
+    lib = capi.lib()
     ip = C.POINTER(C.c_int)
     handle = C.c_void_p()
     capi.check(lib.hc_packing_create(C.byref(handle), grid.ctypes.data_as(ip), len(counts), capi.dptr(sizes), counts.ctypes.data_as(ip),
                                      capi.dptr(pos), None, plan.nominal_fraction, int(bool(rotate)), 0, 0.0))
     try:
+        if walls:
+            dims32 = np.array(mask.shape, dtype=np.int32)
+            per32 = np.array([int(p) for p in periodic], dtype=np.int32)
+            capi.check(lib.hc_packing_set_walls(handle, mask.ctypes.data, dims32.ctypes.data_as(ip), spacing, per32.ctypes.data_as(ip), margin))
         status = np.zeros(12)
         capi.check(lib.hc_packing_run(handle, 0, capi.dptr(status)))
         while not status[1] and int(status[0]) < max_iter:
@@ -275,7 +430,41 @@ def pack_cells(size_um, hematocrit=None, plt_ratio=0.07, cells=None, scale=None,
         capi.check(lib.hc_packing_state(handle, capi.dptr(pos), capi.dptr(quat), None, None))
     finally:
         lib.hc_packing_destroy(handle)
-    return PackResult(plan, pos * (1. / plan.scale), quat, status, seed)
+    res = PackResult(plan, pos * (1. / plan.scale), quat, status, seed)
+    res.lumen_volume_um3 = volume   # None without walls
+    return res
+
+
+def pipe_mask(length_um, radius_um, dx_um=0.5, axis=0):
+    """uint8 wall mask of a straight pipe along axis: round(length / dx) nodes along it, 2 ceil(radius / dx) + 3 across, fluid
+    where a node lies closer than radius / dx nodes to the centre line, so that both cross faces are wall"""
+    if axis not in (0, 1, 2):
+        raise ValueError("axis must be 0, 1 or 2")
+    if not (dx_um > 0 and radius_um > dx_um and length_um >= 2 * dx_um):
+        raise ValueError("a pipe needs dx_um > 0, a radius above dx_um and a length of at least two nodes")
+    n_len = int(round(length_um / dx_um))
+    if abs(n_len * dx_um - length_um) > 1e-9 * length_um:
+        raise ValueError("the pipe's length must be a whole number of dx_um, as it is periodic")
+    n_cross = 2 * int(np.ceil(radius_um / dx_um)) + 3
+    c = (n_cross - 1) / 2.0
+    a = np.arange(n_cross) - c
+    wall2d = (np.hypot(a[:, None], a[None, :]) >= radius_um / dx_um).astype(np.uint8)
+    mask = np.repeat(wall2d[None, :, :], n_len, axis=0)
+    return np.ascontiguousarray(np.moveaxis(mask, 0, axis))
+
+
+def pack_pipe(length_um, radius_um, hematocrit, dx_um=0.5, axis=0, plt_ratio=0.07, cells=None, rotate=True, max_iter=MAX_ITER_DEFAULT,
+              seed=0, steps_per_wait=64, progress=None, wall_margin_um=None):
+    """pack_cells inside pipe_mask(length_um, radius_um, dx_um, axis): periodic along axis, walls all round.  The box is the
+    mask's, (nodes - 1) dx_um across; the result carries the mask as .wall_mask and its spacing as .mask_dx_um."""
+    mask = pipe_mask(length_um, radius_um, dx_um, axis)
+    size = [(n - 1) * dx_um for n in mask.shape]
+    size[axis] = mask.shape[axis] * dx_um
+    periodic = tuple(k == axis for k in range(3))
+    res = pack_cells(size, hematocrit, plt_ratio, cells, None, rotate=rotate, max_iter=max_iter, seed=seed, steps_per_wait=steps_per_wait,
+                     progress=progress, wall_mask=mask, mask_dx_um=dx_um, periodic=periodic, wall_margin_um=wall_margin_um)
+    res.wall_mask, res.mask_dx_um, res.periodic = mask, float(dx_um), periodic
+    return res
 
 
 def _main(argv=None):
@@ -300,6 +489,12 @@ def _main(argv=None):
              "  --maxiter <n>                           Maximum number of iterations\n"
              "  --seed <n>                              Seed of the initial positions, default=0\n"
              "  --outdir <dir>                          Directory the .pos files go to, default=.\n"
+             "  --pipe <radius>                         Pack a pipe of this radius [um] along x, sX long and periodic\n"
+             "                                          (sY and sZ are replaced by the pipe's cross-section)\n"
+             "  --mask <file.npy>                       Pack inside this wall mask, uint8 [nx][ny][nz], 1 = wall\n"
+             "  --mask-dx <um>                          Node spacing of the mask (and of --pipe, default=0.5)\n"
+             "  --periodic <axes>                       Periodic axes of the mask, e.g. x or xyz, default=xyz\n"
+             "  --wall-margin <um>                      Taken off every wall distance, default=one node spacing\n"
              "  --help                                  Print this\n"
              "OUTPUT:\n"
              "  <Cell>.pos for every cell type. The first line holds the number of cells,\n"
@@ -332,6 +527,11 @@ def _main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--help", action="store_true")
     ap.add_argument("--outdir", default=".")
+    ap.add_argument("--pipe", type=float)
+    ap.add_argument("--mask")
+    ap.add_argument("--mask-dx", dest="mask_dx", type=float, default=0.5)
+    ap.add_argument("--periodic", default="xyz")
+    ap.add_argument("--wall-margin", dest="wall_margin", type=float)
     ap.error = lambda msg: (sys.stderr.write(msg + "\n\n" + usage), sys.exit(1))
     a = ap.parse_args(argv)
     if a.help:
@@ -342,14 +542,25 @@ def _main(argv=None):
         sys.stderr.write(usage)
         return 1
     size = [int(float(s)) for s in a.size]   # atoi, packCells.cpp:193-195
+    mask, periodic = None, (True, True, True)
     try:
-        plan = packing_plan(size, a.hematocrit, a.plt_ratio, order, a.scale)
-    except ValueError as e:
+        if a.pipe is not None and a.mask is not None:
+            raise ValueError("--pipe excludes --mask")
+        if a.pipe is not None:
+            mask, periodic = pipe_mask(size[0], a.pipe, a.mask_dx, 0), (True, False, False)
+            size = [size[0], (mask.shape[1] - 1) * a.mask_dx, (mask.shape[2] - 1) * a.mask_dx]
+        elif a.mask is not None:
+            mask, periodic = np.load(a.mask), tuple(c in a.periodic.lower() for c in "xyz")
+        if mask is not None:
+            plan = wall_plan(size, mask, a.mask_dx, periodic, a.hematocrit, a.plt_ratio, order, a.scale)[0]
+        else:
+            plan = packing_plan(size, a.hematocrit, a.plt_ratio, order, a.scale)
+    except (ValueError, OSError) as e:
         sys.stderr.write("%s, exiting...\n" % e)
         sys.stderr.write(usage)
         return 1
     print("Parameters:")
-    print("  Domain Size [um]: ( %d , %d , %d )" % tuple(size))
+    print("  Domain Size [um]: ( %g , %g , %g )" % tuple(size) if mask is not None else "  Domain Size [um]: ( %d , %d , %d )" % tuple(size))
     print("  Maximum Iterations : %d" % a.maxiter)
     print("  Scale              : %.6f" % plan.scale)
     print("  Rotation           : %d" % (not a.noRotate))
@@ -367,9 +578,12 @@ def _main(argv=None):
     print("\nNominal requested volume fraction: %.6f" % plan.nominal_fraction)
     if plan.warning:
         print("*** WARNING ***\n" + plan.warning)
+    if mask is not None:
+        print("Walls: mask %d x %d x %d nodes at %g um, periodic in %s" % (mask.shape + (a.mask_dx, "".join(c for c, p in zip("xyz", periodic) if p) or "-")))
     print(PROGRESS_HEADER)
     res = pack_cells(size, a.hematocrit, a.plt_ratio, order, a.scale, rotate=not a.noRotate, max_iter=a.maxiter, seed=a.seed,
-                     progress=lambda st: print(progress_line(st), flush=True))
+                     progress=lambda st: print(progress_line(st), flush=True), wall_mask=mask, mask_dx_um=a.mask_dx if mask is not None else None,
+                     periodic=periodic, wall_margin_um=a.wall_margin)
     if not res.finished:
         print("WARNING: Force-free packing was NOT achieved! Potential overlaps might still exist.")
     print(" PACKING DONE " if res.finished else " PACKING TERMINATED(!) ")

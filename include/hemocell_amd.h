@@ -750,6 +750,33 @@ int hc_packing_pairs(int n, const double *size_a, const double *quat_a, const do
                      const double *douter2, int rotate, double *lambda, double *f_ab_scl, double *nvec, double *f_a, double *t_a,
                      double *f_b, double *t_b, int *evals, int *kind);
 int hc_packing_destroy(hc_packing *P);
+/* Walls (this back end's own; the reference packs periodic boxes only).  hc_packing_set_walls, after hc_packing_create and
+ * before the first hc_packing_run with max_steps > 0: mask is uint8 [dims0][dims1][dims2], 1 = wall, node i of an axis at
+ * i * spacing grid cells; periodic[k] = 0 stops the wrap of positions and of pair separations on axis k.  A particle whose
+ * centre lies at signed distance s < 0.55 Douter (its largest axis) from the wall surface gets one more partner, its own
+ * mirror image across the tangent plane: same axes, centre x - 2 s n, orientation H R diag(1, 1, -1) with H = I - 2 n n^T.
+ * s is the trilinear sample of the node field sqrt(d^2) - 1/2 (d: exact Euclidean distance in nodes to the nearest wall
+ * node, truncated; -1/2 on wall nodes) times spacing minus wall_margin, n its normalised gradient (below 1e-12: no wall
+ * partner that step).  The call builds the field on the device and repeats the first force evaluation.  Refused
+ * (HC_ERR_ARG): a run has been made, walls are set already, fewer than 2 or more than 4096 nodes on an axis, a periodic
+ * axis with dims * spacing != the box, a non-periodic one with (dims - 1) * spacing > the box or with a fluid node on one
+ * of its two faces, a particle that starts on a wall node.  While walls are set, a centre that ends an iteration nearest
+ * to a wall node, or off the mask on a non-periodic axis, sets the error flag to 2 (1 stays the root-search cap) and the
+ * run returns HC_ERR_STATE.
+ * hc_packing_wall_field: the node field [dims0][dims1][dims2], in node spacings.
+ * hc_packing_walls probes the wall partner as hc_packing_pairs probes a pair: sizes [n][3], quaternions [n][4], s [n],
+ * unit normals [n][3] into the fluid, douter2 [n].  Out: the particle's force and torque increments [n][3], the Dinner^2
+ * candidate (douter2 unless the pair overlaps), the root search's evaluations and kind as in hc_packing_pairs.  The image
+ * pair is evaluated at max(s, 1e-6); a torque whose direction is 0/0 (a principal axis along the normal) is returned as zero.
+ * hc_packing_reserve_lists sets the partner lists' capacity per particle (at most N - 1; storage is never given back).  The
+ * lists are rebuilt by every force evaluation, and one that does not fit grows them as status[11] describes, so a small
+ * capacity costs one interrupted iteration; it is there to test that path. */
+int hc_packing_set_walls(hc_packing *P, const unsigned char *mask, const int dims[3], double spacing, const int periodic[3],
+                         double wall_margin);
+int hc_packing_wall_field(hc_packing *P, double *s_node);
+int hc_packing_reserve_lists(hc_packing *P, int capacity);
+int hc_packing_walls(int n, const double *size, const double *quat, const double *s, const double *normal, const double *douter2,
+                     int rotate, double *force, double *torque, double *candidate, int *evals, int *kind);
 
 #ifdef __cplusplus
 }
