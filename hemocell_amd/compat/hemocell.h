@@ -284,14 +284,14 @@ inline void interpolationCoefficientsPhi2(plb::BlockLattice3D<T, DESCRIPTOR> &, 
 }
 // core/immersedBoundaryMethod.h:140-153 declares these two and the reference has no body for them.  Here
 // field.kernelMethod = interpolationCoefficientsPhi3 (or ...Phi4) selects the three-point (Roma) or four-point (Peskin) delta
-// function of csrc/ibm_wide.hip for the cell type (hcp_type_set_ibm_kernel, include/hemocell_amd.h: the definitions are this
+// function of csrc/ibm_common.h for the cell type (hcp_type_set_ibm_kernel, include/hemocell_amd.h: the definitions are this
 // back end's own).  Assign before the first call that needs the cells on the device (loadParticles, iterate, ...).
 inline void interpolationCoefficientsPhi3(plb::BlockLattice3D<T, DESCRIPTOR> &, HemoCellParticle &) {
-  std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi3 runs on the device (csrc/ibm_wide.hip); it cannot be called on the host" << std::endl;
+  std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi3 runs on the device (csrc/ibm.hip); it cannot be called on the host" << std::endl;
   std::exit(1);
 }
 inline void interpolationCoefficientsPhi4(plb::BlockLattice3D<T, DESCRIPTOR> &, HemoCellParticle &) {
-  std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi4 runs on the device (csrc/ibm_wide.hip); it cannot be called on the host" << std::endl;
+  std::cerr << "(HemoCell) (GPU backend) interpolationCoefficientsPhi4 runs on the device (csrc/ibm.hip); it cannot be called on the host" << std::endl;
   std::exit(1);
 }
 

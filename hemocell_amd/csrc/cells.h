@@ -1,5 +1,5 @@
 // Internal declarations shared by the translation units that work on membrane vertices
-// (cells.hip: storage and stepping, ibm.hip: spread / interpolate, ibm_wide.hip: the same with three- and four-point delta
+// (cells.hip: storage and stepping, ibm.hip: spread / interpolate with two-, three- and four-point delta
 // functions, mechanics.hip: membrane models,
 // exchange.hip: slab envelopes and statistics, repulsion.hip: vertex-vertex and boundary repulsion,
 // preinlet.hip: cell injection and the outflow sink, solidify.hip: binding sites and solidification).
@@ -102,8 +102,8 @@ struct hc_cells {
   DevBuf<int> d_solid; MappedBuf<int> h_solid;
   long solid_nodes_seen = 0;
   bool solidify_on() const { for (int t = 0; t < ntypes; t++) if (solid_on[t]) return true; return false; }
-  // width of the IBM delta function per type (hcp_type_set_ibm_kernel): HC_IBM_PHI2 launches the kernels of ibm.hip, HC_IBM_PHI3 and
-  // HC_IBM_PHI4 those of ibm_wide.hip.  hc::ibm_wide(L) knows the lattices that have such a type.
+  // width of the IBM delta function per type (hcp_type_set_ibm_kernel): the stencil policy the kernels of ibm.hip are launched
+  // with.  hc::ibm_wide(L) knows the lattices that have a type on HC_IBM_PHI3 or HC_IBM_PHI4.
   int ibm_kernel[8] = {HC_IBM_PHI2, HC_IBM_PHI2, HC_IBM_PHI2, HC_IBM_PHI2, HC_IBM_PHI2, HC_IBM_PHI2, HC_IBM_PHI2, HC_IBM_PHI2};
   bool ibm_wide_on() const { for (int t = 0; t < ntypes; t++) if (ibm_kernel[t] != HC_IBM_PHI2) return true; return false; }
   long n_deleted = 0;              // cells removed entirely (by a wall or by the caller; solidified cells are counted apart)
@@ -237,12 +237,6 @@ int upload_xyz(DevBuf<double> dst[3], long first, const double *src, long n);
 int download_xyz(double *dst, const DevBuf<double> src[3], long first, long n);
 int append_cells(hc_cells *C, int type, const long *cell_ids, const int *is_new, int n, long n_new);   // exchange.hip: n_new cells join the end of a type's region (is_new null: all n)
 int interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n, int which);   // ibm.hip: hcp_interpolate_cells through staging slot `which`
-// ibm_wide.hip: one type on the three- or four-point kernel (hc_cells::ibm_kernel), called by the loops of ibm.hip in place of
-// their own launches.  per_vertex: the per-vertex form (hc_debug_ibm_per_vertex).  slots: device list of n cell slots, or null
-// for every cell of the type.  wide_emit: the type's entries of the reproducible spread, W^3 per vertex from entry `ebase` on
-int wide_spread(hc_cells *C, int type, int force_limit, int per_vertex);
-int wide_interpolate(hc_cells *C, int type, const int *slots, int n, int per_vertex);
-int wide_emit(hc_cells *C, int type, const int *d_order, long ebase, int force_limit);
 inline int ibm_width(const hc_cells *C, int type) { return C->ibm_kernel[type]; }   // nodes per axis of the type's stencil
 
 }  // namespace hcc

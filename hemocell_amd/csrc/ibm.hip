@@ -1,56 +1,98 @@
-// Immersed-boundary coupling on the GPU: phi2 force spreading and velocity interpolation.
+// Immersed-boundary coupling on the GPU: force spreading and velocity interpolation with the two-point delta function of the
+// reference and the three-point (Roma) and four-point (Peskin) ones of hcp_type_set_ibm_kernel.  Every kernel is written once
+// over the stencil policy of a width (ibm_common.h: Phi<W>).
 //
 // Replaces (file:line in the HemoCell tree):
 //   core/immersedBoundaryMethod.h:62-138          interpolationCoefficientsPhi2 (cells.h: phi2_stencil)
 //   core/hemoCellParticleField.cpp:841-863        spreadParticleForce
 //   core/hemoCellParticleField.cpp:819-839        interpolateFluidVelocity
+//
+// Three forms: one thread per vertex (hc_debug_ibm_per_vertex), one workgroup per cell on an LDS tile (the default), and the
+// entries of the reproducible spread (hc_set_reproducible_spread).
 #include "ibm_common.h"
 #include <hipcub/hipcub.hpp>
 #include <cstdlib>
-#include <cstring>
 #include <numeric>
 
 namespace {
 
+// FORCE_LIMIT cap, core/hemoCellParticleField.cpp:848-852 (mutates sv.force: the caller stores a force that was scaled)
+__device__ __forceinline__ bool cap_force(double f[3], double f_limit) {
+  const double mag = sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
+  if (mag > f_limit) {
+    const double sc = f_limit / mag;
+    f[0] *= sc; f[1] *= sc; f[2] *= sc;
+    return true;
+  }
+  return false;
+}
+
+// force_repulsion + force (:857-859); the repulsion arrays are null while no repulsion is on
+__device__ __forceinline__ void driving_force(const double *rx, const double *ry, const double *rz, long i, const double f[3], double g[3]) {
+  g[0] = (rx ? rx[i] : 0.0) + f[0]; g[1] = (ry ? ry[i] : 0.0) + f[1]; g[2] = (rz ? rz[i] : 0.0) + f[2];
+}
+
+// external.data[d] += (force_repulsion[d] + force[d]) * weight  (:857-859) with global atomics; g = force_repulsion + force
+__device__ __forceinline__ void add_to_node(const LatView &v, double *F, long node, const double g[3], double w) {
+  v.dirty[node >> 4] = v.epoch;
+  double *Fn = F + 3 * node;
+  unsafeAtomicAdd(Fn, g[0] * w); unsafeAtomicAdd(Fn + 1, g[1] * w); unsafeAtomicAdd(Fn + 2, g[2] * w);
+}
+
+// one vertex with its own gathers: u = sum over the admitted nodes, in visiting order, of u(node) * weight
+template <class S, bool OPEN>
+__device__ __forceinline__ void interpolate_vertex(const LatView &v, const Pops<OPEN> &pv, double px, double py, double pz, double out[3]) {
+  typename S::Global s; typename S::Axes ax;
+  S::stencil(v, px, py, pz, s, ax);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  S::for_each(v, s, ax, [&](int, bool adm, long node, int lx, int ly, int lz, double w) __attribute__((always_inline)) {
+    if (!adm) return;
+    double u[3];
+    node_velocity<OPEN>(v, pv, lx, ly, lz, node, u);
+    a0 += (u[0] * w); a1 += (u[1] * w); a2 += (u[2] * w);
+  });
+  out[0] = a0; out[1] = a1; out[2] = a2;
+}
+
 // ----------------------------------------------------------------------------
-// spread
+// one thread per vertex
+template <class S>
 __global__ __launch_bounds__(256) void ibm_spread_kernel(LatView v, long n, const double *px, const double *py, const double *pz,
                                                          double *fx, double *fy, double *fz, const double *rx, const double *ry, const double *rz,
                                                          double *F, int limit_on, double f_limit, const int *vert_cell, const int *tag, const unsigned char *dead) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   if (dead[i] || tag[vert_cell[i]] == 1) return;   // removed particle / cell gone
-  double f0 = fx[i], f1 = fy[i], f2 = fz[i];
-  if (limit_on) {  // FORCE_LIMIT cap, core/hemoCellParticleField.cpp:848-852 (mutates sv.force)
-    const double mag = sqrt((f0 * f0 + f1 * f1) + f2 * f2);
-    if (mag > f_limit) {
-      const double sc = f_limit / mag;
-      f0 *= sc; f1 *= sc; f2 *= sc;
-      fx[i] = f0; fy[i] = f1; fz[i] = f2;
-    }
-  }
-  Stencil s;
-  phi2_stencil(v, px[i], py[i], pz[i], s);
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    if (s.node[k] < 0) continue;
-    v.dirty[s.node[k] >> 4] = v.epoch;
-    // external.data[d] += (force_repulsion[d] + force[d]) * weight  (:857-859)
-    double *Fn = F + 3 * s.node[k];
-    unsafeAtomicAdd(Fn, ((rx ? rx[i] : 0.0) + f0) * s.w[k]);
-    unsafeAtomicAdd(Fn + 1, ((ry ? ry[i] : 0.0) + f1) * s.w[k]);
-    unsafeAtomicAdd(Fn + 2, ((rz ? rz[i] : 0.0) + f2) * s.w[k]);
-  }
+  double f[3] = {fx[i], fy[i], fz[i]};
+  if (limit_on && cap_force(f, f_limit)) { fx[i] = f[0]; fy[i] = f[1]; fz[i] = f[2]; }
+  typename S::Global s; typename S::Axes ax;
+  S::stencil(v, px[i], py[i], pz[i], s, ax);
+  double g[3];
+  driving_force(rx, ry, rz, i, f, g);
+  S::for_each(v, s, ax, [&](int, bool adm, long node, int, int, int, double w) __attribute__((always_inline)) { if (adm) add_to_node(v, F, node, g, w); });
+}
+
+template <class S, bool OPEN>
+__global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, Pops<OPEN> pv, long n, const double *px, const double *py,
+                                                              const double *pz, double *vx, double *vy, double *vz, const int *vert_cell, const int *tag,
+                                                              const unsigned char *dead) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (dead[i] || tag[vert_cell[i]] == 1) return;
+  double u[3];
+  interpolate_vertex<S, OPEN>(v, pv, px[i], py[i], pz[i], u);
+  vx[i] = u[0]; vy[i] = u[1]; vz[i] = u[2];
 }
 
 // ----------------------------------------------------------------------------
 // reproducible spread (hc_set_reproducible_spread).  The reference adds particle by particle in storage order
 // (core/hemoCellParticleField.cpp:841-863), so a node's force is a sum in a fixed order and a run repeats bit for bit; the
-// atomic kernels above add in whatever order the hardware takes them.  Here every (particle, admitted stencil node) becomes an
-// entry keyed by its node, written in the canonical order (cell type, cell id, vertex id, stencil node); a stable radix
-// sort by node groups the entries of a node without disturbing that order, and ONE thread per node sums them in sequence and
-// adds the sum to the node.  The order does not depend on the storage slots of the cells, so every slab that holds a node
-// forms the bits the single domain forms.
+// atomic kernels add in whatever order the hardware takes them.  Here every (particle, stencil node) becomes an entry keyed by
+// its node, written in the canonical order (cell type, cell id, vertex id, stencil node): W^3 per vertex from entry ebase on,
+// a node that is not admitted with an invalid key.  A stable radix sort by node groups the entries of a node without
+// disturbing that order, and ONE thread per node sums them in sequence and adds the sum to the node.  The order does not
+// depend on the storage slots of the cells, so every slab that holds a node forms the bits the single domain forms.
+template <class S>
 __global__ __launch_bounds__(256) void spread_emit_kernel(LatView v, int nv, long n, const int *order, long ebase, const double *px, const double *py,
                                                           const double *pz, double *fx, double *fy, double *fz, const double *rx, const double *ry,
                                                           const double *rz, int limit_on, double f_limit, const int *tag, const unsigned char *dead,
@@ -59,26 +101,22 @@ __global__ __launch_bounds__(256) void spread_emit_kernel(LatView v, int nv, lon
   if (g >= n) return;
   const int cell = order[g / nv];
   const long i = (long)cell * nv + (g % nv);
-  const long e0 = (ebase + g) * 8;
-  const bool live = tag[cell] != 1 && !dead[i];
-  Stencil s;
-  double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+  const long e0 = ebase + g * (S::W * S::W * S::W);
+  const bool live = tag[cell] != 1 && !dead[i];   // removed particle / cell gone: its entries stay empty
+  typename S::Global s; typename S::Axes ax;
+  S::none(s);
+  double f[3] = {0.0, 0.0, 0.0};
   if (live) {
-    f0 = fx[i]; f1 = fy[i]; f2 = fz[i];
-    if (limit_on) {  // FORCE_LIMIT cap, core/hemoCellParticleField.cpp:848-852 (mutates sv.force)
-      const double mag = sqrt((f0 * f0 + f1 * f1) + f2 * f2);
-      if (mag > f_limit) { const double sc = f_limit / mag; f0 *= sc; f1 *= sc; f2 *= sc; fx[i] = f0; fy[i] = f1; fz[i] = f2; }
-    }
-    if (rx) { f0 = rx[i] + f0; f1 = ry[i] + f1; f2 = rz[i] + f2; }   // force_repulsion + force, :857-859
-    phi2_stencil(v, px[i], py[i], pz[i], s);
+    f[0] = fx[i]; f[1] = fy[i]; f[2] = fz[i];
+    if (limit_on && cap_force(f, f_limit)) { fx[i] = f[0]; fy[i] = f[1]; fz[i] = f[2]; }
+    if (rx) { f[0] = rx[i] + f[0]; f[1] = ry[i] + f[1]; f[2] = rz[i] + f[2]; }   // force_repulsion + force, :857-859
+    S::stencil(v, px[i], py[i], pz[i], s, ax);
   }
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const bool adm = live && s.node[k] >= 0;
-    keys[e0 + k] = adm ? (unsigned int)s.node[k] : 0xffffffffu;
+  S::for_each(v, s, ax, [&](int k, bool adm, long node, int, int, int, double w) __attribute__((always_inline)) {
+    keys[e0 + k] = adm ? (unsigned int)node : 0xffffffffu;
     vals[e0 + k] = (int)(e0 + k);
-    c0[e0 + k] = adm ? f0 * s.w[k] : 0.0; c1[e0 + k] = adm ? f1 * s.w[k] : 0.0; c2[e0 + k] = adm ? f2 * s.w[k] : 0.0;
-  }
+    c0[e0 + k] = adm ? f[0] * w : 0.0; c1[e0 + k] = adm ? f[1] * w : 0.0; c2[e0 + k] = adm ? f[2] * w : 0.0;
+  });
 }
 
 __global__ __launch_bounds__(256) void spread_gather_kernel(LatView v, long n, const unsigned int *keys, const int *vals, const double *c0, const double *c1,
@@ -111,47 +149,17 @@ __global__ __launch_bounds__(256) void face_velocity_kernel(LatView v, Pops<OPEN
   out[k] = u[0]; out[v.ny_nz + k] = u[1]; out[2L * v.ny_nz + k] = u[2];
 }
 
-template <bool OPEN = false>
-__global__ __launch_bounds__(256) void ibm_interpolate_kernel(LatView v, Pops<OPEN> pv, long n, const double *px, const double *py,
-                                                              const double *pz, double *vx, double *vy, double *vz, const int *vert_cell, const int *tag,
-                                                              const unsigned char *dead) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (dead[i] || tag[vert_cell[i]] == 1) return;
-  Stencil s;
-  phi2_stencil(v, px[i], py[i], pz[i], s);
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    if (s.node[k] < 0) continue;
-    double u[3];
-    node_velocity<OPEN>(v, pv, s.lx[k], s.ly[k], s.lz[k], s.node[k], u);
-    a0 += (u[0] * s.w[k]); a1 += (u[1] * s.w[k]); a2 += (u[2] * s.w[k]);
-  }
-  vx[i] = a0; vy[i] = a1; vz[i] = a2;
-}
-
 
 // ----------------------------------------------------------------------------
 // LDS-tiled IBM kernels: one workgroup per cell.
 //
-// All 8-node stencils of a cell fall into the cell's bounding box (+1); the nodes the cell touches are compacted
-// into a list (compact_nodes).  Spread: the workgroup accumulates the three force components per listed node in
-// LDS (ds_add_f64), then flushes them to HBM with one fp64 atomic per (node, component) -- several times fewer,
-// better shaped global atomics than one per (vertex, node, component).  Interpolate: the node velocity
-// (19-population gather + moments) is evaluated once per listed node into LDS, and every vertex then blends its
-// 8 values from LDS.
-constexpr int TILE_CAP = 5832;       // nodes per tile: 18 x 18 x 18, any orientation of a 642-vertex RBC; three workgroups per CU fit the 160 KB LDS
-constexpr int NODE_CAP = 1536;       // distinct nodes of one cell for the interpolation (an RBC touches ~1300)
-
-
-__device__ __forceinline__ int stencil_base(const LatView &v, double px, double py, double pz, int b[3]) {
-  const double p[3] = {px, py, pz};
-#pragma unroll
-  for (int a = 0; a < 3; a++) { const long c = nearest_node(p[a]); b[a] = (int)c + ((p[a] < (double)c) ? -1 : 0); }
-  return 0;
-}
-
+// All stencils of a cell fall into the cell's bounding box; the nodes the cell touches are compacted into a list
+// (compact_nodes).  Spread: the workgroup accumulates the three force components per listed node in LDS (ds_add_f64), then
+// flushes them to HBM with one fp64 atomic per (node, component) -- several times fewer, better shaped global atomics than one
+// per (vertex, node, component).  Interpolate: the node velocity (19-population gather + moments) is evaluated once per listed
+// node into LDS, and every vertex then blends its W^3 values from LDS.
+// LDS of both (ibm_common.h: the caps): 16-bit slots, and the node list reuses the mask tile (the mask is only read while the
+// stencils are formed).
 
 // Workgroups are handed to the 8 XCDs round robin, and every XCD has its own L2.  Cells are stored in placement order,
 // neighbours in space mostly next to each other; giving each XCD a contiguous range of cells lets neighbouring cells,
@@ -164,101 +172,12 @@ __device__ __forceinline__ int xcd_contiguous(int b, int n) {
   return (b & 7) * per + (b >> 3);
 }
 
-// compact per-vertex stencil kept in registers across the passes of the cell kernels
-struct VStencil { double w[8]; int base; unsigned adm; };   // base = tile index of the lowest corner; adm = admitted-node bits
-
-constexpr int NVPT = 3;        // vertices per thread held in registers (642 vertices / 256 threads)
-// Four waves per workgroup (MAXW, ibm_common.h).  Eight waves per cell (512 threads, two vertices each) were tried for both kernels: the spread gains 3.5 % at 10 % hematocrit
-// and nothing at 25 % (and loses once its loads are reordered), the interpolation loses 9-15 % (184 VGPRs: one cell per CU);
-// capping the interpolation at 168 / 128 VGPRs for three cells per CU spills and loses 15 %.  Both kernels wait 80 % of their
-// wave cycles (rocprofv3 SQ_WAIT_ANY + SQ_WAIT_INST_ANY) and respond to neither more waves nor shorter workgroups.
-
-// -DHC_IBM_PHASE_TIMES (scratch builds only): thread 0 of every workgroup adds the shader cycles between consecutive stamps to
-// g_phase[k]; hc_debug_phase_times() reads and clears them
-#ifdef HC_IBM_PHASE_TIMES
-__device__ unsigned long long g_phase[32];
-#define PH_PARAM , long long &ph_last
-#define PH_ARG , ph_last
-#define PH_INIT long long ph_last = clock64();
-#define STAMP(k) do { if (threadIdx.x == 0) { const long long ph_now = clock64(); atomicAdd(&g_phase[k], (unsigned long long)(ph_now - ph_last)); ph_last = ph_now; } } while (0)
-#else
-#define PH_PARAM
-#define PH_ARG
-#define PH_INIT
-#define STAMP(k) do {} while (0)
-#endif
-
-
-// local (wrapped) origin and decode reciprocals; false when the tile cannot be used
-__device__ __forceinline__ bool tile_finish(const LatView &v, Tile &t) {
-  if (t.vol > TILE_CAP) return false;
-  if ((v.wrap_x && t.e[0] > v.nx) || (v.per_y && t.e[1] > v.ny) || (v.per_z && t.e[2] > v.nz)) return false;
-  t.ow[0] = v.wrap_x ? (int)pmod((long)t.o[0] - v.x0, v.nx) : t.o[0] - v.x0;
-  t.ow[1] = v.per_y ? (int)pmod(t.o[1], v.ny) : t.o[1];
-  t.ow[2] = v.per_z ? (int)pmod(t.o[2], v.nz) : t.o[2];
-  t.r1 = 1.0f / (float)t.e[1]; t.r2 = 1.0f / (float)t.e[2];
-  return true;
-}
-
-
-// interpolationCoefficientsPhi2 against the LDS copy of the mask; same arithmetic and visiting order as phi2_stencil
-__device__ __forceinline__ void tile_stencil(const Tile &t, const unsigned char *mt, double px, double py, double pz, const int b[3], VStencil &o) {
-  const int sy = t.e[2], sx = t.e[1] * t.e[2];
-  o.base = ((b[0] - t.o[0]) * t.e[1] + (b[1] - t.o[1])) * t.e[2] + (b[2] - t.o[2]);
-  o.adm = 0;
-  double total = 0.0;
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int k = 0; k < 2; k++) {
-        const int idx = i * 4 + j * 2 + k;
-        const double weight = phi2(px - (double)(b[0] + i)) * phi2(py - (double)(b[1] + j)) * phi2(pz - (double)(b[2] + k));
-        const bool adm = (weight != 0.0) && (!mt || mt[o.base + i * sx + j * sy + k] == 0);   // mt == nullptr: no wall anywhere near this cell
-        if (adm) { total += weight; o.adm |= 1u << idx; }
-        o.w[idx] = adm ? weight : 0.0;
-      }
-  const double coeff = 1.0 / total;
-#pragma unroll
-  for (int idx = 0; idx < 8; idx++) o.w[idx] *= coeff;
-}
-
-// Is every node of the tile an ordinary fluid node inside the domain?  Then interpolationCoefficientsPhi2 admits every node
-// with a non-zero weight and the mask need not be looked at (most cells of a vessel are nowhere near its wall).  Answered
-// from one byte per 8 x 8 x 8 brick of the padded lattice (hc_lattice::wallbrick: set when the brick holds a non-fluid node or
-// touches a face the stencils cannot cross); a tile covers at most 4 x 4 x 4 bricks, one per lane of wave 0.
-__device__ __forceinline__ bool tile_is_clear(const LatView &v, const Tile &t, int *s_near) {
-  const int n[3] = {v.nx, v.ny, v.nz};
-  bool inside = v.wallbrick != nullptr;
-  int b0[3], nb[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const int lo = a == 0 ? t.ow[0] + HALO : t.ow[a], hi = lo + t.e[a] - 1, lim = a == 0 ? v.nx + 2 * HALO : n[a];   // x in padded planes
-    inside = inside && lo >= 0 && hi < lim && (a != 0 || !v.wrap_x || (t.ow[0] >= 0 && t.ow[0] + t.e[0] <= v.nx));
-    b0[a] = lo >> 3; nb[a] = (hi >> 3) - b0[a] + 1;
-  }
-  if (!inside) return false;   // uniform: the tile wraps around a periodic face or leaves the addressable range
-  if (nb[0] * nb[1] * nb[2] > 64) return false;   // uniform: a thin, long tile (5832 nodes can span more bricks than one wave looks at) takes the mask path
-  if (threadIdx.x < 64) {
-    const int l = threadIdx.x;
-    bool near = false;
-    if (l < nb[0] * nb[1] * nb[2]) {
-      const int bz = l % nb[2], by = (l / nb[2]) % nb[1], bx = l / (nb[2] * nb[1]);
-      near = v.wallbrick[((long)(b0[0] + bx) * v.nby + (b0[1] + by)) * v.nbz + (b0[2] + bz)] != 0;
-    }
-    const unsigned long long any = __ballot(near);
-    if (l == 0) *s_near = any != 0ull;
-  }
-  __syncthreads();
-  return *s_near == 0;
-}
-
-// shared prologue of the two cell kernels: positions -> registers, tile, mask tile (only near walls), stencils.
-// returns false (uniformly) when the cell does not fit the tile and the caller must take the fallback path
+// shared prologue of the two cell kernels: positions -> registers, tile, mask tile (two points: only near walls), admission.
+// returns false (uniformly) when the cell does not fit the tile and the caller must take the per-vertex path
 // dead: removed particles of an INCOMPLETE cell (null for a complete one); they take no part in anything
+template <class S>
 __device__ __forceinline__ bool cell_prologue(const LatView &v, int nv, long base, const double *px, const double *py, const double *pz,
-                                              const unsigned char *dead, int *s_red, int *s_near, unsigned char *mt, Tile &t, VStencil vs[NVPT] PH_PARAM) {
+                                              const unsigned char *dead, int *s_red, unsigned char *mt, Tile &t, typename S::Kept vs[NVPT]) {
   const int tid = threadIdx.x, nth = blockDim.x;
   double p[NVPT][3]; int b[NVPT][3]; bool live[NVPT];
   int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-0x7fffffff, -0x7fffffff, -0x7fffffff};
@@ -268,99 +187,79 @@ __device__ __forceinline__ bool cell_prologue(const LatView &v, int nv, long bas
     live[j] = i < nv && !(dead && dead[base + i]);
     if (live[j]) {
       p[j][0] = px[base + i]; p[j][1] = py[base + i]; p[j][2] = pz[base + i];
-      stencil_base(v, p[j][0], p[j][1], p[j][2], b[j]);
+      S::rows(p[j], b[j], vs[j]);
 #pragma unroll
-      for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], b[j][a]); hi[a] = max(hi[a], b[j][a] + 1); }
+      for (int a = 0; a < 3; a++) { lo[a] = min(lo[a], b[j][a]); hi[a] = max(hi[a], b[j][a] + S::W - 1); }
     }
   }
   block_bbox(lo, hi, s_red, t);
-  STAMP(1);
-  if (!tile_finish(v, t) || nv > NVPT * nth) return false;
-  const bool clear = tile_is_clear(v, t, s_near);   // uniform
-  STAMP(2);
+  if (!tile_finish(v, t, S::TILE) || nv > NVPT * nth) return false;
+  bool clear = false;
+  if constexpr (S::WALL_BRICKS) clear = tile_is_clear(v, t);   // uniform
   if (!clear) {
 #pragma unroll 4
     for (int i = tid; i < t.vol; i += nth) mt[i] = tile_mask(v, t, i);
     __syncthreads();
   }
-  STAMP(3);
 #pragma unroll
   for (int j = 0; j < NVPT; j++) {
     vs[j].adm = 0; vs[j].base = 0;
-    if (live[j]) tile_stencil(t, clear ? nullptr : mt, p[j][0], p[j][1], p[j][2], b[j], vs[j]);
+    if (live[j]) S::admit(t, clear ? nullptr : mt, p[j], b[j], vs[j]);
   }
-  STAMP(4);
   return true;
 }
 
-// Compacts the nodes the cell's stencils admit: slot[tile index] = rank of the node, list[rank] = tile index, in tile order within
-// each wave's 256 tile entries (runs along z stay runs).  One LDS atomic per wave, ranks within the wave from its ballot.  Returns
-// the node count (uniform); a count above NODE_CAP means the list is incomplete and the caller takes its fallback path.
-constexpr unsigned short SLOT_FREE = 0xFFFF, SLOT_MARK = 0xFFFE;
-__device__ __forceinline__ int compact_nodes(const Tile &t, const VStencil vs[NVPT], unsigned short *slot, unsigned short *list, int *s_count) {
+// the FORCE_LIMIT cap of a cell's vertices: those a thread holds in registers (f), else strided over the stored forces
+__device__ __forceinline__ void cap_cell_forces(int nv, long base, double *fx, double *fy, double *fz, const unsigned char *dead, double f_limit,
+                                                bool in_regs, double f[NVPT][3]) {
   const int tid = threadIdx.x, nth = blockDim.x;
-  const int sy = t.e[2], sx = t.e[1] * t.e[2];
-  for (int i = tid; i < t.vol; i += nth) slot[i] = SLOT_FREE;
-  if (tid == 0) *s_count = 0;
-  __syncthreads();   // also: every thread is done reading the mask tile, list may overwrite it
+  if (in_regs) {
 #pragma unroll
-  for (int j = 0; j < NVPT; j++)   // mark the admitted nodes
-#pragma unroll
-    for (int k = 0; k < 8; k++) if (vs[j].adm & (1u << k)) slot[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)] = SLOT_MARK;
-  __syncthreads();
-  for (int i0 = 0; i0 < t.vol; i0 += nth) {
-    const int i = i0 + tid;
-    const bool marked = i < t.vol && slot[i] == SLOT_MARK;
-    const unsigned long long b = __ballot(marked);
-    int first = 0;
-    if ((tid & 63) == 0 && b) first = atomicAdd(s_count, (int)__popcll(b));
-    first = __shfl(first, 0);
-    if (marked) {
-      const int n = first + (int)__popcll(b & ((1ull << (tid & 63)) - 1ull));
-      if (n < NODE_CAP) { slot[i] = (unsigned short)n; list[n] = (unsigned short)i; }
+    for (int j = 0; j < NVPT; j++) {
+      const int i = tid + j * nth;
+      if (i < nv && !(dead && dead[base + i]) && cap_force(f[j], f_limit)) {   // a removed particle is not in the list: its force stays
+        fx[base + i] = f[j][0]; fy[base + i] = f[j][1]; fz[base + i] = f[j][2];
+      }
+    }
+  } else {
+    for (int i = tid; i < nv; i += nth) {
+      if (dead && dead[base + i]) continue;
+      double g[3] = {fx[base + i], fy[base + i], fz[base + i]};
+      if (cap_force(g, f_limit)) { fx[base + i] = g[0]; fy[base + i] = g[1]; fz[base + i] = g[2]; }
     }
   }
-  __syncthreads();
-  return *s_count;
 }
 
-// per-vertex spread with direct global atomics: cells larger than the tile or touching more than NODE_CAP nodes
+// per-vertex spread with direct global atomics: cells larger than the tile or touching more than S::NODES nodes
+template <class S>
 __device__ void spread_direct(const LatView &v, int nv, long base, const double *px, const double *py, const double *pz, const double *fx,
                               const double *fy, const double *fz, const double *rx, const double *ry, const double *rz, double *F,
                               const unsigned char *dead) {
   for (int i = threadIdx.x; i < nv; i += blockDim.x) {
     if (dead && dead[base + i]) continue;
-    Stencil s;
-    phi2_stencil(v, px[base + i], py[base + i], pz[base + i], s);
-    const double f0 = (rx ? rx[base + i] : 0.0) + fx[base + i], f1 = (ry ? ry[base + i] : 0.0) + fy[base + i], f2 = (rz ? rz[base + i] : 0.0) + fz[base + i];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      if (s.node[k] < 0) continue;
-      v.dirty[s.node[k] >> 4] = v.epoch;
-      double *Fn = F + 3 * s.node[k];
-      unsafeAtomicAdd(Fn, f0 * s.w[k]);
-      unsafeAtomicAdd(Fn + 1, f1 * s.w[k]);
-      unsafeAtomicAdd(Fn + 2, f2 * s.w[k]);
-    }
+    typename S::Global s; typename S::Axes ax;
+    S::stencil(v, px[base + i], py[base + i], pz[base + i], s, ax);
+    const double f[3] = {fx[base + i], fy[base + i], fz[base + i]};
+    double g[3];
+    driving_force(rx, ry, rz, base + i, f, g);
+    S::for_each(v, s, ax, [&](int, bool adm, long node, int, int, int, double w) __attribute__((always_inline)) { if (adm) add_to_node(v, F, node, g, w); });
   }
 }
 
+template <class S>
 __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv, const double *px, const double *py, const double *pz,
                                                               double *fx, double *fy, double *fz, const double *rx, const double *ry, const double *rz,
                                                               double *F, int limit_on, double f_limit, int xcd_ranges, const int *tag, const unsigned char *vdead) {
-  // 54 KB in all, so that three workgroups share a CU: 16-bit slots, the node list reuses the mask tile, and the three force
-  // components of a touched node side by side (acc[3 * rank + component], the layout of F)
-  __shared__ unsigned short slot[TILE_CAP];
-  __shared__ __attribute__((aligned(16))) unsigned char raw[TILE_CAP > 2 * NODE_CAP ? TILE_CAP : 2 * NODE_CAP];
+  // the three force components of a touched node side by side (acc[3 * rank + component], the layout of F)
+  __shared__ unsigned short slot[S::TILE];
+  __shared__ __attribute__((aligned(16))) unsigned char raw[S::TILE > 2 * S::NODES ? S::TILE : 2 * S::NODES];
   unsigned char *mt = raw; unsigned short *list = reinterpret_cast<unsigned short *>(raw);
-  __shared__ double acc[3 * NODE_CAP];
-  __shared__ int s_red[6 * MAXW], s_count, s_near;
+  __shared__ double acc[3 * S::NODES];
+  __shared__ int s_red[6 * MAXW], s_count;
   const int tid = threadIdx.x, nth = blockDim.x;
-  PH_INIT
   const int cell = xcd_ranges ? xcd_contiguous((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
   const int state = tag[cell];
   if (state == 1) return;                                        // the cell is gone
-  STAMP(0);
   const unsigned char *dead = state == 2 ? vdead : nullptr;      // incomplete: skip its removed particles
   const long base = (long)cell * nv;
   const bool in_regs = nv <= NVPT * nth;
@@ -375,34 +274,14 @@ __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv,
       if (i < nv) { f[j][0] = fx[base + i]; f[j][1] = fy[base + i]; f[j][2] = fz[base + i]; }
     }
   }
-  Tile t; VStencil vs[NVPT];
-  bool tiled = cell_prologue(v, nv, base, px, py, pz, dead, s_red, &s_near, mt, t, vs PH_ARG);
-  // FORCE_LIMIT cap, core/hemoCellParticleField.cpp:848-852 (mutates sv.force)
-  if (limit_on) {
-    if (in_regs) {
-#pragma unroll
-      for (int j = 0; j < NVPT; j++) {
-        const int i = tid + j * nth;
-        if (i < nv && !(dead && dead[base + i])) {   // a removed particle is not in the list: its force stays
-          const double mag = sqrt((f[j][0] * f[j][0] + f[j][1] * f[j][1]) + f[j][2] * f[j][2]);
-          if (mag > f_limit) { const double sc = f_limit / mag; f[j][0] *= sc; f[j][1] *= sc; f[j][2] *= sc; fx[base + i] = f[j][0]; fy[base + i] = f[j][1]; fz[base + i] = f[j][2]; }
-        }
-      }
-    } else {
-      for (int i = tid; i < nv; i += nth) {
-        if (dead && dead[base + i]) continue;
-        const double f0 = fx[base + i], f1 = fy[base + i], f2 = fz[base + i];
-        const double mag = sqrt((f0 * f0 + f1 * f1) + f2 * f2);
-        if (mag > f_limit) { const double sc = f_limit / mag; fx[base + i] = f0 * sc; fy[base + i] = f1 * sc; fz[base + i] = f2 * sc; }
-      }
-    }
-  }
+  Tile t; typename S::Kept vs[NVPT];
+  const bool tiled = cell_prologue<S>(v, nv, base, px, py, pz, dead, s_red, mt, t, vs);
+  if (limit_on) cap_cell_forces(nv, base, fx, fy, fz, dead, f_limit, in_regs, f);
   // The touched nodes are compacted and all three components accumulated per node in LDS (ds_add_f64), then flushed with one
   // fp64 atomic per (node, component), consecutive lanes on consecutive addresses: a z-run of a membrane across a row leaves as
   // one 48-96 byte segment of F instead of three 16-32 byte segments in three component planes.
-  const int n = tiled ? compact_nodes(t, vs, slot, list, &s_count) : 0;
-  STAMP(5);
-  if (!tiled || n > NODE_CAP) { spread_direct(v, nv, base, px, py, pz, fx, fy, fz, rx, ry, rz, F, dead); return; }   // uniform
+  const int n = tiled ? compact_nodes<S>(t, vs, slot, list, &s_count) : 0;
+  if (!tiled || n > S::NODES) { spread_direct<S>(v, nv, base, px, py, pz, fx, fy, fz, rx, ry, rz, F, dead); return; }   // uniform
   const int sy = t.e[2], sx = t.e[1] * t.e[2];
   for (int k = tid; k < 3 * n; k += nth) acc[k] = 0.0;
   __syncthreads();
@@ -410,17 +289,14 @@ __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv,
   for (int j = 0; j < NVPT; j++) {
     const int i = tid + j * nth;
     if (i >= nv || !vs[j].adm) continue;
-    double fv[3];   // force_repulsion + force, :857-859
-    fv[0] = (rx ? rx[base + i] : 0.0) + f[j][0]; fv[1] = (ry ? ry[base + i] : 0.0) + f[j][1]; fv[2] = (rz ? rz[base + i] : 0.0) + f[j][2];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      if (!(vs[j].adm & (1u << k))) continue;
-      double *a = &acc[3 * slot[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)]];
-      atomicAdd(a, fv[0] * vs[j].w[k]); atomicAdd(a + 1, fv[1] * vs[j].w[k]); atomicAdd(a + 2, fv[2] * vs[j].w[k]);
-    }
+    double g[3];
+    driving_force(rx, ry, rz, base + i, f[j], g);
+    S::for_each(vs[j], sx, sy, [&](int at, double w) __attribute__((always_inline)) {
+      double *a = &acc[3 * slot[at]];
+      atomicAdd(a, g[0] * w); atomicAdd(a + 1, g[1] * w); atomicAdd(a + 2, g[2] * w);
+    });
   }
   __syncthreads();
-  STAMP(6);
   for (int k = tid; k < 3 * n; k += nth) {
     const double val = acc[k];
     if (val != 0.0) {
@@ -429,35 +305,28 @@ __global__ __launch_bounds__(256) void ibm_spread_cell_kernel(LatView v, int nv,
       unsafeAtomicAdd(&F[3 * node + (k - 3 * q)], val);
     }
   }
-  STAMP(7);
 }
 
-template <bool OPEN = false>
+template <class S, bool OPEN>
 __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Pops<OPEN> pv, int nv, const double *px, const double *py,
                                                                    const double *pz, double *vx, double *vy, double *vz, const int *slots, int xcd_ranges,
                                                                    const int *tag, const unsigned char *vdead) {
-  // 54 KB in all, so that three workgroups share a CU: 16-bit slots, and the node list reuses the mask tile
-  // (the mask is only read while the stencils are formed)
-  __shared__ unsigned short slot[TILE_CAP];
-  __shared__ __attribute__((aligned(16))) unsigned char raw[TILE_CAP > 2 * NODE_CAP ? TILE_CAP : 2 * NODE_CAP];
+  __shared__ unsigned short slot[S::TILE];
+  __shared__ __attribute__((aligned(16))) unsigned char raw[S::TILE > 2 * S::NODES ? S::TILE : 2 * S::NODES];
   unsigned char *mt = raw; unsigned short *list = reinterpret_cast<unsigned short *>(raw);
-  __shared__ double ux[NODE_CAP], uy[NODE_CAP], uz[NODE_CAP];
-  __shared__ int s_red[6 * MAXW], s_count, s_near;
+  __shared__ double ux[S::NODES], uy[S::NODES], uz[S::NODES];
+  __shared__ int s_red[6 * MAXW], s_count;
   const int tid = threadIdx.x, nth = blockDim.x;
   const int cell = slots ? slots[blockIdx.x] : (xcd_ranges ? xcd_contiguous((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x);   // slots: only the listed cells of the type
   const int state = tag[cell];
   if (state == 1) return;
   const unsigned char *dead = state == 2 ? vdead : nullptr;
   const long base = (long)cell * nv;
-  Tile t; VStencil vs[NVPT];
-  PH_INIT
-  bool tiled = cell_prologue(v, nv, base, px, py, pz, dead, s_red, &s_near, mt, t, vs PH_ARG);
-  const int sy = t.e[2], sx = t.e[1] * t.e[2];
+  Tile t; typename S::Kept vs[NVPT];
+  bool tiled = cell_prologue<S>(v, nv, base, px, py, pz, dead, s_red, mt, t, vs);
+  if (tiled && compact_nodes<S>(t, vs, slot, list, &s_count) > S::NODES) tiled = false;   // uniform: s_count is shared
   if (tiled) {
-    if (compact_nodes(t, vs, slot, list, &s_count) > NODE_CAP) tiled = false;   // uniform: s_count is shared
-    STAMP(12);
-  }
-  if (tiled) {
+    const int sy = t.e[2], sx = t.e[1] * t.e[2];
     const int n = s_count;
     for (int k = tid; k < n; k += nth) {       // node velocity once per node
       int lx, ly, lz;
@@ -467,39 +336,43 @@ __global__ __launch_bounds__(256) void ibm_interpolate_cell_kernel(LatView v, Po
       ux[k] = u[0]; uy[k] = u[1]; uz[k] = u[2];
     }
     __syncthreads();
-    STAMP(13);
 #pragma unroll
     for (int j = 0; j < NVPT; j++) {
       const int i = tid + j * nth;
       if (i >= nv || (dead && dead[base + i])) continue;   // a removed particle keeps its velocity, as in the per-vertex forms
       double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        if (!(vs[j].adm & (1u << k))) continue;
-        const int q = slot[vs[j].base + (k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)];
-        a0 += (ux[q] * vs[j].w[k]); a1 += (uy[q] * vs[j].w[k]); a2 += (uz[q] * vs[j].w[k]);
-      }
+      S::for_each(vs[j], sx, sy, [&](int at, double w) __attribute__((always_inline)) {
+        const int q = slot[at];
+        a0 += (ux[q] * w); a1 += (uy[q] * w); a2 += (uz[q] * w);
+      });
       vx[base + i] = a0; vy[base + i] = a1; vz[base + i] = a2;
     }
-    STAMP(14);
     return;
   }
   for (int i = tid; i < nv; i += nth) {   // fallback: per-vertex gathers
     if (dead && dead[base + i]) continue;
-    Stencil s;
-    phi2_stencil(v, px[base + i], py[base + i], pz[base + i], s);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      if (s.node[k] < 0) continue;
-      double u[3];
-      node_velocity<OPEN>(v, pv, s.lx[k], s.ly[k], s.lz[k], s.node[k], u);
-      a0 += (u[0] * s.w[k]); a1 += (u[1] * s.w[k]); a2 += (u[2] * s.w[k]);
-    }
-    vx[base + i] = a0; vy[base + i] = a1; vz[base + i] = a2;
+    double u[3];
+    interpolate_vertex<S, OPEN>(v, pv, px[base + i], py[base + i], pz[base + i], u);
+    vx[base + i] = u[0]; vy[base + i] = u[1]; vz[base + i] = u[2];
   }
 }
 
+// The policy of a stencil width (ibm_width): f(Phi<W>{}), in the style of hc::launch_open
+template <class F>
+void with_width(int w, F f) {
+  if (w == HC_IBM_PHI3) f(Phi<3>{});
+  else if (w == HC_IBM_PHI4) f(Phi<4>{});
+  else f(Phi<2>{});
+}
+// hc::launch_open for a kernel K<S, OPEN>: the OPEN instantiations exist for two points only (a three- or four-point kernel is
+// refused on a lattice with open boundaries, and its four-point interpolation has no registers left for one)
+template <class S, class Launch>
+void launch_pops(const hc_lattice *L, const PopView &pv, Launch launch) {
+  if constexpr (S::W == 2) hc::launch_open(L, pv, launch);
+  else launch(std::false_type{}, pv);
+}
+// threads of a per-cell workgroup: NVPT vertices per thread cover the largest mesh
+dim3 cell_block(int nv) { return dim3(nv > 128 ? 256 : 128); }
 
 }  // namespace
 
@@ -515,8 +388,7 @@ extern "C" int hc_set_reproducible_spread(int on) { g_reproducible = on ? 1 : 0;
 // the gather form of the spread: entries -> stable sort by node -> one sequential sum per node
 static int spread_reproducible(hc_cells *C, int force_limit) {
   const LatView v = make_view(C->L);
-  // entries: 8 per vertex of a type on two points, 27 or 64 on the wide kernels (ibm_wide.hip).  A type's entries start on a
-  // multiple of 8, the unit spread_emit_kernel counts its base in; entries in between keep an invalid key
+  // entries: W^3 per vertex of a type.  A type's entries start on a multiple of 8; entries in between keep an invalid key
   long n_e = 0, first_e[8];
   for (int t = 0; t < C->ntypes; t++) {
     const long w = ibm_width(C, t);
@@ -554,12 +426,12 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
     const int nv = C->types[t]->host.nv;
     const long n = C->ncells[t] * nv;
     if (n == 0) continue;
-    if (ibm_width(C, t) != HC_IBM_PHI2) { if ((rc = wide_emit(C, t, d_order + obase[(size_t)t], first_e[t], force_limit)) != HC_OK) return rc; continue; }
-    const long ebase = first_e[t] / 8;
     const TypeArrays a = vert_arrays(C, t);   // r is set exactly when rep_on(), see vert_arrays: hcp_spread has synchronised to the device
-    hipLaunchKernelGGL(spread_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, nv, n, (const int *)(d_order + obase[(size_t)t]), ebase,
-                       a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], force_limit, C->P.f_limit, a.tag, a.dead, C->det_keys[0], C->det_vals[0],
-                       C->det_val[0], C->det_val[1], C->det_val[2]);
+    with_width(ibm_width(C, t), [&](auto s) {
+      hipLaunchKernelGGL(spread_emit_kernel<decltype(s)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, nv, n,
+                         (const int *)(d_order + obase[(size_t)t]), first_e[t], a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], force_limit,
+                         C->P.f_limit, a.tag, a.dead, C->det_keys[0], C->det_vals[0], C->det_val[0], C->det_val[1], C->det_val[2]);
+    });
     HC_HIP(hipGetLastError());
   }
   // only the bits a node index needs: 2^bits > npad, so the low bits of an invalid key (all ones) still sort behind every node
@@ -572,16 +444,33 @@ static int spread_reproducible(hc_cells *C, int force_limit) {
   HC_HIP(hipGetLastError());
   return HC_OK;
 }
-#ifdef HC_IBM_PHASE_TIMES
-extern "C" int hc_debug_phase_times(double *out) {
-  unsigned long long h[32];
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase), sizeof(h)) != hipSuccess) return HC_ERR_HIP;
-  for (int k = 0; k < 32; k++) out[k] = (double)h[k];
-  std::memset(h, 0, sizeof(h));
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), h, sizeof(h)) != hipSuccess) return HC_ERR_HIP;
+
+// the interpolation of one type.  d_slots: device list of n_slots cell slots, or null for every cell of the type (then
+// hc_debug_ibm_per_vertex picks the per-vertex form)
+static int interpolate_type(hc_cells *C, int t, const int *d_slots, int n_slots) {
+  const hc_lattice *L = C->L;
+  const int w = ibm_width(C, t);
+  HC_REQUIRE(w == HC_IBM_PHI2 || (L->ob_n == 0 && L->n_slabs == 1), "hcp_interpolate: a three- or four-point IBM kernel on a lattice with open boundaries or slabs");   // refused at set-up, both ways
+  const LatView v = make_view(L);
+  const PopView pv = make_pops(L);
+  const int nv = C->types[t]->host.nv;
+  const long n = C->ncells[t] * nv;
+  const TypeArrays a = vert_arrays(C, t);
+  with_width(w, [&](auto s) {
+    using S = decltype(s);
+    launch_pops<S>(L, pv, [&](auto open, const auto &pops) {
+      constexpr bool OPEN = decltype(open)::value;
+      if (g_ibm_per_vertex && !d_slots)
+        hipLaunchKernelGGL((ibm_interpolate_kernel<S, OPEN>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, pops, n, a.p[0], a.p[1], a.p[2],
+                           a.v[0], a.v[1], a.v[2], a.vert_cell, a.tag_all, a.dead);
+      else   // XCD-contiguous cell order: the full launch on two points (untried on three and four)
+        hipLaunchKernelGGL((ibm_interpolate_cell_kernel<S, OPEN>), dim3(d_slots ? (unsigned)n_slots : (unsigned)C->ncells[t]), cell_block(nv), 0, hc::stream(), v, pops,
+                           nv, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2], d_slots, !d_slots && S::W == 2, a.tag, a.dead);
+    });
+  });
+  HC_HIP(hipGetLastError());
   return HC_OK;
 }
-#endif
 
 extern "C" {
 
@@ -592,18 +481,21 @@ int hcp_spread(hc_cells *C, int force_limit) {
   hc::ProfScope prof(hc::PK_SPREAD);
   if (reproducible()) return spread_reproducible(C, force_limit);
   const LatView v = make_view(C->L);
+  double *F = C->L->force[C->L->fcur];
   for (int t = 0; t < C->ntypes; t++) {
-    const long n = C->ncells[t] * C->types[t]->host.nv;
-    if (n == 0) continue;
     const int nv = C->types[t]->host.nv;
-    if (ibm_width(C, t) != HC_IBM_PHI2) { if ((rc = wide_spread(C, t, force_limit, g_ibm_per_vertex)) != HC_OK) return rc; continue; }
+    const long n = C->ncells[t] * nv;
+    if (n == 0) continue;
     const TypeArrays a = vert_arrays(C, t);   // r is set exactly when rep_on(), see vert_arrays: the sync_to_device above has run
-    if (g_ibm_per_vertex)
-      hipLaunchKernelGGL(ibm_spread_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2],
-                         a.r[0], a.r[1], a.r[2], C->L->force[C->L->fcur], force_limit, C->P.f_limit, a.vert_cell, a.tag_all, a.dead);
-    else
-      hipLaunchKernelGGL(ibm_spread_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), 0, hc::stream(), v, nv, a.p[0], a.p[1], a.p[2],
-                         a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], C->L->force[C->L->fcur], force_limit, C->P.f_limit, 1, a.tag, a.dead);
+    with_width(ibm_width(C, t), [&](auto s) {
+      using S = decltype(s);
+      if (g_ibm_per_vertex)
+        hipLaunchKernelGGL(ibm_spread_kernel<S>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hc::stream(), v, n, a.p[0], a.p[1], a.p[2], a.f[0], a.f[1], a.f[2],
+                           a.r[0], a.r[1], a.r[2], F, force_limit, C->P.f_limit, a.vert_cell, a.tag_all, a.dead);
+      else
+        hipLaunchKernelGGL(ibm_spread_cell_kernel<S>, dim3((unsigned)C->ncells[t]), cell_block(nv), 0, hc::stream(), v, nv, a.p[0], a.p[1], a.p[2],
+                           a.f[0], a.f[1], a.f[2], a.r[0], a.r[1], a.r[2], F, force_limit, C->P.f_limit, S::W == 2, a.tag, a.dead);
+    });
     HC_HIP(hipGetLastError());
   }
   return HC_OK;
@@ -614,23 +506,8 @@ int hcp_interpolate(hc_cells *C) {
   int rc = sync_to_device(C); if (rc != HC_OK) return rc;
   if (C->nverts == 0) return HC_OK;
   hc::ProfScope prof(hc::PK_INTERP);
-  const hc_lattice *L = C->L;
-  const LatView v = make_view(L);
-  const PopView pv = make_pops(L);
-  for (int t = 0; t < C->ntypes; t++) {
-    const long n = C->ncells[t] * C->types[t]->host.nv;
-    if (n == 0) continue;
-    const int nv = C->types[t]->host.nv;
-    if (ibm_width(C, t) != HC_IBM_PHI2) { if ((rc = wide_interpolate(C, t, nullptr, 0, g_ibm_per_vertex)) != HC_OK) return rc; continue; }
-    const TypeArrays a = vert_arrays(C, t);
-    if (g_ibm_per_vertex)
-      HC_LAUNCH_POPS(ibm_interpolate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), v, pv, n, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
-                     a.vert_cell, a.tag_all, a.dead);
-    else
-      HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)C->ncells[t]), dim3(nv > 128 ? 256 : 128), v, pv, nv, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
-                     (const int *)nullptr, 1, a.tag, a.dead);
-    HC_HIP(hipGetLastError());
-  }
+  for (int t = 0; t < C->ntypes; t++)
+    if (C->ncells[t] * C->types[t]->host.nv != 0 && (rc = interpolate_type(C, t, nullptr, 0)) != HC_OK) return rc;
   return HC_OK;
 }
 
@@ -673,6 +550,32 @@ int hcl_download_face_velocity(hc_lattice *L, int side, double *host_u) {
 
 int hcp_interpolate_cells(hc_cells *C, int type, const int *slots, int n) { return hcc::interpolate_cells_staged(C, type, slots, n, 1); }
 
+// the width of a type's delta function.  The lattice-side registry (hc::ibm_wide) lets open boundaries and the pre-inlet refuse
+// a lattice that has a type on three or four points
+int hcp_type_set_ibm_kernel(hc_cells *C, int type, int kernel) {
+  HC_REQUIRE(C && type >= 0 && type < C->ntypes, "hcp_type_set_ibm_kernel: unknown cell type");
+  HC_REQUIRE(kernel == HC_IBM_PHI2 || kernel == HC_IBM_PHI3 || kernel == HC_IBM_PHI4, "hcp_type_set_ibm_kernel: kernel must be HC_IBM_PHI2, HC_IBM_PHI3 or HC_IBM_PHI4");
+  const int old = C->ibm_kernel[type];
+  if (kernel == old) return HC_OK;
+  const hc_lattice *L = C->L;
+  if (kernel != HC_IBM_PHI2) {
+    HC_REQUIRE(L->n_slabs == 1, "hcp_type_set_ibm_kernel: a three- or four-point kernel needs the whole domain on one GPU (n_slabs = 1): four points need two halo planes");
+    HC_REQUIRE(L->ob_n == 0, "hcp_type_set_ibm_kernel: the lattice has open-boundary nodes; those and a three- or four-point kernel do not combine");
+    HC_REQUIRE(!hc::in_preinlet_pair(L), "hcp_type_set_ibm_kernel: the lattice is part of a pre-inlet pair; a pre-inlet and a three- or four-point kernel do not combine");
+    HC_REQUIRE(!C->visc_class[type], "hcp_type_set_ibm_kernel: the type has interior viscosity, whose membrane pass walks the eight-node stencil");
+  }
+  if (old == HC_IBM_PHI2) hc::ibm_wide_add(C, L);
+  else if (kernel == HC_IBM_PHI2) hc::ibm_wide_remove_one(C);
+  C->ibm_kernel[type] = kernel;
+  return HC_OK;
+}
+
+int hcp_type_get_ibm_kernel(hc_cells *C, int type, int *kernel) {
+  HC_REQUIRE(C && kernel && type >= 0 && type < C->ntypes, "hcp_type_get_ibm_kernel: bad arguments");
+  *kernel = C->ibm_kernel[type];
+  return HC_OK;
+}
+
 }  // extern "C"
 
 // which: the staging slot the list travels through (a caller that issues several lists in one step gives each its own, so that
@@ -686,14 +589,5 @@ int hcc::interpolate_cells_staged(hc_cells *C, int type, const int *slots, int n
   int *d_slots = nullptr;
   rc = stage_ints(C, which, &d_slots, slots, n); if (rc != HC_OK) return rc;
   hc::ProfScope prof(hc::PK_INTERP);
-  if (ibm_width(C, type) != HC_IBM_PHI2) return wide_interpolate(C, type, d_slots, n, 0);
-  const hc_lattice *L = C->L;
-  const LatView v = make_view(L);
-  const PopView pv = make_pops(L);
-  const TypeArrays a = vert_arrays(C, type);
-  const int nv = C->types[type]->host.nv;
-  HC_LAUNCH_POPS(ibm_interpolate_cell_kernel, dim3((unsigned)n), dim3(nv > 128 ? 256 : 128), v, pv, nv, a.p[0], a.p[1], a.p[2], a.v[0], a.v[1], a.v[2],
-                 (const int *)d_slots, 0, a.tag, a.dead);
-  HC_HIP(hipGetLastError());
-  return HC_OK;
+  return interpolate_type(C, type, d_slots, n);
 }

@@ -11,7 +11,7 @@ build(name, f_limit) returns a dict:
   particles counted}}, open (None, or the Zou-He planes of the lattice: dict(patches=[(kind, box, values)], code [nx][ny][nz],
   val [slots][4]) in the conventions of tests/open_boundary_ref.py).
 
-TILE_CAP, NODE_CAP, NVPT and the x padding are the constants of hemocell_amd/csrc/ibm.hip and common.h
+TILE_CAP, NODE_CAP, NVPT and the x padding are the constants of hemocell_amd/csrc/ibm_common.h and common.h
 (tests/test_ibm_ref_cpu.py checks the copies): a case sits where it claims to only as long as they hold.
 """
 import zlib

@@ -2,7 +2,7 @@
 
 build(name, W, f_limit) returns a case in the format of tests/ibm_cases.py with one more key, kernels {type name: 2, 3 or 4}.
 Cases that do not depend on the caps are those of ibm_cases, taken by import with every type on W (REUSED); the cases around
-the caps of hemocell_amd/csrc/ibm_wide.hip (TILE_CAP3/4, NODE_CAP3/4; tests/test_ibm_wide_cpu.py checks the copies below) and
+the caps of hemocell_amd/csrc/ibm_common.h (TILE_CAP3/4, NODE_CAP3/4; tests/test_ibm_wide_cpu.py checks the copies below) and
 the container with types on different kernels are made here.  expect {cell: {'tiled': bool, 'vol': ..., 'nodes': ...}} is what
 ibm_wide_ref.predict must say of the cell.
 

@@ -1,5 +1,5 @@
 """Restatement of the immersed-boundary coupling with the three- and four-point delta functions (hcp_type_set_ibm_kernel,
-hemocell_amd/csrc/ibm_wide.hip) in extended precision -- test infrastructure only, in the manner of tests/ibm_ref.py, whose
+hemocell_amd/csrc/ibm.hip) in extended precision -- test infrastructure only, in the manner of tests/ibm_ref.py, whose
 helpers and conventions it uses: values in extended precision rounded to double at the end, every sum returned together with
 the sum of the magnitudes of its terms ('<name>_abs').
 
@@ -48,7 +48,7 @@ def base(p, W):
     return (np.floor(p + 0.5) if W == 3 else np.floor(p)).astype(np.int64) - 1
 
 
-# ---- the kernel's doubles, operation for operation (hemocell_amd/csrc/ibm_wide.hip: phi3, phi4)
+# ---- the kernel's doubles, operation for operation (hemocell_amd/csrc/ibm_common.h: phi3, phi4)
 def phi_double(r, W):
     r = np.abs(np.asarray(r, dtype=np.float64))
     with np.errstate(invalid="ignore"):

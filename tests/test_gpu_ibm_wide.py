@@ -1,4 +1,4 @@
-"""The three- and four-point IBM kernels (hcp_type_set_ibm_kernel, hemocell_amd/csrc/ibm_wide.hip) against tests/ibm_wide_ref.py,
+"""The three- and four-point IBM kernels (hcp_type_set_ibm_kernel, hemocell_amd/csrc/ibm.hip) against tests/ibm_wide_ref.py,
 the extended-precision restatement of the standard phi3 / phi4 inside the reference's interpolationCoefficientsPhi2, on the
 crafted geometries of tests/ibm_wide_cases.py.  Every case runs for W = 3 and W = 4 in three kernel forms: per cell (the
 default), per vertex (hc_debug_ibm_per_vertex) and the gather form of the spread (hc_set_reproducible_spread).  The oracle
@@ -18,6 +18,7 @@ Bound: |gpu - ref| <= K 2^-53 abs, K = 16: the rounding figure measured on the C
 (test_ibm_wide_cpu.py::test_rounding_figure_behind_k) does not exceed 4.  Stencil admission is compared exactly: the nodes the
 spread leaves non-zero are the nodes the restatement admits.  Every case must miss the restatement of the other width by 100
 bounds, in the spread and in the interpolation."""
+import ctypes as C
 import os
 import shutil
 import subprocess
@@ -107,6 +108,50 @@ def test_ibm_wide_case(gpu, W, name, form):
         cells.destroy(); Lg.destroy()
         for T in types:
             T.destroy()
+
+
+# ---- hcp_interpolate_cells: the listed-cells launch of the per-cell kernel
+def _listed_cells(gpu, case, calls):
+    """calls: (type index, slots of the type, cells of the case those are); after each call exactly the live particles of the
+    listed cells hold, bit for bit, what the interpolation of the whole container gave them"""
+    lib = gpu.capi.lib()
+    alive, sl = case["alive"], IC.cell_slices(case)
+    _, Lg, cells, types = _setup(gpu, case)
+    try:
+        _set_kernels(cells, case)
+        Lg.collideAndStream(1)
+        cells.interpolateFluidVelocity()
+        full = cells.velocities
+        assert (full[alive] != SENTINEL).all() and (full[~alive] == SENTINEL).all()
+        for ti, slots, listed in calls:
+            cells.velocities = np.full(full.shape, SENTINEL)
+            s = np.ascontiguousarray(slots, dtype=np.int32)
+            gpu.check(lib.hcp_interpolate_cells(cells.ptr, ti, s.ctypes.data_as(C.POINTER(C.c_int)), len(s)))
+            v = cells.velocities
+            rows = np.zeros(len(full), bool)
+            for c in listed:
+                rows[sl[c]] = True
+            rows &= alive
+            assert rows.any() and np.array_equal(v[rows], full[rows])
+            assert (v[~rows] == SENTINEL).all()                                   # other cells and removed particles are not written
+    finally:
+        cells.destroy(); Lg.destroy()
+        for T in types:
+            T.destroy()
+
+
+@pytest.mark.parametrize("W", (PHI3, PHI4))
+def test_listed_cells_on_wide_kernels(gpu, W):
+    """hcp_interpolate_cells on types of three and four points (the slab path, its only caller inside the library, refuses
+    them): one RBC on W and two platelets on the other wide kernel, listed one by one and in reverse; then the incomplete cell
+    of dead_vertices, whose removed particles keep their velocity."""
+    P = gpu.base_parameters()
+    case = WC.build("mixed_rbc3_plt4" if W == PHI3 else "mixed_rbc4_plt3", W, P.f_limit)
+    assert case["kinds"] == ["rbc", "plt", "plt"]
+    _listed_cells(gpu, case, [(1, [1], [2]), (1, [1, 0], [1, 2]), (0, [0], [0])])
+    case = WC.build("dead_vertices", W, P.f_limit)
+    assert case["kinds"][0] == "rbc" and 0 < case["alive"][IC.cell_slices(case)[0]].sum() < IC.NV["rbc"]
+    _listed_cells(gpu, case, [(0, [0], [0])])
 
 
 # ---- hc_iterate

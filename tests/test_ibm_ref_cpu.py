@@ -1,5 +1,5 @@
 """tests/ibm_ref.py and tests/ibm_cases.py without a GPU: the restatement against the CPU oracle on every crafted case, the
-cases' preconditions (ibm_ref.predict against the caps of hemocell_amd/csrc/ibm.hip, so that a changed TILE_CAP or NODE_CAP
+cases' preconditions (ibm_ref.predict against the caps of hemocell_amd/csrc/ibm_common.h, so that a changed TILE_CAP or NODE_CAP
 fails here instead of moving the edges silently), the mutation controls against the right restatement, and the pinned
 constants and visiting orders."""
 import ctypes as C
@@ -27,12 +27,13 @@ def _src(*path):
 
 def test_pinned_constants_and_orders(orc):
     ibm, common, cells_h = _src("hemocell_amd", "csrc", "ibm.hip"), _src("hemocell_amd", "csrc", "common.h"), _src("hemocell_amd", "csrc", "cells.h")
-    assert int(re.search(r"constexpr int TILE_CAP = (\d+);", ibm).group(1)) == IC.TILE_CAP == 18 ** 3
-    assert int(re.search(r"constexpr int NODE_CAP = (\d+);", ibm).group(1)) == IC.NODE_CAP
-    assert int(re.search(r"constexpr int NVPT = (\d+);", ibm).group(1)) == IC.NVPT
+    ibm_h = _src("hemocell_amd", "csrc", "ibm_common.h")
+    assert int(re.search(r"constexpr int TILE_CAP = (\d+);", ibm_h).group(1)) == IC.TILE_CAP == 18 ** 3
+    assert int(re.search(r"constexpr int NODE_CAP = (\d+);", ibm_h).group(1)) == IC.NODE_CAP
+    assert int(re.search(r"constexpr int NVPT = (\d+);", ibm_h).group(1)) == IC.NVPT
     assert int(re.search(r"constexpr int HALO = (\d+);", common).group(1)) == IC.HALO
-    assert ibm.count("dim3(nv > 128 ? 256 : 128)") == 3                      # the block size rule of ibm_cases.BLOCK
-    assert "nb[0] * nb[1] * nb[2] > 64" in ibm and "n >> 3" in ibm            # 64 bricks per wave, 8 XCD ranges
+    assert (ibm + ibm_h).count("dim3(nv > 128 ? 256 : 128)") == 1            # the block size rule of ibm_cases.BLOCK, stated once
+    assert "nb[0] * nb[1] * nb[2] > 64" in ibm_h and "n >> 3" in ibm          # 64 bricks per wave, 8 XCD ranges
     assert "const int idx = i * 4 + j * 2 + k;" in cells_h                    # the kernels' visiting order: OFFSETS
     assert [tuple(o) for o in IR.OFFSETS] == [(i, j, k) for i in range(2) for j in range(2) for k in range(2)]
     # D3Q19: observables_ref.C is the oracle's orc_c (test_observables_cpu checks the copy); the stencil order is the oracle's

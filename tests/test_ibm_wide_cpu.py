@@ -1,6 +1,6 @@
 """tests/ibm_wide_ref.py and tests/ibm_wide_cases.py without a GPU: the properties of the three- and four-point delta
 functions, where their branches and the floor ties sit, the cases' preconditions against the caps of
-hemocell_amd/csrc/ibm_wide.hip (a changed cap fails here instead of moving an edge silently), the mutation control of every
+hemocell_amd/csrc/ibm_common.h (a changed cap fails here instead of moving an edge silently), the mutation control of every
 case (the other width) against the right restatement, the rounding figure behind the bound of the GPU tests, and a facade
 driver that assigns both new names to HemoCellField::kernelMethod.
 
@@ -35,14 +35,14 @@ def _f_limit(orc):
 
 
 def test_pinned_constants():
-    wide, hdr = _src("hemocell_amd", "csrc", "ibm_wide.hip"), _src("include", "hemocell_amd.h")
+    wide, hdr = _src("hemocell_amd", "csrc", "ibm_common.h"), _src("include", "hemocell_amd.h")
     for W in WR.WIDTHS:
         assert int(re.search(r"constexpr int TILE_CAP%d = (\d+);" % W, wide).group(1)) == WC.TILE_CAP[W] == (16 + W) ** 3
         assert int(re.search(r"constexpr int NODE_CAP%d = (\d+);" % W, wide).group(1)) == WC.NODE_CAP[W]
         assert int(re.search(r"#define HC_IBM_PHI%d (\d)" % W, hdr).group(1)) == W
     assert int(re.search(r"#define HC_IBM_PHI2 (\d)", hdr).group(1)) == 2
     assert int(re.search(r"constexpr int NVPT = (\d+);", wide).group(1)) == IC.NVPT
-    assert wide.count("dim3(nv > 128 ? 256 : 128)") == 2                      # the block size rule of ibm_cases.BLOCK
+    assert (wide + _src("hemocell_amd", "csrc", "ibm.hip")).count("dim3(nv > 128 ? 256 : 128)") == 1   # the block size rule of ibm_cases.BLOCK, stated once for all widths
     # LDS of a per-cell workgroup: slots, mask tile / node list, three doubles per node; within the 160 KB of a CU
     for W in WR.WIDTHS:
         lds = 2 * WC.TILE_CAP[W] + max(WC.TILE_CAP[W], 2 * WC.NODE_CAP[W]) + 24 * WC.NODE_CAP[W] + 104
