@@ -238,6 +238,14 @@ SIGNATURES = {
     "hc_packing_reserve_lists": (C.c_int, [VP, C.c_int]),
     "hc_packing_walls": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p,
                                    c_double_p, c_int_p, c_int_p]),
+    "hc_stats_create": (C.c_int, [VP, VP, C.c_int, C.POINTER(VP)]),
+    "hc_stats_destroy": (C.c_int, [VP]),
+    "hc_stats_set_every": (C.c_int, [VP, C.c_int]),
+    "hc_stats_sample": (C.c_int, [VP]),
+    "hc_stats_reset": (C.c_int, [VP]),
+    "hc_stats_samples": (C.c_int, [VP, c_long_p]),
+    "hc_stats_download_fluid": (C.c_int, [VP, C.c_int, c_double_p]),
+    "hc_stats_download_cells": (C.c_int, [VP, C.c_int, C.c_int, c_long_p]),
 }
 
 _lib = None

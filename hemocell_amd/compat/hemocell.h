@@ -870,6 +870,8 @@ class HemoCell {
   HemoCellFields *cellfields = nullptr;
   unsigned int iter = 0;
   PreInlet *preInlet = nullptr;   // hemocell.h:226; deleted before the lattices and containers
+  // set while a hemo::FlowStatistics (compat/flowStatistics.h) is attached: zeroes its sums.  They are not checkpointed.
+  std::function<void()> flowStatisticsReset;
   string outDir, configFile, configElement;
   vector<int> fluidOutputs;
 };
@@ -1204,6 +1206,11 @@ inline void HemoCell::saveCheckPoint() {
     told = true;
     return;
   }
+  if (flowStatisticsReset) {
+    static bool told = false;
+    if (!told) hlog << "(HemoCell) (saveCheckPoint) the running statistics (FlowStatistics) are not checkpointed: a resumed run starts its sums at zero" << endl;
+    told = true;
+  }
   string dir = global.checkpointDirectory; while (dir.size() > 1 && dir[dir.size() - 1] == '/') dir.pop_back();
   if (global.rank == 0) {
     mkpath(dir);
@@ -1388,6 +1395,7 @@ inline void HemoCell::loadCheckPoint() {
   cellfields->number_of_cells = (int)nct;
   iter = (unsigned int)hdr[1];
   lattice->mark_stepped();
+  if (flowStatisticsReset) flowStatisticsReset();   // the sums are not part of the dump
   hlog << "(HemoCell) (loadCheckPoint) resumed at iteration " << iter << endl;
 }
 

@@ -376,6 +376,7 @@ int hcp_envelope(const hc_cells *C, double *share_in_use, long *late_copies) {
 
 int hcp_destroy(hc_cells *C) {
   if (!C) return HC_OK;
+  HC_REQUIRE(!hc::stats_refers_to(C), "hcp_destroy: an hc_stats refers to the container; destroy it first (hc_stats_destroy)");
   (void)hipStreamSynchronize(hc::stream());
   hc::ibm_wide_remove(C);
   delete C;
@@ -838,6 +839,12 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
   const bool solid = C->solidify_on();
   if (solid) { const char *why = solidify_refusal(L); if (why) { hc::set_error(std::string("hc_iterate: ") + why); return HC_ERR_STATE; } }
   struct ForkGuard { ~ForkGuard() { if (hc::forked()) hc::join(); else hc::route(0); } } guard;   // error paths leave one timeline behind
+  // Running statistics (stats.hip): with a handle on the lattice and a cadence, iteration `it` is sampled when
+  // (it + 1) % every == 0, after *iter = it + 1, where the call would return had it ended there.  Such an iteration runs on the
+  // main timeline alone, like the last one of a call: the spread of iteration it + 1 has not been queued, so the sample reads the
+  // force buffer the observers would read.  Without a handle stats_every is 0 and nothing below launches anything.
+  hc_stats *const stats = L->stats;
+  const int stats_every = stats ? hc::stats_every(stats) : 0;
   const bool may_overlap = g_overlap && !C->rep_enabled && !C->brep_enabled;
   bool spread_done = false;
   int rc;
@@ -854,7 +861,8 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     const bool particle_step = it % particle_timescale == 0;
     const bool visc_grid = visc && it % C->visc_grid_every == 0, visc_membrane = visc && it % C->visc_every == 0;
     const bool solid_check = solid && it % C->solid_every == 0;
-    const bool overlap = may_overlap && !particle_step && !visc_grid && !visc_membrane && !solid_check && s + 1 < n;
+    const bool sampled = stats_every > 0 && (it + 1) % stats_every == 0;
+    const bool overlap = may_overlap && !particle_step && !visc_grid && !visc_membrane && !solid_check && !sampled && s + 1 < n;
     if (overlap && (rc = hc::fork()) != HC_OK) return rc;
     if ((rc = hcl_collide_stream_part(L, 0)) != HC_OK) return rc;               // :317
     hcl_step_end(L);
@@ -880,6 +888,7 @@ int hc_iterate(hc_lattice *L, hc_cells *C, long *iter, int n, int particle_times
     }
     if (visc_membrane) { if ((rc = hcp_interior_membrane(C)) != HC_OK) return rc; }   // :353-357
     *iter = it + 1;                                                             // :374 (force zeroing is fused into the collide kernel)
+    if (sampled && !hc::stats_deferred() && (rc = hc::stats_sample(stats, "hc_iterate")) != HC_OK) return rc;
     if (!overlap && (it + 1) % deletion_check_every == 0 && s + 1 < n) { if ((rc = poll_deletions(C, true)) != HC_OK) return rc; }   // on the main timeline only
   }
   if ((rc = poll_deletions(C, true)) != HC_OK) return rc;

@@ -102,7 +102,7 @@ template <class T> struct Staged {
 };
 
 // per-kernel hipEvent timing (hc_profile_*)
-enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_SCALAR, PK_SOLIDIFY_PREPARE, PK_SOLIDIFY_FLAG, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
+enum ProfKernel { PK_COLLIDE = 0, PK_SPREAD, PK_INTERP, PK_ADVANCE, PK_MECH, PK_COLLIDE_BESIDE, PK_LEES_EDWARDS, PK_COLLIDE_VISC, PK_INTERIOR_FIND, PK_INTERIOR_MEMBRANE, PK_SCALAR, PK_SOLIDIFY_PREPARE, PK_SOLIDIFY_FLAG, PK_STATS_FLUID, PK_STATS_DENSITY, PK_STATS_INSIDE, PK_COUNT };   // _BESIDE: collide launches with side-stream work next to them; _VISC: those of the interior-viscosity instantiation, counted a second time (prof_count: no events)
 void prof_count(int kernel);   // one more launch of `kernel`, without a time (while profiling is on)
 struct ProfScope {
   int k; bool on;
@@ -302,6 +302,9 @@ struct hc_lattice {
   // hcl_binding_* call.  hcp_solidify_prepare turns fluid nodes into bounce-back nodes and binding sites while a run is
   // queued: it writes mask, binding and wallbrick on the device, and hmask follows at the end of the call that ran it.
   hc::DevBuf<uint8_t> binding;   // [npad], device
+  // Running statistics (stats.hip): the one hc_stats bound to this lattice, or null.  hc_iterate samples it at its cadence;
+  // hcl_destroy refuses while it is set, so the handle never outlives the lattice.
+  hc_stats *stats = nullptr;
   hc::DevBuf<int> ob_list;      // staging of hcl_plane_velocity's node list
   hc::DevBuf<double> ob_out;    // ... and of its output when the caller's buffer is on the host
 };
@@ -335,6 +338,16 @@ void ibm_wide_remove_one(const void *owner);   // a type went back to two points
 void ibm_wide_remove(const void *owner);       // hcp_destroy
 void ibm_wide_forget(const hc_lattice *L);     // hcl_destroy
 bool ibm_wide(const hc_lattice *L);
+// Running statistics (stats.hip).  stats_fluid_sample (lattice.hip, beside the observers it shares its arithmetic with) queues
+// one sample of the fluid sets `what` selects into the accumulator planes; stats_every / stats_sample are what hc_iterate asks
+// and does at a sampled iteration; stats_refers_to tells hcp_destroy that a handle still names the container.
+int stats_fluid_sample(hc_lattice *L, int what, double *acc_rho_u, double *acc_uu, double *acc_pi, long stride);
+int stats_every(const hc_stats *S);
+void stats_defer(bool on);   // hc_preinlet_iterate: hc_iterate leaves the due samples to the caller ...
+bool stats_deferred();
+int stats_sample_if_due(hc_lattice *L, long iterations_done, const char *who);   // ... who takes them here, after its hand-over
+int stats_sample(hc_stats *S, const char *who);
+bool stats_refers_to(const hc_cells *C);
 }
 
 // slab.hip: HemoCell::iterate / collideAndStream on one x-slab of a multi-GPU run (halo and envelope exchange inside)

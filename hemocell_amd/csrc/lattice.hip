@@ -269,36 +269,23 @@ __global__ void upload_kernel(LatArgs a, const double *aos, int lo_ok, int hi_ok
 #undef M
 }
 
-template <bool OPEN = false>
-__global__ void rho_u_kernel(Args<OPEN> a, double *rho, double *u) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.plane) return;
-  const int x = a.x_begin + blockIdx.y;
-  const int y = p / a.nz, z = p - y * a.nz;
-  const long node = (long)(x + HALO) * a.xs + p;
-  double f[HC_Q];
-  const Moments m = observe<OPEN>(a, x, y, z, node, f);
-  const long o = (long)x * a.plane + p;
-  rho[o] = 1.0 + m.rhoBar;
+// What hcl_download_rho_u reports on a node, from the moments observe() took there: rho = 1 + rhoBar and
+// u = j / rho + (body + IBM force) / 2 with the IBM force of the buffer the next collide reads.  One function for the download
+// kernel and the running statistics (stats_fluid_kernel), so that both form the same bits.
+__device__ __forceinline__ void rho_u_values(const LatArgs &a, const Moments &m, int x, int y, int z, long node, double &rho, double u[3]) {
+  rho = 1.0 + m.rhoBar;
   double bx, by, bz;
   body_at(a, x, y, z, bx, by, bz);
-  u[3 * o] = m.j0 * m.invRho + (bx + a.Fin[3 * node]) / 2.0;
-  u[3 * o + 1] = m.j1 * m.invRho + (by + a.Fin[3 * node + 1]) / 2.0;
-  u[3 * o + 2] = m.j2 * m.invRho + (bz + a.Fin[3 * node + 2]) / 2.0;
+  u[0] = m.j0 * m.invRho + (bx + a.Fin[3 * node]) / 2.0;
+  u[1] = m.j1 * m.invRho + (by + a.Fin[3 * node + 1]) / 2.0;
+  u[2] = m.j2 * m.invRho + (bz + a.Fin[3 * node + 2]) / 2.0;
 }
 
 // Off-equilibrium part of the momentum-flux tensor, as Palabos' momentTemplates::compute_rhoBar_j_PiNeq forms it from the
 // stored populations f_i - t_i: Pi_ab = sum_i c_ia c_ib fbar_i - j_a j_b / rho - cs2 rhoBar delta_ab, components in the
-// order xx, xy, xz, yy, yz, zz.  Output fields only (shear stress, strain rate); nothing on the step path reads it.
-template <bool OPEN = false>
-__global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.plane) return;
-  const int x = a.x_begin + blockIdx.y;
-  const int y = p / a.nz, z = p - y * a.nz;
-  const long node = (long)(x + HALO) * a.xs + p;
-  double f[HC_Q];
-  const Moments m = observe<OPEN>(a, x, y, z, node, f);
+// order xx, xy, xz, yy, yz, zz.  Output fields only (shear stress, strain rate); nothing on the step path reads it.  Shared by
+// the download kernel and the running statistics, as rho_u_values is.
+__device__ __forceinline__ void pi_neq_values(const double f[HC_Q], const Moments &m, double pi[6]) {
   const double rhoBar = m.rhoBar, j0 = m.j0, j1 = m.j1, j2 = m.j2, invRho = m.invRho;
   double xx = 0, xy = 0, xz = 0, yy = 0, yz = 0, zz = 0;
 #define M(Q, CX, CY, CZ)                       \
@@ -311,13 +298,80 @@ __global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
   FOR_Q(M)
 #undef M
   const double cs2 = 1.0 / 3.0;
+  pi[0] = xx - invRho * j0 * j0 - cs2 * rhoBar;
+  pi[1] = xy - invRho * j0 * j1;
+  pi[2] = xz - invRho * j0 * j2;
+  pi[3] = yy - invRho * j1 * j1 - cs2 * rhoBar;
+  pi[4] = yz - invRho * j1 * j2;
+  pi[5] = zz - invRho * j2 * j2 - cs2 * rhoBar;
+}
+
+template <bool OPEN = false>
+__global__ void rho_u_kernel(Args<OPEN> a, double *rho, double *u) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.plane) return;
+  const int x = a.x_begin + blockIdx.y;
+  const int y = p / a.nz, z = p - y * a.nz;
+  const long node = (long)(x + HALO) * a.xs + p;
+  double f[HC_Q];
+  const Moments m = observe<OPEN>(a, x, y, z, node, f);
+  const long o = (long)x * a.plane + p;
+  double r, v[3];
+  rho_u_values(a, m, x, y, z, node, r, v);
+  rho[o] = r;
+  u[3 * o] = v[0]; u[3 * o + 1] = v[1]; u[3 * o + 2] = v[2];
+}
+
+template <bool OPEN = false>
+__global__ void pi_neq_kernel(Args<OPEN> a, double *pi) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.plane) return;
+  const int x = a.x_begin + blockIdx.y;
+  const int y = p / a.nz, z = p - y * a.nz;
+  const long node = (long)(x + HALO) * a.xs + p;
+  double f[HC_Q];
+  const Moments m = observe<OPEN>(a, x, y, z, node, f);
+  double v[6];
+  pi_neq_values(f, m, v);
   const long o = 6 * ((long)x * a.plane + p);
-  pi[o] = xx - invRho * j0 * j0 - cs2 * rhoBar;
-  pi[o + 1] = xy - invRho * j0 * j1;
-  pi[o + 2] = xz - invRho * j0 * j2;
-  pi[o + 3] = yy - invRho * j1 * j1 - cs2 * rhoBar;
-  pi[o + 4] = yz - invRho * j1 * j2;
-  pi[o + 5] = zz - invRho * j2 * j2 - cs2 * rhoBar;
+#pragma unroll
+  for (int k = 0; k < 6; k++) pi[o + k] = v[k];
+}
+
+// One sample of the running statistics (stats.hip): every selected fluid set takes what the two kernels above report on the
+// node, from ONE gather of its populations.  acc holds 16 planes of the node's padded numbering, `stride` doubles apart, in the
+// order rho, u (3), uu (6: xx, xy, xz, yy, yz, zz), pi (6); a plane of a set that was not selected is never touched (and not
+// allocated).  Consecutive lanes hold consecutive z, so every plane is read and written in whole lines like a population.  One
+// thread owns a node and samples are serial on the stream: acc += value in sample order, the host loop's bits.
+template <bool OPEN = false>
+__global__ __launch_bounds__(256) void stats_fluid_kernel(Args<OPEN> a, int what, double *acc_rho_u, double *acc_uu, double *acc_pi, long stride) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.plane) return;
+  const int x = a.x_begin + blockIdx.y;
+  const int y = p / a.nz, z = p - y * a.nz;
+  const long node = (long)(x + HALO) * a.xs + p;
+  double f[HC_Q];
+  const Moments m = observe<OPEN>(a, x, y, z, node, f);
+  if (what & (HC_STATS_RHO_U | HC_STATS_UU)) {
+    double r, u[3];
+    rho_u_values(a, m, x, y, z, node, r, u);
+    if (what & HC_STATS_RHO_U) {
+      acc_rho_u[node] += r;
+#pragma unroll
+      for (int d = 0; d < 3; d++) acc_rho_u[(1 + d) * stride + node] += u[d];
+    }
+    if (what & HC_STATS_UU) {   // the product is rounded, then added (-ffp-contract=off)
+      const double uu[6] = {u[0] * u[0], u[0] * u[1], u[0] * u[2], u[1] * u[1], u[1] * u[2], u[2] * u[2]};
+#pragma unroll
+      for (int k = 0; k < 6; k++) acc_uu[k * stride + node] += uu[k];
+    }
+  }
+  if (what & HC_STATS_PI) {
+    double v[6];
+    pi_neq_values(f, m, v);
+#pragma unroll
+    for (int k = 0; k < 6; k++) acc_pi[k * stride + node] += v[k];
+  }
 }
 
 // Cell::computeVelocity with the body force alone on the listed nodes of the plane coordinate[AXIS] == plane of the lattice `a`:
@@ -787,6 +841,7 @@ int hcl_create(hc_lattice **out, int nx, int ny, int nz, const int periodic[3], 
 
 int hcl_destroy(hc_lattice *L) {
   if (!L) return HC_OK;
+  HC_REQUIRE(!L->stats, "hcl_destroy: an hc_stats refers to the lattice; destroy it first (hc_stats_destroy)");
   hcs::lattice_destroyed(L);
   hc::scalar_lattice_destroyed(L);
   hc::preinlet_pair_forget(L);
@@ -1482,3 +1537,13 @@ double hcl_mlups_bytes_per_node(const hc_lattice *L) {
 }
 
 }  // extern "C"
+
+// stats.hip: one sample of the selected fluid sets, queued on the stream in use.  The arguments are those of the observers at
+// this moment (make_args): the populations the next collide gathers and the force buffer it reads.
+int hc::stats_fluid_sample(hc_lattice *L, int what, double *acc_rho_u, double *acc_uu, double *acc_pi, long stride) {
+  launch_open(L, make_args(L), [&](auto open, const auto &a) {
+    hipLaunchKernelGGL(stats_fluid_kernel<decltype(open)::value>, plane_grid(L, L->nx), dim3(256), 0, hc::stream(), a, what, acc_rho_u, acc_uu, acc_pi, stride);
+  });
+  HC_HIP(hipGetLastError());
+  return HC_OK;
+}

@@ -552,6 +552,11 @@ int hc_preinlet_iterate(hc_preinlet *F, hc_preinlet_cells *X, long *iter, int n,
   HC_REQUIRE(particle_timescale >= 1 && deletion_check_every >= 1, "hc_preinlet_iterate: timescales must be >= 1");
   // an injected cell would arrive with untagged nodes inside it, and the pre-inlet's own field is not built
   HC_REQUIRE(X->dom->L->visc_n == 0 && !(X->pre && X->pre->L->visc_n), "hc_preinlet_iterate: a lattice has interior viscosity enabled; interior viscosity and a pre-inlet do not combine");
+  // Running statistics: a lattice that carries an hc_stats is sampled at the end of the coupled iteration, after the hand-over
+  // and the cell check, which is where this call would return -- not where the lattice's own hc_iterate does.  Without a
+  // handle on either lattice nothing changes and nothing is launched.
+  const bool stats = X->dom->L->stats || (X->pre && X->pre->L->stats);
+  struct Defer { bool on; explicit Defer(bool o) : on(o) { if (on) hc::stats_defer(true); } ~Defer() { if (on) hc::stats_defer(false); } } defer(stats);
   for (int s = 0; s < n; s++) {
     int rc;
     long a = *iter, b = *iter;
@@ -560,6 +565,10 @@ int hc_preinlet_iterate(hc_preinlet *F, hc_preinlet_cells *X, long *iter, int n,
     if (F && (rc = hcl_preinlet_apply(F)) != HC_OK) return rc;
     *iter = b;
     if (b % cells_every == 0 && (rc = hcp_preinlet_apply(X, nullptr, nullptr)) != HC_OK) return rc;
+    if (stats) {
+      if (X->pre && (rc = hc::stats_sample_if_due(X->pre->L, b, "hc_preinlet_iterate")) != HC_OK) return rc;
+      if ((rc = hc::stats_sample_if_due(X->dom->L, b, "hc_preinlet_iterate")) != HC_OK) return rc;
+    }
   }
   return HC_OK;
 }

@@ -190,7 +190,7 @@ int hc_profile_reset(void) {
 }
 int hc_profile_read(const char *kernel, double *total_ms, long *launches) {
   HC_REQUIRE(kernel && total_ms && launches, "hc_profile_read: null pointer");
-  static const char *names[hc::PK_COUNT] = {"collide_stream_alone", "ibm_spread", "ibm_interpolate", "advance", "mechanics", "collide_stream_beside", "lees_edwards", "collide_stream_interior", "interior_find", "interior_membrane", "scalar_step", "solidify_prepare", "solidify_flag"};
+  static const char *names[hc::PK_COUNT] = {"collide_stream_alone", "ibm_spread", "ibm_interpolate", "advance", "mechanics", "collide_stream_beside", "lees_edwards", "collide_stream_interior", "interior_find", "interior_membrane", "scalar_step", "solidify_prepare", "solidify_flag", "stats_fluid", "stats_cell_density", "stats_inside"};
   hc::prof_collect();
   if (std::strcmp(kernel, "collide_stream") == 0) {   // every launch of the collide kernel
     *total_ms = hc::g_prof_ms[hc::PK_COLLIDE] + hc::g_prof_ms[hc::PK_COLLIDE_BESIDE];

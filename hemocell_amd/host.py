@@ -1189,6 +1189,93 @@ class HemoCell:
         check(capi.lib().hc_synchronize())
 
 
+class Statistics:
+    """Running statistics of a lattice and, for the cell sets, of one Cells container on it (hc_stats): sums kept on the
+    device, sampled every `every` iterations inside iterate() -- the handle sits on the lattice, so every path that goes
+    through hc_iterate or hc_preinlet_iterate honours it -- or by sample().  `what` is a mask of the sets below or an
+    iterable of their names.  Arrays are fp64, in the lattice's node order z + nz*(y + ny*x).  Destroy the Statistics
+    before its lattice and container."""
+    RHO_U, UU, PI, CELL_DENSITY, INSIDE = 1, 2, 4, 8, 16
+    SETS = {"rho_u": 1, "uu": 2, "pi": 4, "cell_density": 8, "inside": 16}
+
+    def __init__(self, lattice, cells=None, what=RHO_U | UU | PI, every=0):
+        self.lib = capi.lib()
+        self.lattice, self.cells = lattice, cells
+        if not isinstance(what, int):
+            what = sum(self.SETS[str(w)] for w in set(what))
+        self.what = int(what)
+        self.ptr = C.c_void_p()
+        check(self.lib.hc_stats_create(lattice.ptr, cells.ptr if cells is not None else None, self.what, C.byref(self.ptr)))
+        if every:
+            self.setEvery(every)
+
+    def setEvery(self, every):
+        """sample after every iteration it with (it + 1) % every == 0; 0: explicit samples only"""
+        check(self.lib.hc_stats_set_every(self.ptr, int(every)))
+
+    def sample(self):
+        """one sample now, queued behind the work in flight; does not wait"""
+        check(self.lib.hc_stats_sample(self.ptr))
+
+    def reset(self):
+        check(self.lib.hc_stats_reset(self.ptr))
+
+    @property
+    def samples(self):
+        n = C.c_long()
+        check(self.lib.hc_stats_samples(self.ptr, C.byref(n)))
+        return n.value
+
+    def sums(self, which):
+        """the raw sums of one fluid set: [n][4] (rho, u) for RHO_U, [n][6] (xx, xy, xz, yy, yz, zz) for UU and PI"""
+        which = self.SETS.get(which, which) if isinstance(which, str) else int(which)
+        out = np.empty((self.lattice.n, 4 if which == self.RHO_U else 6), dtype=np.float64)
+        check(self.lib.hc_stats_download_fluid(self.ptr, which, dptr(out)))
+        return out
+
+    def counts(self, which, type_index):
+        """the raw int64 counts [n] of one cell set (CELL_DENSITY or INSIDE) and cell type"""
+        which = self.SETS.get(which, which) if isinstance(which, str) else int(which)
+        out = np.empty(self.lattice.n, dtype=np.int64)
+        check(self.lib.hc_stats_download_cells(self.ptr, which, int(type_index), lptr(out)))
+        return out
+
+    def _mean(self, a):
+        n = self.samples
+        if n == 0:
+            raise HcError("Statistics: no samples yet")
+        return a / float(n)
+
+    def mean_density(self):
+        return self._mean(self.sums(self.RHO_U)[:, 0])
+
+    def mean_velocity(self):
+        return self._mean(self.sums(self.RHO_U)[:, 1:4])
+
+    def velocity_covariance(self):
+        """<u_a u_b> - <u_a><u_b>, [n][6] in the order xx, xy, xz, yy, yz, zz"""
+        u = self.mean_velocity()
+        pairs = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+        return self._mean(self.sums(self.UU)) - np.stack([u[:, a] * u[:, b] for a, b in pairs], axis=1)
+
+    def mean_pi_neq(self):
+        return self._mean(self.sums(self.PI))
+
+    def cell_density(self, type_index):
+        """mean number of vertices of the type whose nearest node this is"""
+        return self._mean(self.counts(self.CELL_DENSITY, type_index).astype(np.float64))
+
+    def hematocrit(self, type_index):
+        """fraction of the samples in which the node lay inside a cell of the type (fluid nodes only; two cells that
+        overlap on a node both count)"""
+        return self._mean(self.counts(self.INSIDE, type_index).astype(np.float64))
+
+    def destroy(self):
+        if self.ptr:
+            check(self.lib.hc_stats_destroy(self.ptr))
+            self.ptr = C.c_void_p()
+
+
 def pipe_mask(nx, ny, nz):
     """analytic cylinder along x replacing tube.stl: radius (ny-2)/2 centred at
     ((ny-1)/2,(nz-1)/2); node solid iff r > R"""

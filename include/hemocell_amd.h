@@ -58,7 +58,7 @@ int hc_side_stream(void **hip_stream);  /* the side stream's hipStream_t, for a 
 int hc_set_overlap(int on);
 /* per-launch hipEvent timing of the dominant kernel (helper/profiler.h:46-77 "collideAndStream" timer) */
 int hc_profile_enable(int on);
-int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics", "lees_edwards" (both kernels of the pass), "collide_stream_interior" (how many of the "collide_stream" launches ran the interior-viscosity instantiation: a count, its time is 0), "interior_find", "interior_membrane" (one entry per pass) */
+int hc_profile_read(const char *kernel, double *total_ms, long *launches); /* "collide_stream" (every launch) = "collide_stream_alone" + "collide_stream_beside" (launches with advance / spread on the side stream next to them), "ibm_spread", "ibm_interpolate", "advance", "mechanics", "lees_edwards" (both kernels of the pass), "collide_stream_interior" (how many of the "collide_stream" launches ran the interior-viscosity instantiation: a count, its time is 0), "interior_find", "interior_membrane" (one entry per pass), "stats_fluid", "stats_cell_density", "stats_inside" (the kernels of one hc_stats sample; the two cell kernels once per cell type) */
 int hc_profile_reset(void);
 /* identifies the build of the dominant kernel: first 16 hex digits of the SHA-256 of csrc/lattice.hip and csrc/d3q19.h (a committed PMC
  * traffic figure is only quoted next to a timing when it was measured on the same kernel) */
@@ -777,6 +777,56 @@ int hc_packing_wall_field(hc_packing *P, double *s_node);
 int hc_packing_reserve_lists(hc_packing *P, int capacity);
 int hc_packing_walls(int n, const double *size, const double *quat, const double *s, const double *normal, const double *douter2,
                      int rotate, double *force, double *torque, double *candidate, int *evals, int *kind);
+
+/* ------------------------------------------------------------------ running statistics
+ * This back end's own.  The reference obtains time-averaged fields by writing whole fields to HDF5 every few thousand
+ * iterations and averaging offline (io/FluidHdf5IO.hh, CellDensity :374-402); here the sums are kept on the device and a
+ * sample is one or two kernels queued behind the step, with no host wait.
+ * An hc_stats is bound to one lattice (n_slabs = 1; one handle per lattice) and, for the cell sets, to one container on
+ * that lattice.  `what` is a mask of the sets; only those are allocated:
+ *   HC_STATS_RHO_U         4 fp64 per node: what hcl_download_rho_u reports (1 + rhoBar; j / rho + (body + IBM force) / 2;
+ *                          open-boundary nodes give the completed moments)
+ *   HC_STATS_UU            6 fp64 per node: u_a u_b of that u (xx, xy, xz, yy, yz, zz), each product rounded, then added
+ *   HC_STATS_PI            6 fp64 per node: what hcl_download_pi_neq reports
+ *   HC_STATS_CELL_DENSITY  one 64-bit count per node and cell type: +1 per live vertex at its nearest node floor(p + 0.5),
+ *                          wrapped on periodic axes and dropped outside the block on the others; removed particles and the
+ *                          vertices of gone cells are not counted
+ *   HC_STATS_INSIDE        one 64-bit count per node and cell type: +1 per COMPLETE cell of the type whose surface encloses
+ *                          the node (the ray cast of the interior-viscosity pass: truncated bounding box, fluid nodes only,
+ *                          odd parity; a cell whose box spans four periods tags nothing).  Two cells that overlap both
+ *                          count, so a node's sum may exceed the number of samples.
+ * The fluid sums are deterministic: one thread owns a node and samples are serial on the stream, so a sum equals the host
+ * loop acc += value in sample order bit for bit.  The counts are integer atomics, hence order independent; being 64-bit they
+ * cannot wrap and no sample cap applies.
+ * hc_stats_set_every(S, every): hc_iterate samples after every iteration `it` with (it + 1) % every == 0, at the point where
+ * the call would return had it ended there, so that a sample equals what hcl_download_rho_u, hcl_download_pi_neq, hcp_download
+ * and hcp_download_alive would report then.  Such an iteration is not overlapped with the side stream.  every = 0 (the
+ * default): explicit samples only.  hc_preinlet_iterate samples a lattice that carries a handle by the same rule at the end of
+ * the coupled iteration, after the fluid hand-over and the cell check -- again where that call would return.  Cell types must
+ * be added to the container before hc_stats_create with a cell set.
+ * hc_stats_sample queues one sample now and does not wait.  hc_stats_reset zeroes the sums and the sample count.
+ * hc_stats_download_fluid(S, set, out): the raw sums of ONE fluid set, [n][k] (k = 4: rho, u; 6; 6) in the reference node
+ * order z + nz * (y + ny * x); hc_stats_download_cells(S, set, type, out): [n] counts of one cell set and type.  Both wait for
+ * the queued work.  Divide by hc_stats_samples for means.
+ * Refused (HC_ERR_ARG / HC_ERR_STATE, message in hc_last_error): a lattice with n_slabs > 1, a second hc_stats on a lattice,
+ * a container bound to another lattice, a cell set without a container, an empty or unknown `what`, a negative cadence, a
+ * type index out of range, a download of a set that was not selected (or of more than one set at once).
+ * Lifetime: hcl_destroy and hcp_destroy REFUSE (HC_ERR_ARG) while an hc_stats refers to the lattice or the container; destroy
+ * the hc_stats first.  The accumulators are not part of any checkpoint. */
+#define HC_STATS_RHO_U 1
+#define HC_STATS_UU 2
+#define HC_STATS_PI 4
+#define HC_STATS_CELL_DENSITY 8
+#define HC_STATS_INSIDE 16
+typedef struct hc_stats hc_stats;
+int hc_stats_create(hc_lattice *L, hc_cells *C_or_null, int what, hc_stats **out);
+int hc_stats_destroy(hc_stats *S);
+int hc_stats_set_every(hc_stats *S, int every);
+int hc_stats_sample(hc_stats *S);
+int hc_stats_reset(hc_stats *S);
+int hc_stats_samples(const hc_stats *S, long *n);
+int hc_stats_download_fluid(hc_stats *S, int set, double *out);
+int hc_stats_download_cells(hc_stats *S, int set, int type, long *out);
 
 #ifdef __cplusplus
 }
