@@ -5,17 +5,9 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from lattice_geometry_cases import O_T, random_populations as _random_populations   # noqa: F401 -- other modules take them from here
 
 pytestmark = pytest.mark.gpu
-
-
-def _random_populations(rng, n, amp=0.02):
-    # fBar = f - t_i around rest equilibrium (0) with a smooth-ish random perturbation
-    return amp * rng.standard_normal((n, 19)) * np.array(O_T())[None, :]
-
-
-def O_T():
-    return [1 / 3] + [1 / 18] * 3 + [1 / 36] * 6 + [1 / 18] * 3 + [1 / 36] * 6
 
 
 def _both_lattices(orc, gpu, nx, ny, nz, periodic, omega, mask=None):
